@@ -195,8 +195,20 @@ def oracle_selfcheck():
     print("oracle_selfcheck.npz:", len(out), "arrays")
 
 
+def ref_live_values():
+    """What tests/test_oracle_vs_ref.py computes live from oracle/_ref/libref_grid.so (tests/ref_live.py)."""
+    import ref_live
+
+    R = O.ref()
+    assert R is not None, "oracle/_ref/libref_grid.so missing (needs /root/reference)"
+    out = ref_live.all_values(O, R)
+    np.savez_compressed(ref_live.FIXTURE, **out)
+    print("ref_live.npz:", len(out), "arrays")
+
+
 if __name__ == "__main__":
     O.build()
     ref_grid()
     ref_mc()
     oracle_selfcheck()
+    ref_live_values()

@@ -121,21 +121,23 @@ def test_tables_vs_reference_digest():
 
 
 def test_tables_vs_reference_live():
-    """The same comparison against the reference header itself, when /root/reference is present (build container)."""
+    """The same comparison against the reference header itself where oracle/_ref/libref_mc.so was built from it;
+    elsewhere the reference side is the committed digest of that header's tables."""
     import ctypes as C
-    import pytest
     so = os.path.join(ROOT, "oracle", "_ref", "libref_mc.so")
-    if not os.path.exists("/root/reference/src/mc_constants.h") or not os.path.exists(so):
-        pytest.skip("reference not present (GPU box): covered by the committed digest")
-    R = C.CDLL(so)
-    for f in (R.ref_mc_edge, R.ref_mc_numverts, R.ref_mc_tri):
-        f.restype = C.c_uint32
+    S = np.load(os.path.join(ROOT, "tests", "golden", "ref_mc_digest.npz"))
     edge, nv, tri = load(os.path.join(ROOT, "oracle", "mc_tables.h"))
-    assert [R.ref_mc_edge(ci) for ci in range(256)] == list(edge)
-    assert [R.ref_mc_numverts(ci) for ci in range(256)] == list(nv)
-    ref = [[R.ref_mc_tri(ci, j) for j in range(16)] for ci in range(256)]
-    la, ta = _digests()(ref)
+    if os.path.exists(so):
+        R = C.CDLL(so)
+        for f in (R.ref_mc_edge, R.ref_mc_numverts, R.ref_mc_tri):
+            f.restype = C.c_uint32
+        ref_edge = [R.ref_mc_edge(ci) for ci in range(256)]
+        ref_nv = [R.ref_mc_numverts(ci) for ci in range(256)]
+        la, ta = _digests()([[R.ref_mc_tri(ci, j) for j in range(16)] for ci in range(256)])
+    else:
+        ref_edge, ref_nv, la, ta = list(S["edge"]), list(S["numverts"]), S["loops_crc"], S["tris_crc"]
+    assert ref_edge == list(edge)
+    assert ref_nv == list(nv)
     lb, tb = _digests()(tri)
     assert np.array_equal(la, lb) and int((ta == tb).sum()) == 98
-    S = np.load(os.path.join(ROOT, "tests", "golden", "ref_mc_digest.npz"))
     assert np.array_equal(la, S["loops_crc"]) and np.array_equal(ta, S["tris_crc"])   # the fixture is current

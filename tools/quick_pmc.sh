@@ -2,7 +2,7 @@
 # usage: bash tools/quick_pmc.sh <out-subdir-of-gpurun_out> [extra bench args]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-qp}; mkdir -p $O; shift
-B="--steps 10 --warmup 3 $*"
+B="--full --steps 10 --warmup 3 $*"
 i=0
 while read -r cset; do
   i=$((i+1))

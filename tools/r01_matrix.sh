@@ -1,6 +1,6 @@
 # (GPU box) the measurement matrix quoted in DESIGN.md §6
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/matrix.txt; : > $O
-run() { tag=$1; shift; timeout -k 10 200 python3 $R/bench.py --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['value']/1e6,1), 'M/s', round(d['ms_per_step'],3), 'ms', d['roofline']['kernel'], round(d['roofline']['mean_launch_ms'],4))" >> $O || echo "$tag FAILED" >> $O; }
+run() { tag=$1; shift; timeout -k 10 200 python3 $R/bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$tag', round(d['value']/1e6,1), 'M/s', round(d['ms_per_step'],3), 'ms', d['roofline']['kernel'], round(d['roofline']['mean_launch_ms'],4))" >> $O || echo "$tag FAILED" >> $O; }
 run fast1M --fast-math
 run f32_256K --particles 262144
 run f64_1M --fp64

@@ -8,15 +8,15 @@ try:
 except Exception as e: print("$n ERR", e)
 PY
 }
-run 1m_precise python3 $R/bench.py --no-cpu-baseline
-run 1m_fast python3 $R/bench.py --no-cpu-baseline --fast-math
-for c in 2 4 8; do PBF_COOP=$c run 1m_coop$c python3 $R/bench.py --no-cpu-baseline; done
-PBF_COOP=4 run 1m_fast_coop4 python3 $R/bench.py --no-cpu-baseline --fast-math
-run 256k python3 $R/bench.py --no-cpu-baseline --particles 262144
-run 1m_fp64 python3 $R/bench.py --no-cpu-baseline --fp64
-run 256k_fp64 python3 $R/bench.py --no-cpu-baseline --fp64 --particles 262144
-run 4m python3 $R/bench.py --no-cpu-baseline --particles 4194304 --steps 100
-PBF_BENCH_FORCE_SLAB=1 run 1m_slab_1rank python3 $R/bench.py --no-cpu-baseline
+run 1m_precise python3 $R/bench.py --full --no-cpu-baseline
+run 1m_fast python3 $R/bench.py --full --no-cpu-baseline --fast-math
+for c in 2 4 8; do PBF_COOP=$c run 1m_coop$c python3 $R/bench.py --full --no-cpu-baseline; done
+PBF_COOP=4 run 1m_fast_coop4 python3 $R/bench.py --full --no-cpu-baseline --fast-math
+run 256k python3 $R/bench.py --full --no-cpu-baseline --particles 262144
+run 1m_fp64 python3 $R/bench.py --full --no-cpu-baseline --fp64
+run 256k_fp64 python3 $R/bench.py --full --no-cpu-baseline --fp64 --particles 262144
+run 4m python3 $R/bench.py --full --no-cpu-baseline --particles 4194304 --steps 100
+PBF_BENCH_FORCE_SLAB=1 run 1m_slab_1rank python3 $R/bench.py --full --no-cpu-baseline
 B=$R/pbf-sph_amd/benchmark
 $B --scene dam-break --particles 1048576 --solver-iter 4 -n 100 -w 20 --no-surface -o "" 2>&1 | grep "Particle-steps\|Frame-time mean" | sed 's/^/cli advance 1M: /'
 $B --scene dam-break --particles 1048576 --solver-iter 4 -n 100 -w 20 --no-surface --resident -o "" 2>&1 | grep "Particle-steps\|Frame-time mean" | sed 's/^/cli resident 1M: /'

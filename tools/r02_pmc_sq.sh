@@ -8,7 +8,7 @@ rocprofv3 -L > $O/counters_list.txt 2>&1 || true
 i=0
 while read -r cset; do
   i=$((i+1))
-  PBF_BENCH_NO_EVENTS=1 timeout -k 10 150 rocprofv3 --kernel-trace --pmc $cset --output-format csv -d $O/pass$i -o run -- python3 $R/bench.py --no-cpu-baseline --steps 10 --warmup 190 > $O/pass$i.log 2>&1 || { echo "pass $i ($cset) failed"; tail -3 $O/pass$i.log; }
+  PBF_BENCH_NO_EVENTS=1 timeout -k 10 150 rocprofv3 --kernel-trace --pmc $cset --output-format csv -d $O/pass$i -o run -- python3 $R/bench.py --full --no-cpu-baseline --steps 10 --warmup 190 > $O/pass$i.log 2>&1 || { echo "pass $i ($cset) failed"; tail -3 $O/pass$i.log; }
   echo "pass $i done: $cset"
 done <<'SETS'
 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU

@@ -15,20 +15,20 @@ PY
 run() { n=$1; shift; "$@" > $O/$n.json 2> $O/$n.err || echo "$n failed"; show $n; }
 for w in $WHAT; do case $w in
 configs)
-  run bench_256k python3 $R/bench.py --steps 20 --warmup 5 --particles 262144
-  run bench_1m python3 $R/bench.py --steps 20 --warmup 5
-  run bench_1m_fp64 python3 $R/bench.py --steps 20 --warmup 5 --fp64
-  run bench_4m_1gpu python3 $R/bench.py --steps 20 --warmup 5 --gpus 1 --scaling strong
+  run bench_256k python3 $R/bench.py --full --steps 20 --warmup 5 --particles 262144
+  run bench_1m python3 $R/bench.py --full --steps 20 --warmup 5
+  run bench_1m_fp64 python3 $R/bench.py --full --steps 20 --warmup 5 --fp64
+  run bench_4m_1gpu python3 $R/bench.py --full --steps 20 --warmup 5 --gpus 1 --scaling strong
   ;;
 ab)
-  run ab_1m_default python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5
-  run ab_1m_fast python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 --fast-math
-  PBF_BENCH_FORCE_SLAB=1 run ab_1m_slab_1rank python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5
-  PBF_PIPELINE=0 run ab_fp64_pipeline0 python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 --fp64
-  PBF_PIPELINE=1 run ab_fp64_pipeline1 python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 --fp64
-  PBF_OVERLAP_DIFFUSE=0 run ab_256k_diffuse_serial python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 --particles 262144
-  PBF_OVERLAP_DIFFUSE=1 run ab_256k_diffuse_overlapped python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 --particles 262144
-  run ab_256k_fp64 python3 $R/bench.py --no-cpu-baseline --steps 20 --warmup 5 --fp64 --particles 262144
+  run ab_1m_default python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5
+  run ab_1m_fast python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --fast-math
+  PBF_BENCH_FORCE_SLAB=1 run ab_1m_slab_1rank python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5
+  PBF_PIPELINE=0 run ab_fp64_pipeline0 python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --fp64
+  PBF_PIPELINE=1 run ab_fp64_pipeline1 python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --fp64
+  PBF_OVERLAP_DIFFUSE=0 run ab_256k_diffuse_serial python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --particles 262144
+  PBF_OVERLAP_DIFFUSE=1 run ab_256k_diffuse_overlapped python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --particles 262144
+  run ab_256k_fp64 python3 $R/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --fp64 --particles 262144
   ;;
 cli)
   B=$R/pbf-sph_amd/benchmark

@@ -6,7 +6,7 @@
 # usage: bash tools/r03_profiles.sh <out-subdir-of-gpurun_out> [extra bench args]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-r3prof}; mkdir -p $O; shift
-B="--steps 20 --warmup 5 $*"
+B="--full --steps 20 --warmup 5 $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o run -- python3 $R/bench.py $B --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/ks.err || { echo kernel-stats failed; tail -3 $O/ks.err; exit 1; }
 echo kernel-stats done
 for cset in FETCH_SIZE WRITE_SIZE; do

@@ -1,7 +1,7 @@
 # (GPU box) kernel-level profile of ONE rank running through the slab machinery (pbf_slab_step, RCCL communicator, no neighbours)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-slabprof}; mkdir -p $O
-PBF_BENCH_FORCE_SLAB=1 PBF_BENCH_NO_EVENTS=1 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/err.log || tail -3 $O/err.log
+PBF_BENCH_FORCE_SLAB=1 PBF_BENCH_NO_EVENTS=1 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o run -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/err.log || tail -3 $O/err.log
 python3 - <<PY
 import pandas as pd
 d=pd.read_csv("$O/ks/run_kernel_stats.csv")
