@@ -94,6 +94,20 @@ int pbf_abi_version(void);
  * is bit-identical.  Unknown names return PBF_ERR_INVALID. */
 int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value);
 
+/* Opt-in surface tension and adhesion after Akinci, Akinci & Teschner 2013, "Versatile Surface Tension and Adhesion for
+ * SPH Fluids" (ACM TOG 32(6)); no reference counterpart.  A post-solve velocity correction that runs last among the extras
+ * (after vorticity confinement and XSPH, whose results it does not change), in three neighbour passes over the final pStar
+ * (solver frame: world / scale, h = pbf_desc.h, m = particle mass, rho0 = 6378):
+ *   rho_i = sum_{j in N(i) u {i}} m_j W_poly6(r)   (obstacles included);   n_i = h sum_{fluid j != i} (m_j / rho_j) grad W_spiky
+ *   v_i += -dt [ sum_fluid j  K_ij (cohesion m_j C(r) x_ij / r + cohesion (n_i - n_j))  +  sum_obstacle b  adhesion m_b A(r) x_ib / r ]
+ * with K_ij = 2 rho0 / (rho_i + rho_j), C Akinci's cohesion spline and A his adhesion kernel (both zero beyond h, A also
+ * below h / 2).  Akinci's boundary pseudo-mass Psi_b is replaced by the obstacle particle's mass.  Obstacle velocities are
+ * unchanged.  The setting persists in the ctx (default 0 / 0 = off; on when either is > 0) and applies to every later
+ * pbf_step / pbf_steps (hipGraph replays included: the coefficients are part of a captured step's key).  NaN, infinite or
+ * negative values return PBF_ERR_INVALID.  Slab mode is not supported: enabling it on a slab-attached ctx, and
+ * pbf_slab_step / a slab-mode finalise with it enabled, return PBF_ERR_STATE. */
+int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion);
+
 /* ---- particle state (replaces the std::vector<Particle>& in/out argument, src/sph.hpp:124) */
 int pbf_upload(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type, const void *mass, const void *pos,
                const void *vel, const void *colour);
@@ -154,7 +168,9 @@ enum pbf_buffer {
                             dry): the particle walks its cells; diagnostic, list gather only */
   PBF_BUF_OMEGA = 4,  /* N[4n]: {omega.xyz, 0}, the vorticity estimate of the last step run with pbf_params.vorticity
                          (opt-in extra, absent from the reference), device order; PBF_ERR_STATE when there is none */
-  PBF_BUF_COUNT_ = 5,
+  PBF_BUF_SURFACE = 5, /* N[4n]: {n.xyz, rho} of the last surface-tension pass (pbf_set_surface_tension), device order; zero
+                          for obstacles; PBF_ERR_STATE when there is none */
+  PBF_BUF_COUNT_ = 6,
 };
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes);
 size_t pbf_table_size(const pbf_ctx *ctx);                /* Morton(extent), sph.hpp:240 */

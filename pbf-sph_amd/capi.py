@@ -17,6 +17,7 @@ FLAG_NO_LDS = 1 << 2
 BUF_KEYS, BUF_TABLE, BUF_PSTAR = 0, 1, 2
 BUF_NBR_COUNT = 3
 BUF_OMEGA = 4
+BUF_SURFACE = 5
 
 
 class PbfError(RuntimeError):
@@ -102,6 +103,7 @@ _lib = None
 _SIGS = {
     "pbf_abi_version": (C.c_int, []),
     "pbf_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "pbf_set_surface_tension": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "pbf_create": (C.c_int, [C.POINTER(Desc), C.POINTER(C.c_void_p)]),
     "pbf_destroy": (None, [C.c_void_p]),
     "pbf_last_error": (C.c_char_p, [C.c_void_p]),
@@ -293,6 +295,19 @@ class Solver:
     def set_option(self, name, value):
         self._chk(self.L.pbf_set_option(self.ctx, name.encode(), int(value)), "pbf_set_option")
         return self
+
+    def set_surface_tension(self, cohesion, adhesion=0.0):
+        """Opt-in surface tension (cohesion gamma) and adhesion to obstacles (beta) after Akinci et al. 2013; 0 / 0 = off.
+        Persists in the solver and applies to every later step (include/pbf_hip.h)."""
+        self._chk(self.L.pbf_set_surface_tension(self.ctx, float(cohesion), float(adhesion)), "pbf_set_surface_tension")
+        return self
+
+    def surface_state(self):
+        """(n,4): {n.xyz, rho} of the last surface-tension pass — surface normal and density per particle, device order
+        (zero for obstacles)"""
+        a = np.empty((self.n, 4), self.dtype)
+        self._chk(self.L.pbf_read_buffer(self.ctx, BUF_SURFACE, _vp(a), a.nbytes), "read surface state")
+        return a
 
     def sync(self):
         self._chk(self.L.pbf_sync(self.ctx), "pbf_sync")

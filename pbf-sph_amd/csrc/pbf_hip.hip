@@ -68,7 +68,7 @@ struct GraphEntry {
 };
 struct GraphKey {
   StepState before;
-  unsigned char params[sizeof(double) * 11 + 32];  // dt, scale, force, bounds, iteration, xsph, vorticity
+  unsigned char params[sizeof(double) * 11 + 32];  // dt, scale, force, bounds, iteration, xsph, vorticity, cohesion, adhesion
   uint64_t n;
   int options[10];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
@@ -146,6 +146,10 @@ struct pbf_ctx {
   uint32_t nbrChunks = 0, nbrChunksOpt = 0;
   bool nbrValid = false;     // the lists describe pstar[pcur] as it is now
   bool omegaValid = false;   // pstar[2] holds the vorticity of the last extras pass (PBF_BUF_OMEGA), same order as the arrays
+  // pbf_set_surface_tension (opt-in, Akinci 2013): coefficients, the two Jacobi fields of its passes (allocated on first use)
+  double cohesion = 0, adhesion = 0;
+  DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE)
+  bool surfaceValid = false;   // surfB holds the record of the last surface-tension pass; invalidated with omegaValid
   // advance() path: the caller's std::vector<Particle> buffer, page-locked in place (hipHostRegister) so the per-frame
   // 56-byte-per-particle upload and download are plain DMA instead of the runtime's pageable staging
   void *regPtr = nullptr;
@@ -470,7 +474,7 @@ template <typename N> int stage_predict(pbf_ctx *ctx, const pbf_params *p) {
   ctx->sorted = false;
   ctx->nbrValid = false;
   ctx->qposValid = false;
-  ctx->omegaValid = false;
+  ctx->omegaValid = false, ctx->surfaceValid = false;
   ctx->pstarInRows = false, ctx->rowsValid = false, ctx->rowsCurrent = false;
   ctx->counted = true;
   ctx->countedTableN = c.tableN;
@@ -787,7 +791,7 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
   // one-workgroup-per-CU launch is then longer than the iteration it hides behind) — measured, profiles/r03_matrix.txt
   overlap = overlap && ctx->overlapDiffuse && ctx->cellDiffuse && !(ctx->desc.flags & PBF_FLAG_NO_LDS) && !timed &&
             (ctx->overlapDiffuseForced || ctx->n >= (size_t(1) << 19));
-  ctx->omegaValid = false;  // (the per-cell sums may be parked in pStar's idle Jacobi partner)
+  ctx->omegaValid = false, ctx->surfaceValid = false;  // (the per-cell sums may be parked in pStar's idle Jacobi partner)
   StageTimer t(ctx, ST_DIFFUSE);
   if (ctx->cellDiffuse && ctx->rowColValid && ctx->rowsValid && ctx->rowDiffuse) {
     // the row-major copy: one wave per segment of 64 x cells, runs staged through LDS, sums applied in place (k_diffuse_rows).
@@ -935,7 +939,7 @@ template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   StageTimer t(ctx, ST_DELTA);
   if (ctx->nbrValid && ctx->nbrRows && ctx->rowsValid && ctx->rowsCurrent) {  // list-driven delta-p on the row-major copy
-    ctx->nbrValid = false, ctx->omegaValid = false;
+    ctx->nbrValid = false, ctx->omegaValid = false, ctx->surfaceValid = false;
     const dim3 g = grid_for(ctx->n), b(BLOCK);
     const RowWalk rw = row_walk<N>(ctx);
     const int rin = ctx->rcur, rout = 1 - rin;
@@ -961,7 +965,7 @@ template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
   const int s = ctx->cur, in = ctx->pcur, out = other_pstar(ctx);
   const GatherMode from = (ctx->nbrValid && !ctx->nbrRows) ? GATHER_FROM_LISTS : GATHER_PLAIN;
   ctx->nbrValid = false;  // delta moves pStar: the lists are stale afterwards
-  ctx->omegaValid = false;  // (and may write the buffer the last vorticity pass left its result in)
+  ctx->omegaValid = false, ctx->surfaceValid = false;  // (and may write the buffer the last vorticity pass left its result in)
   int rc;
   // delta-p's epilogue also writes the quantised copy of the new pStar: the next iteration's list build needs it
   uint2 *qp = ctx->qposValid ? ctx->qpos.as<uint2>() : nullptr;
@@ -979,7 +983,42 @@ template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
   return PBF_OK;
 }
 
-// Opt-in extras (pbf_params.vorticity / .xsph), absent from the reference: see VorticityOp / XsphOp.
+// Opt-in extras (pbf_params.vorticity / .xsph, pbf_set_surface_tension), absent from the reference: see VorticityOp /
+// XsphOp / SurfaceTensionOp.  Off (the default), none of them changes a launch of the step.
+bool surface_on(const pbf_ctx *ctx) { return ctx->cohesion > 0 || ctx->adhesion > 0; }
+bool extras_on(const pbf_ctx *ctx, const pbf_params *p) { return p->vorticity || p->xsph || surface_on(ctx); }
+// its two fields, sized to the particle capacity.  Allocated when the feature is enabled and when an upload grows the
+// capacity, so that no step allocates (a step that allocates is never captured into a hipGraph, and one that does so while
+// being captured turns graph replay off)
+int ensure_surface(pbf_ctx *ctx) {
+  const size_t bytes = ctx->cap * (ctx->fp64 ? sizeof(double4) : sizeof(float4));
+  if (int rc = ensure(ctx, ctx->surfA, bytes)) return rc;
+  return ensure(ctx, ctx->surfB, bytes);
+}
+
+// Surface tension and adhesion (Akinci et al. 2013), last among the extras: density -> A, normals -> B, velocity update.
+template <typename N, bool FAST> int surface_tension_impl(pbf_ctx *ctx, const StepConsts<N> &c) {
+  if (int rc = ensure_surface(ctx)) return rc;
+  const int s = ctx->cur, o = 1 - s;
+  const double h = ctx->desc.h;
+  SurfArgs<N> a{};
+  a.pstar = ctx->pstar[s].as<const vec4<N>>(), a.pos4 = ctx->pos4[s].as<const vec4<N>>();
+  a.type = ctx->type[s].as<const uint8_t>();
+  a.cohesion = N(ctx->cohesion), a.adhesion = N(ctx->adhesion);
+  a.cohFactor = N(32.0 / (M_PI * std::pow(h, 9))), a.h6over64 = N(std::pow(h, 6) / 64.0);
+  a.adhFactor = N(0.007 / std::pow(h, 3.25)), a.adhQuad = N(-4.0 / h);
+  a.fieldOut = ctx->surfA.as<vec4<N>>();
+  if (int rc = launch_gather<N, SurfaceDensityOp<N, FAST>>(ctx, c, a)) return rc;
+  a.fieldIn = ctx->surfA.as<const vec4<N>>(), a.fieldOut = ctx->surfB.as<vec4<N>>();  // Jacobi: A is read while B is written
+  if (int rc = launch_gather<N, SurfaceNormalOp<N, FAST>>(ctx, c, a)) return rc;
+  a.fieldIn = ctx->surfB.as<const vec4<N>>(), a.fieldOut = nullptr;
+  a.velIn = ctx->vel4[s].as<const vec4<N>>(), a.velOut = ctx->vel4[o].as<vec4<N>>();
+  if (int rc = launch_gather<N, SurfaceTensionOp<N, FAST>>(ctx, c, a)) return rc;
+  std::swap(ctx->vel4[s], ctx->vel4[o]);
+  ctx->surfaceValid = true;
+  return PBF_OK;
+}
+
 template <typename N, bool FAST> int extras_impl(pbf_ctx *ctx, const pbf_params *p, const StepConsts<N> &c) {
   const int s = ctx->cur, o = 1 - s;
   const uint8_t *type = ctx->type[s].as<const uint8_t>();
@@ -998,9 +1037,12 @@ template <typename N, bool FAST> int extras_impl(pbf_ctx *ctx, const pbf_params 
     if (int rc = launch_gather<N, XsphOp<N, FAST>>(ctx, c, a3)) return rc;
     std::swap(ctx->vel4[s], ctx->vel4[o]);
   }
+  if (surface_on(ctx)) return surface_tension_impl<N, FAST>(ctx, c);
   return PBF_OK;
 }
 template <typename N> int extras(pbf_ctx *ctx, const pbf_params *p, const StepConsts<N> &c) {
+  if (ctx->slabActive && surface_on(ctx))
+    return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_set_surface_tension(ctx, 0, 0) turns it off)");
   if (ctx->slabActive) return PBF_OK;  // slab mode: pbf_slab_step runs them itself, with the ghost refreshes in between
   return ctx->fast ? extras_impl<N, true>(ctx, p, c) : extras_impl<N, false>(ctx, p, c);
 }
@@ -1009,7 +1051,7 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   const int s = ctx->cur;
-  if (ctx->fuseNextPredict && !(p->vorticity || p->xsph)) {
+  if (ctx->fuseNextPredict && !extras_on(ctx, p)) {
     // finalise(t) + predict(t + 1) in one pass: everything stage_predict does, around one launch
     ctx->fuseNextPredict = false;
     if (int rc = ensure_table(ctx, c.tableN)) return rc;
@@ -1028,13 +1070,13 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
                        ctx->pstarInRows ? ctx->rowSlotOf.as<const uint32_t>() : nullptr);
     ctx->pstarInRows = false, ctx->rowsValid = false, ctx->rowsCurrent = false;
     LAUNCH_CHECK(ctx);
-    ctx->sorted = false, ctx->nbrValid = false, ctx->qposValid = false, ctx->omegaValid = false;
+    ctx->sorted = false, ctx->nbrValid = false, ctx->qposValid = false, ctx->omegaValid = false, ctx->surfaceValid = false;
     ctx->counted = true, ctx->countedTableN = c.tableN;
     ctx->prePredicted = true;
     return PBF_OK;
   }
   ctx->fuseNextPredict = false;
-  if (ctx->pstarInRows && (p->vorticity || p->xsph))  // the extras read the Morton-sorted pStar
+  if (ctx->pstarInRows && extras_on(ctx, p))  // the extras read the Morton-sorted pStar
     if (int rc = materialise_pstar<N>(ctx)) return rc;
   StageTimer t(ctx, ST_FINALISE);
   if (ctx->pstarInRows)
@@ -1052,7 +1094,7 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
     ctx->pcur = s;
   }
   ctx->nbrValid = false;
-  if (p->vorticity || p->xsph) return extras<N>(ctx, p, c);
+  if (extras_on(ctx, p)) return extras<N>(ctx, p, c);
   return PBF_OK;
 }
 
@@ -1097,8 +1139,10 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
                 const N *vel, const N *colour) {
   if (ctx->downloadPending) (void)pbf_download_aos_end(ctx);  // (a download left open: finish it before the state changes)
   if (int rc = ensure_particles(ctx, n)) return rc;
+  if (surface_on(ctx))
+    if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
-  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false;
+  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->surfaceValid = false;
   ctx->ghostsPending = false, ctx->slabActive = false, ctx->prePredicted = false;
   ctx->n = n;
   ctx->hasObstacles = false;
@@ -1156,6 +1200,20 @@ int download_impl(pbf_ctx *ctx, uint64_t *id, uint8_t *type, N *mass, N *pos, N 
 extern "C" {
 
 int pbf_abi_version(void) { return PBF_ABI_VERSION; }
+
+int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!std::isfinite(cohesion) || !std::isfinite(adhesion) || cohesion < 0 || adhesion < 0)
+    return fail(ctx, PBF_ERR_INVALID, "pbf_set_surface_tension: cohesion and adhesion must be finite and >= 0");
+  if (ctx->comm && (cohesion > 0 || adhesion > 0))
+    return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_slab_attach)");
+  ctx->cohesion = cohesion, ctx->adhesion = adhesion;
+  if (surface_on(ctx) && ctx->cap) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return ensure_surface(ctx);
+  }
+  return PBF_OK;
+}
 
 int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return PBF_ERR_INVALID;
@@ -1284,7 +1342,7 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->pstar[0], &ctx->pstar[1], &ctx->pstar[2], &ctx->count, &ctx->table,   &ctx->blockSums,
                    &ctx->permTmp, &ctx->wells,   &ctx->staging, &ctx->bricks, &ctx->brickCtl, &ctx->bigCells,
                    &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->meshV, &ctx->meshN,
-                   &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt};
+                   &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
@@ -1351,8 +1409,10 @@ int pbf_upload_aos(pbf_ctx *ctx, size_t n, const void *particles, const pbf_aos_
   if (n >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "n must be < 2^31");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = ensure_particles(ctx, n)) return rc;
+  if (surface_on(ctx))
+    if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
-  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->n = n;
+  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->n = n, ctx->surfaceValid = false;
   ctx->ghostsPending = false, ctx->slabActive = false;
   ctx->hasObstacles = false;
   if (n == 0) return PBF_OK;
@@ -1484,8 +1544,10 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p) {
   std::memcpy(k.params, v, sizeof(v));
   const uint64_t it = p->iteration;
   const int32_t xv[2] = {p->xsph, p->vorticity};
+  const double st[2] = {ctx->cohesion, ctx->adhesion};  // (pbf_set_surface_tension: a ctx setting, not a pbf_params field)
   std::memcpy(k.params + sizeof(v), &it, 8);
   std::memcpy(k.params + sizeof(v) + 8, xv, 8);
+  std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
   const int opt[10] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
                        int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap)};
@@ -1504,6 +1566,7 @@ int step_maybe_graphed(pbf_ctx *ctx, const pbf_params *p) {
   if (it != ctx->graphs.end()) {
     HIPCHK(ctx, hipGraphLaunch(it->second.exec, ctx->stream));
     restore(ctx, it->second.after);
+    ctx->surfaceValid = surface_on(ctx);  // (the coefficients are part of the key: the replayed step ran the pass iff they are on)
     ctx->graphMisses = 0;
     ctx->graphReplays++;
     return PBF_OK;
@@ -1633,6 +1696,10 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
     case PBF_BUF_OMEGA:
       if (!ctx->omegaValid) return fail(ctx, PBF_ERR_STATE, "no vorticity pass since the arrays last changed (pbf_params.vorticity)");
       src = ctx->pstar[2].p, avail = ctx->n * v;
+      break;
+    case PBF_BUF_SURFACE:
+      if (!ctx->surfaceValid) return fail(ctx, PBF_ERR_STATE, "no surface-tension pass since the arrays last changed (pbf_set_surface_tension)");
+      src = ctx->surfB.p, avail = std::min(ctx->n * v, ctx->surfB.cap);
       break;
     default: return fail(ctx, PBF_ERR_INVALID, "unknown buffer");
   }
@@ -2180,7 +2247,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
     if (int rc = refresh()) return rc;
   }
   if (int rc = stage_finalise<N>(ctx, p)) return rc;
-  if (p->vorticity || p->xsph)
+  if (extras_on(ctx, p))  // (surface tension is refused by pbf_slab_steps before anything runs)
     if (int rc = ctx->fast ? slab_extras_impl<N, true>(ctx, p) : slab_extras_impl<N, false>(ctx, p)) return rc;
   if (int rc = join_diffuse(ctx)) return rc;
   // The copies stay where they are: the next step's predict marks them dead and its sort drops them; whoever looks at
@@ -2310,11 +2377,13 @@ int pbf_slab_step(pbf_ctx *ctx, const pbf_params *p) { return pbf_slab_steps(ctx
 int pbf_slab_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   if (int rc = check(ctx, p, false)) return rc;
   if (!ctx->comm) return fail(ctx, PBF_ERR_STATE, "pbf_slab_step needs pbf_slab_attach first");
+  if (surface_on(ctx))
+    return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_set_surface_tension(ctx, 0, 0) turns it off)");
   // finalise(t) + predict(t + 1) as one kernel between two steps of THIS call (same parameters, same cuts, nothing looks
   // at the state in between) — like pbf_steps
   const bool timed = (ctx->desc.flags & PBF_FLAG_STAGE_TIMING) != 0 &&
                      (((ctx->timingMask >> ST_PREDICT) & 1u) != 0 || ((ctx->timingMask >> ST_FINALISE) & 1u) != 0);
-  const bool fusable = ctx->fusePredict && !timed && !(p->vorticity || p->xsph);
+  const bool fusable = ctx->fusePredict && !timed && !extras_on(ctx, p);
   for (uint32_t i = 0; i < count; ++i) {
     ctx->fuseNextPredict = fusable && i + 1 < count;
     if (int rc = DISPATCH(ctx, slab_step_impl, ctx, p)) {

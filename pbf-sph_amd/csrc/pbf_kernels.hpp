@@ -535,6 +535,7 @@ template <typename N, bool FAST> struct PairGeom {
   N dx, dy, dz;  // a - b
   N r;
   N hr2_over_r;  // (h - r)^2 / r, valid when inSpiky
+  N rinv;        // ~1 / r (the sqrt's by-product), a divide seed where inSpiky (surface tension's x_ij / r)
   bool inH, inSpiky;
 };
 __device__ inline float fast_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
@@ -637,6 +638,7 @@ __device__ inline PairGeom<N, FAST> pair_geom(const vec4<N> &a, const vec4<N> &b
     g.r = g.inSpiky ? d2 * rinv : N(0);
     const N hr = h - g.r;
     g.hr2_over_r = (hr * hr) * rinv;
+    g.rinv = rinv;
   } else {
     const N d2 = bx * bx + by * by + bz * bz;
     N rinv;
@@ -645,6 +647,7 @@ __device__ inline PairGeom<N, FAST> pair_geom(const vec4<N> &a, const vec4<N> &b
     g.inSpiky = g.inH && g.r >= N(EPSILON);
     const N hr = h - g.r;
     g.hr2_over_r = div_seeded(hr * hr, g.r, rinv);  // (only used where inSpiky)
+    g.rinv = rinv;
   }
   return g;
 }
@@ -994,6 +997,170 @@ template <typename N, bool FAST> struct XsphOp {
   __device__ void end(const StepConsts<N> &, const Args &a, uint32_t i) {
     vec4<N> v = va;
     v.x = va.x + ax * N(C_XSPH), v.y = va.y + ay * N(C_XSPH), v.z = va.z + az * N(C_XSPH);
+    a.velOut[i] = v;
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
+// Opt-in surface tension and adhesion after Akinci, Akinci & Teschner 2013 ("Versatile Surface Tension and Adhesion for
+// SPH Fluids", ACM TOG 32(6)), absent from the reference; pbf_set_surface_tension.  Three Jacobi passes over the same
+// neighbour set as the extras above, run last among them, on the final pStar:
+//   SurfaceDensityOp  rho_i = sum_{j in N(i) u {i}} m_j W_poly6(r)                  (obstacles included)   -> A = {0, rho}
+//   SurfaceNormalOp   n_i = h sum_{fluid j != i} (m_j / rho_j) grad W_spiky(x_ij)                           -> B = {n, rho}
+//   SurfaceTensionOp  v_i += -dt [ sum_fluid K_ij (gamma m_j C(r) x_ij / r + gamma (n_i - n_j))
+//                                  + sum_obstacle beta m_b A(r) x_ib / r ],   K_ij = 2 rho0 / (rho_i + rho_j)
+// (the force divided by m_i, which cancels).  C is Akinci's cohesion spline, A his adhesion kernel; Akinci's boundary
+// pseudo-mass Psi_b is replaced by the obstacle particle's own mass m_b.  Obstacles keep their velocity bit for bit and get
+// zero records.  Pairs with r < EPSILON add nothing to a direction term (the spiky convention); the curvature term needs no
+// direction, so a coincident fluid pair still contributes it.  Candidates are loaded as SurfSrc: position, the field of the
+// previous pass, mass and whether the candidate is fluid — its TYPE is read in load(), never skipped (kNeedsCandidateType
+// would drop the obstacles adhesion needs).
+// ------------------------------------------------------------------------------------------------
+template <typename N> struct SurfSrc {
+  vec4<N> p;  // pStar.xyz (.w unused)
+  vec4<N> f;  // the previous pass's record {n, rho}
+  N m;        // pos4.w
+  uint32_t fluid;  // 1 = fluid, 0 = obstacle
+};
+template <typename N> struct SurfArgs {
+  const vec4<N> *pstar, *pos4, *fieldIn;  // fieldIn: unused by the density pass
+  vec4<N> *fieldOut;                      // density / normal pass
+  const vec4<N> *velIn;                   // tension pass
+  vec4<N> *velOut;
+  const uint8_t *type;
+  N cohesion, adhesion;  // gamma, beta
+  N cohFactor;           // 32 / (pi h^9)
+  N h6over64;            // h^6 / 64
+  N adhFactor;           // 0.007 / h^3.25
+  N adhQuad;             // -4 / h
+};
+template <typename N> __device__ inline SurfSrc<N> surf_load(const SurfArgs<N> &a, uint32_t b) {
+  SurfSrc<N> s;
+  s.p = a.pstar[b];
+  s.f = a.fieldIn[b];
+  s.m = a.pos4[b].w;
+  s.fluid = (a.type[b] & 1) ^ 1u;
+  return s;
+}
+
+template <typename N, bool FAST> struct SurfaceDensityOp {
+  using Src = SurfSrc<N>;
+  using Args = SurfArgs<N>;
+  static constexpr bool kNeedsCandidateType = false;
+  static constexpr bool kFilter = true;
+  static constexpr bool kTileable = false;
+  __device__ static Src load(const Args &a, uint32_t b) {
+    Src s;
+    s.p = a.pstar[b];
+    s.f = make_vec4<N>(N(0), N(0), N(0), N(0));  // (no previous field: this pass makes the first)
+    s.m = a.pos4[b].w;
+    s.fluid = 1u;
+    return s;
+  }
+  vec4<N> pa;
+  N rho;
+  __device__ bool near(const StepConsts<N> &c, const Src &b) const { return maybe_within_h<N>(pa, b.p, c.h2filter); }
+  __device__ bool begin(const StepConsts<N> &c, const Args &a, uint32_t i) {
+    rho = N(0);
+    if (c.hasObstacles && a.type[i] != 0) {
+      a.fieldOut[i] = make_vec4<N>(N(0), N(0), N(0), N(0));
+      return false;
+    }
+    pa = a.pstar[i];
+    return true;
+  }
+  __device__ void add(const StepConsts<N> &c, const Src &b) { add_bf(c, b); }
+  __device__ void add_bf(const StepConsts<N> &c, const Src &b, bool valid = true) {
+    const auto g = pair_geom<N, FAST>(pa, b.p, c.h);
+    const N d = (c.h * c.h) - g.r * g.r;
+    const N w = b.m * (c.poly6Factor * (d * d * d));
+    rho += (g.inH && valid) ? w : N(0);
+  }
+  __device__ void end(const StepConsts<N> &, const Args &a, uint32_t i) {
+    a.fieldOut[i] = make_vec4<N>(N(0), N(0), N(0), rho);
+  }
+};
+
+template <typename N, bool FAST> struct SurfaceNormalOp {
+  using Src = SurfSrc<N>;
+  using Args = SurfArgs<N>;
+  static constexpr bool kNeedsCandidateType = false;
+  static constexpr bool kFilter = true;
+  static constexpr bool kTileable = false;
+  __device__ static Src load(const Args &a, uint32_t b) { return surf_load<N>(a, b); }
+  vec4<N> pa;
+  N rho, nx, ny, nz;
+  __device__ bool near(const StepConsts<N> &c, const Src &b) const { return maybe_within_h<N>(pa, b.p, c.h2filter); }
+  __device__ bool begin(const StepConsts<N> &c, const Args &a, uint32_t i) {
+    nx = ny = nz = N(0);
+    if (c.hasObstacles && a.type[i] != 0) {
+      a.fieldOut[i] = make_vec4<N>(N(0), N(0), N(0), N(0));
+      return false;
+    }
+    pa = a.pstar[i], rho = a.fieldIn[i].w;
+    return true;
+  }
+  __device__ void add(const StepConsts<N> &c, const Src &b) { add_bf(c, b); }
+  __device__ void add_bf(const StepConsts<N> &c, const Src &b, bool valid = true) {
+    const auto g = pair_geom<N, FAST>(pa, b.p, c.h);
+    // ONE select on the common factor: an obstacle's rho is 0 (m / 0 = inf) and r = 0 makes hr2_over_r infinite
+    const N s = (g.inSpiky && valid && b.fluid) ? (c.spikyFactor * g.hr2_over_r) * (b.m / b.f.w) : N(0);
+    nx += g.dx * s, ny += g.dy * s, nz += g.dz * s;
+  }
+  __device__ void end(const StepConsts<N> &c, const Args &a, uint32_t i) {
+    a.fieldOut[i] = make_vec4<N>(c.h * nx, c.h * ny, c.h * nz, rho);
+  }
+};
+
+template <typename N, bool FAST> struct SurfaceTensionOp {
+  using Src = SurfSrc<N>;
+  using Args = SurfArgs<N>;
+  static constexpr bool kNeedsCandidateType = false;
+  static constexpr bool kFilter = true;
+  static constexpr bool kTileable = false;
+  __device__ static Src load(const Args &a, uint32_t b) { return surf_load<N>(a, b); }
+  vec4<N> pa, na, va;
+  N sx, sy, sz, cx, cy, cz;
+  N gamma, beta, cohFactor, h6over64, adhFactor, adhQuad;  // (Args' per-launch constants: add_bf does not see Args)
+  __device__ bool near(const StepConsts<N> &c, const Src &b) const { return maybe_within_h<N>(pa, b.p, c.h2filter); }
+  __device__ bool begin(const StepConsts<N> &c, const Args &a, uint32_t i) {
+    sx = sy = sz = cx = cy = cz = N(0);
+    va = a.velIn[i];
+    if (c.hasObstacles && a.type[i] != 0) {
+      a.velOut[i] = va;
+      return false;
+    }
+    pa = a.pstar[i], na = a.fieldIn[i];
+    gamma = a.cohesion, beta = a.adhesion;
+    cohFactor = a.cohFactor, h6over64 = a.h6over64, adhFactor = a.adhFactor, adhQuad = a.adhQuad;
+    return true;
+  }
+  __device__ void add(const StepConsts<N> &c, const Src &b) { add_bf(c, b); }
+  // Branch-free: lanes of a wave see fluid and obstacle candidates, inside and outside h / 2, in any mix.  Every excluded
+  // term is SELECTED to 0, never multiplied by it (the cohesion spline's 1 / r and K_ij are not finite everywhere).
+  __device__ void add_bf(const StepConsts<N> &c, const Src &b, bool valid = true) {
+    const auto g = pair_geom<N, FAST>(pa, b.p, c.h);
+    const N r = g.r, hr = c.h - r;
+    const bool outer = r > N(0.5) * c.h;  // the h / 2 split of both kernels
+    const N q = (hr * hr * hr) * (r * r * r);
+    const N coh = cohFactor * (outer ? q : N(2) * q - h6over64);
+    const N x = fma(adhQuad * r, r, fma(N(6), r, N(-2) * c.h));  // -4 r^2 / h + 6 r - 2 h
+    N y;
+    const N adh = adhFactor * sqrt_rsq(sqrt_rsq(max(x, N(0)), y), y);  // (at r = h, x = 0: the root is 2^-25 resp. 2^-150, not 0)
+    const N K = N(2.0 * RHO) / (na.w + b.f.w);  // (an obstacle's record is 0: finite, and selected away below)
+    const N radial = b.fluid ? gamma * (K * b.m) * coh : (outer ? beta * b.m * adh : N(0));
+    N t;
+    if constexpr (FAST) t = radial * g.rinv;
+    else t = div_seeded(radial, r, g.rinv);
+    t = (g.inSpiky && valid) ? t : N(0);
+    const N k = (g.inH && valid && b.fluid) ? K : N(0);
+    sx += t * g.dx, sy += t * g.dy, sz += t * g.dz;
+    cx += k * (na.x - b.f.x), cy += k * (na.y - b.f.y), cz += k * (na.z - b.f.z);
+  }
+  __device__ void end(const StepConsts<N> &c, const Args &a, uint32_t i) {
+    const N kc = c.dt * a.cohesion;
+    vec4<N> v = va;
+    v.x = va.x - (c.dt * sx + kc * cx), v.y = va.y - (c.dt * sy + kc * cy), v.z = va.z - (c.dt * sz + kc * cz);
     a.velOut[i] = v;
   }
 };
@@ -2070,6 +2237,11 @@ __device__ inline void pin_registers(double4 &v) { asm volatile("" : "+v"(v.x), 
 template <typename N> __device__ inline void pin_registers(PosVel<N> &b) {
   pin_registers(b.p);
   pin_registers(b.v);
+}
+template <typename N> __device__ inline void pin_registers(SurfSrc<N> &b) {
+  pin_registers(b.p);
+  pin_registers(b.f);
+  asm volatile("" : "+v"(b.m), "+v"(b.fluid));
 }
 
 // List-driven gather: the survivors recorded by the previous list build on the same pStar, visited in the recorded

@@ -32,6 +32,7 @@ struct Args {
   bool json = false;                      // --json: one machine-readable line after the summary
   bool allDevices = false;                // --all-devices: EVERY device matching -d becomes one x-slab (RCCL halo)
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
+  double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
 
   Args(size_t defaultIterations, std::string defaultOutput)
       : iterations(defaultIterations), output(std::move(defaultOutput)) {}
@@ -65,7 +66,9 @@ struct Args {
           "      --json                            Print one JSON line with the results\n"
           "      --all-devices                     Use EVERY device matching -d: one x-slab per GPU, ghost-layer\n"
           "                                        exchange over RCCL (implies --resident --no-surface)\n"
-          "      --slabs=[K]                       K slabs on the first matching device (in-process exchange; tests)\n";
+          "      --slabs=[K]                       K slabs on the first matching device (in-process exchange; tests)\n"
+          "      --surface-tension=[g[,b]]         Opt-in surface tension (cohesion g) and adhesion to obstacles (b) after\n"
+          "                                        Akinci et al. 2013; not in the reference. Single device only\n";
   }
 
   // returns false if the program should exit (help / parse error), like the reference's parse()
@@ -103,6 +106,12 @@ struct Args {
         else if (a == "--json") json = true;
         else if (a == "--all-devices") allDevices = true;
         else if (value(i, a, "", "--slabs", v)) slabs = std::stoull(v);
+        else if (value(i, a, "", "--surface-tension", v)) {
+          const size_t comma = v.find(',');
+          cohesion = std::stod(v.substr(0, comma));
+          adhesion = comma == std::string::npos ? 0.0 : std::stod(v.substr(comma + 1));
+          if (!(cohesion >= 0 && adhesion >= 0)) throw std::runtime_error("--surface-tension: values must be >= 0");
+        }
         else if (value(i, a, "-i", "--impl", v)) impl = v;
         else if (value(i, a, "-d", "--devices", v)) devices.push_back(v);
         else if (value(i, a, "-n", "--iter", v)) iterations = std::stoull(v);

@@ -104,7 +104,13 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     else std::cout << "Slab mode (" << devices.size() << " slabs)" << std::endl;
     args.resident = true;
   }
+  const bool surfaceTension = args.cohesion > 0 || args.adhesion > 0;
+  if (surfaceTension && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--surface-tension is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
   sph::hip_impl::Solver<T, N> solver(N(0.1), devices, flags);
+  if (surfaceTension) solver.surfaceTension(N(args.cohesion), N(args.adhesion));
   sph::Result<T, N, sph::vec> result;
   auto frameParam = [&](size_t frame) { return moving ? sph::applyMotionSinXCosZ(param, frame) : param; };
 

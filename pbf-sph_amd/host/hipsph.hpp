@@ -338,6 +338,14 @@ public:
 
   pbf_ctx *context() { return ctx_; }
 
+  // Opt-in surface tension (cohesion) and adhesion to obstacles after Akinci et al. 2013 (pbf_set_surface_tension; no
+  // reference counterpart): persists for every later step, 0 / 0 = off.  A single-device feature (not in slab mode).
+  Solver &surfaceTension(N cohesion, N adhesion = 0) {
+    if (multi()) throw std::runtime_error("surface tension is a single-device feature");
+    check(pbf_set_surface_tension(ctx_, double(cohesion), double(adhesion)), "pbf_set_surface_tension");
+    return *this;
+  }
+
   // ---- device-resident path -------------------------------------------------------------------
   // Several devices: `config` places the cuts (its bounds and scale define the grid columns); the slabs start with
   // equal particle counts.
