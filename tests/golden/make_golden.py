@@ -77,6 +77,38 @@ def ref_grid():
         out[f"fg_{tag}_homes"] = homes
         out[f"fg_{tag}_counts"] = np.array(counts, np.uint64)
         out[f"fg_{tag}_visits"] = np.concatenate(visits) if visits else np.zeros(0, np.uint64)
+    # extent 1023 x 8 x 8: tableN > 2^27, so x - 1 at x = 0 wraps (10 bits) to column 1023, a code INSIDE the table.
+    # Sparse keys in x-columns 0, 1, 1022 and 1023 on shared (y, z) cells, interior keys and keys >= tableN; homes on
+    # all six faces.  The 1.5e8-entry table is not stored: its SHA-256 digest is (tests/ref_live.py digest()).
+    import ref_live
+
+    crng = np.random.default_rng(20261016)
+    ext = (1023, 8, 8)
+    tn = R.ref_make_grid_table(*ext, 0, None, None)
+    yz = [(0, 0), (0, 3), (2, 0), (3, 4), (7, 7), (5, 7), (7, 2), (4, 1)]
+    face = [R.ref_morton_encode(x, y, z) for x in (0, 1, 1022, 1023) for (y, z) in yz for _ in range(2)]
+    inner = [R.ref_morton_encode(int(x), int(y), int(z)) for x, y, z in
+             zip(crng.integers(2, 1022, 300), crng.integers(0, 8, 300), crng.integers(0, 8, 300))]
+    keys = np.sort(np.array(face + inner + [tn - 1, tn, tn + 5, 2 ** 30 - 1], np.uint64))
+    table = np.empty(tn, np.uint64)
+    assert R.ref_make_grid_table(*ext, len(keys), vp(keys), vp(table)) == tn
+    out["gt_c_extent"] = np.array(ext, np.uint64)
+    out["gt_c_keys"] = keys
+    out["gt_c_table_sha256"] = ref_live.digest(table)
+    homes = [R.ref_morton_encode(x, y, z) for x in (0, 1023, 1, 1022) for (y, z) in yz[:5]]
+    homes += [R.ref_morton_encode(int(x), y, z) for x in crng.integers(2, 1022, 3) for (y, z) in ((0, 4), (7, 4), (4, 0), (4, 7))]
+    homes = np.array(homes + [tn, tn + 5], np.uint64)
+    buf = np.empty(4096, np.uint64)
+    visits, counts = [], []
+    for hcell in homes:
+        k = R.ref_foreach_grid(int(hcell), vp(table), tn, vp(buf), len(buf))
+        assert k <= len(buf)
+        counts.append(k)
+        visits.append(buf[:k].copy())
+    del table
+    out["fg_c_homes"] = homes
+    out["fg_c_counts"] = np.array(counts, np.uint64)
+    out["fg_c_visits"] = np.concatenate(visits)
     out["factors"] = np.array([R.ref_poly6_factor_f32(0.1), R.ref_spiky_factor_f32(0.1), R.ref_poly6_factor_f64(0.1),
                                R.ref_spiky_factor_f64(0.1), R.ref_poly6_factor_f32(0.05), R.ref_spiky_factor_f64(0.2)])
     # scene factory: simpleConfigWith2Cubes(2048 | 20000, 4, 500)
