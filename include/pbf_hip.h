@@ -157,6 +157,49 @@ int pbf_stage_lambda(pbf_ctx *ctx, const pbf_params *params);   /* ompsph.hpp:21
 int pbf_stage_delta(pbf_ctx *ctx, const pbf_params *params);    /* ompsph.hpp:235-248 */
 int pbf_stage_finalise(pbf_ctx *ctx, const pbf_params *params); /* ompsph.hpp:256-264 */
 
+/* ---- sources, drains and cell queries on resident state (the rest of sph::Scene, src/sph.hpp:56-79) -----------
+ * What the reference does on the host at the top of advance() (src/omp/ompsph.hpp:93-118) runs here on the device,
+ * before predict, inside every pbf_step / each step of pbf_steps while a source or a drain is set:
+ *   emit   for each source in the order given: size = sqrt(N(rate)), a floor(size) x ceil(size) sheet in x / z at spacing
+ *          h * scale / 2 around `centre` (ompsph.hpp:93-105), id = tag, type fluid, mass 1, the source's colour and
+ *          velocity; appended behind the particles present (i.e. behind the last step's Z-order);
+ *   drain  a fluid particle (freshly emitted ones included, obstacles never) leaves when
+ *          sqrt(dx*dx + dy*dy + dz*dz) < width for any drain (ompsph.hpp:107-118), in N on the stored world position;
+ *          the survivors keep their order (std::remove_if).
+ * The doubles below are rounded to N first.  The settings are copied and persist in the ctx (n = 0 clears); with both
+ * cleared pbf_step makes exactly the launches it makes without them.  While either is set the steps run eagerly (no
+ * hipGraph replay: the particle count changes) and pbf_steps does not fuse finalise(t) with predict(t + 1).
+ * NaN, infinite or negative rate / width, non-finite coordinates and a NULL array with n > 0 return PBF_ERR_INVALID and
+ * leave the setting unchanged.  Growth is bounded by the capacity: the count of the last upload, or — with pbf_reserve
+ * before pbf_upload — the larger of that and the reserve, exactly (the slack the arrays carry beyond a reserve for slab
+ * mode is not counted).  A step whose emission would exceed it returns PBF_ERR_INVALID before anything is launched, the
+ * state untouched.  The emitted count is host
+ * arithmetic; the drained count is data: one host read-back per step while a drain is set and there are particles (a
+ * kernel writes the count and a sequence number to pinned memory, the host polls: no hipStreamSynchronize), none
+ * otherwise.  Slab mode is not supported: setting either on a slab-attached ctx, and pbf_slab_step(s) with either
+ * set, return PBF_ERR_STATE. */
+typedef struct pbf_source { /* sph::Source, src/sph.hpp:62-67 */
+  uint64_t tag;
+  double centre[3], velocity[3], colour[4], rate;
+} pbf_source;
+typedef struct pbf_drain { /* sph::Drain, src/sph.hpp:69-72 */
+  double centre[3], width;
+} pbf_drain;
+int pbf_set_sources(pbf_ctx *ctx, size_t n, const pbf_source *sources);
+int pbf_set_drains(pbf_ctx *ctx, size_t n, const pbf_drain *drains);
+/* emit + drain alone (ompsph.hpp:93-118), like the other pbf_stage_*: exactly what pbf_step does first */
+int pbf_stage_scene(pbf_ctx *ctx, const pbf_params *params);
+/* host read-backs made for drains so far (at most one per step) */
+uint64_t pbf_scene_host_syncs(const pbf_ctx *ctx);
+/* ompsph.hpp:167-186 on the keys and table of the last step: for each world point (3 doubles) the cell code of
+ * point / scale - minExtent; if code + 1 < pbf_table_size, the ids of the FLUID particles of that cell in sorted order,
+ * otherwise none.  counts[i] = the full count of point i, ids[i * cap_per_point ..] its first min(count, cap_per_point)
+ * ids (the rest of the row is not written).  Synchronises: meant for a handful of points per frame.  PBF_ERR_STATE before
+ * any step, after anything that invalidated the table (upload, pbf_stage_scene), with params whose bounds or scale
+ * describe another grid than the last step's (nothing is launched, pbf_table_size unchanged) and in slab mode. */
+int pbf_query_cells(pbf_ctx *ctx, const pbf_params *params, size_t n_points, const double *points, uint32_t *counts,
+                    uint64_t *ids, size_t cap_per_point);
+
 /* ---- introspection (parity tests, Stopwatch analogue) ------------------------------------ */
 enum pbf_buffer {
   PBF_BUF_KEYS = 0,   /* uint32[n]  Morton cell key per particle, current device order */
@@ -228,7 +271,7 @@ typedef struct pbf_slab_cut {
   uint32_t xlo, xhi;           /* owned cell columns [xlo, xhi), grid coordinates of pbf_grid_extent */
   int32_t has_left, has_right; /* is there a rank on that side */
 } pbf_slab_cut;
-int pbf_reserve(pbf_ctx *ctx, size_t capacity); /* room for migrants + copies; call before pbf_upload */
+int pbf_reserve(pbf_ctx *ctx, size_t capacity); /* room for migrants + copies / for what sources emit; call before pbf_upload */
 /* Optional, before the first step: key the particles in a rank-LOCAL x frame (origin = PBF_SLAB_FRAME_MARGIN columns left of this slab's first column), so the grid table covers only the slab + ghost columns instead of Morton(global extent) — on an
  * elongated N-slab box that is 2 M entries per rank instead of 138 M at N = 8.  left_xlo / right_xlo = the
  * xlo of the neighbouring slabs (0 for rank 0 / unused without that neighbour); records are re-keyed on arrival.

@@ -84,6 +84,17 @@ EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_
                           C.c_void_p, C.c_size_t)
 
 
+class Source(C.Structure):
+    """sph::Source (sph.hpp:62-67)"""
+    _fields_ = [("tag", C.c_uint64), ("centre", C.c_double * 3), ("velocity", C.c_double * 3), ("colour", C.c_double * 4),
+                ("rate", C.c_double)]
+
+
+class Drain(C.Structure):
+    """sph::Drain (sph.hpp:69-72)"""
+    _fields_ = [("centre", C.c_double * 3), ("width", C.c_double)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -124,6 +135,11 @@ _SIGS = {
     "pbf_stage_lambda": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
     "pbf_stage_delta": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
     "pbf_stage_finalise": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
+    "pbf_stage_scene": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
+    "pbf_set_sources": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pbf_set_drains": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pbf_scene_host_syncs": (C.c_uint64, [C.c_void_p]),
+    "pbf_query_cells": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pbf_read_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "pbf_table_size": (C.c_size_t, [C.c_void_p]),
     "pbf_selftest_math": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -308,6 +324,44 @@ class Solver:
         a = np.empty((self.n, 4), self.dtype)
         self._chk(self.L.pbf_read_buffer(self.ctx, BUF_SURFACE, _vp(a), a.nbytes), "read surface state")
         return a
+
+    def reserve(self, capacity):
+        """Particle capacity for what sources emit (and, in slab mode, migrants and copies); before upload()."""
+        self._chk(self.L.pbf_reserve(self.ctx, int(capacity)), "pbf_reserve")
+        return self
+
+    def set_sources(self, sources):
+        """sources: list of (tag, centre3, velocity3, colour4, rate) (sph::Source); [] clears.  Emitted on the device at
+        the top of every later step (include/pbf_hip.h)."""
+        arr = (Source * max(len(sources), 1))()
+        for a, (tag, centre, velocity, colour, rate) in zip(arr, sources):
+            a.tag, a.rate = int(tag), float(rate)
+            a.centre[:], a.velocity[:], a.colour[:] = [float(v) for v in centre], [float(v) for v in velocity], [float(v) for v in colour]
+        self._chk(self.L.pbf_set_sources(self.ctx, len(sources), C.byref(arr) if sources else None), "pbf_set_sources")
+        return self
+
+    def set_drains(self, drains):
+        """drains: list of (centre3, width) (sph::Drain); [] clears.  Applied on the device after the sources."""
+        arr = (Drain * max(len(drains), 1))()
+        for a, (centre, width) in zip(arr, drains):
+            a.centre[:], a.width = [float(v) for v in centre], float(width)
+        self._chk(self.L.pbf_set_drains(self.ctx, len(drains), C.byref(arr) if drains else None), "pbf_set_drains")
+        return self
+
+    def scene_host_syncs(self):
+        """host read-backs made for drains so far (at most one per step)"""
+        return int(self.L.pbf_scene_host_syncs(self.ctx))
+
+    def query(self, p, points, cap=4096):
+        """ids of the fluid particles in the cell of each world point, on the last step's table (ompsph.hpp:167-186) ->
+        list of uint64 arrays (the first `cap` ids of a cell); last_query_counts keeps the full counts"""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        counts = np.zeros(len(pts), np.uint32)
+        ids = np.zeros((len(pts), max(cap, 1)), np.uint64)
+        self._chk(self.L.pbf_query_cells(self.ctx, C.byref(p), len(pts), _vp(pts), _vp(counts), _vp(ids), cap),
+                  "pbf_query_cells")
+        self.last_query_counts = counts
+        return [ids[i, :min(int(counts[i]), cap)].copy() for i in range(len(pts))]
 
     def sync(self):
         self._chk(self.L.pbf_sync(self.ctx), "pbf_sync")

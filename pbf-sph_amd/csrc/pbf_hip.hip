@@ -150,6 +150,17 @@ struct pbf_ctx {
   double cohesion = 0, adhesion = 0;
   DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE)
   bool surfaceValid = false;   // surfB holds the record of the last surface-tension pass; invalidated with omegaValid
+  // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
+  // the compaction's per-tile counts and total, the pinned words of the drained count's read-back {total, sequence number}
+  std::vector<pbf_source> sources;
+  std::vector<pbf_drain> drains;
+  uint32_t emitTotal = 0;  // particles the sources emit per step
+  size_t uploaded = 0;     // particles of the last upload: with pbf_reserve the sources' bound is max(reserve, uploaded)
+  DevBuf sceneSources, sceneDrains, drainCounts;
+  uint32_t *hostScene = nullptr;
+  uint32_t sceneSeq = 0;
+  uint64_t sceneHostSyncs = 0;
+  DevBuf queryPoints, queryCounts, queryIds;  // pbf_query_cells
   // advance() path: the caller's std::vector<Particle> buffer, page-locked in place (hipHostRegister) so the per-frame
   // 56-byte-per-particle upload and download are plain DMA instead of the runtime's pageable staging
   void *regPtr = nullptr;
@@ -454,6 +465,26 @@ int upload_wells(pbf_ctx *ctx, const pbf_params *p) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // w is a temporary
   }
   return PBF_OK;
+}
+
+// Spin on a pinned word a kernel writes last (behind a system-scope fence).  A kernel fault or a lost device would leave it
+// unwritten for ever: every ~2 ms of spinning the stream is queried, and an error (or an idle stream without the word) ends
+// the wait.
+int wait_for_word(pbf_ctx *ctx, const volatile uint32_t *word, uint32_t seq, const char *what) {
+  for (uint64_t spin = 1;; ++spin) {
+    if (*word == seq) return PBF_OK;
+    if ((spin & 0xFFFFu) == 0) {
+      const hipError_t e = hipStreamQuery(ctx->stream);
+      if (e == hipSuccess) {
+        if (*word == seq) return PBF_OK;
+        return fail(ctx, PBF_ERR_HIP, std::string(what) + ": the stream went idle without delivering the counts");
+      }
+      if (e != hipErrorNotReady) {
+        ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+        return PBF_ERR_HIP;
+      }
+    }
+  }
 }
 
 // ---- stages ------------------------------------------------------------------------------------
@@ -1098,7 +1129,70 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   return PBF_OK;
 }
 
+// Sources and drains of the scene (ompsph.hpp:93-118) on the resident arrays: append the sources' sheets behind the
+// particles present, then compact the fluid particles no drain reaches into the other array set (the sets swap roles,
+// as in the sort).  The emitted count is host arithmetic; the drained one is data: ONE read-back per call while a drain
+// is set (k_drain_scan -> pinned word, polled).  It is awaited before the move: when every particle survives — the
+// common frame of an outlet nothing has reached yet — the arrays stay where they are and the move is not launched.
+bool scene_on(const pbf_ctx *ctx) { return !ctx->sources.empty() || !ctx->drains.empty(); }
+const char *kSceneSlabError = "sources and drains are not supported in slab mode (pbf_set_sources / pbf_set_drains with n = 0 clear them)";
+
+template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
+  if (!scene_on(ctx)) return PBF_OK;
+  if (ctx->comm || ctx->slabActive || ctx->ghostsPending) return fail(ctx, PBF_ERR_STATE, kSceneSlabError);
+  const size_t e = ctx->emitTotal;
+  // (the arrays carry slab-mode slack beyond a reserve, ensure_particles: not part of what the caller asked for)
+  const size_t limit = ctx->reserve ? std::min(ctx->cap, std::max(ctx->reserve, ctx->uploaded)) : ctx->cap;
+  if (ctx->n + e > limit)
+    return fail(ctx, PBF_ERR_INVALID, "particle capacity exceeded by the sources' emission: call pbf_reserve before pbf_upload");
+  if (e == 0 && (ctx->drains.empty() || ctx->n == 0)) return PBF_OK;
+  if (ctx->downloadPending) (void)pbf_download_aos_end(ctx);
+  if (int rc = join_diffuse(ctx)) return rc;
+  if (int rc = drop_histogram(ctx)) return rc;  // (a predict without its sort: it describes the set before this stage)
+  ctx->sorted = false, ctx->nbrValid = false, ctx->qposValid = false, ctx->omegaValid = false, ctx->surfaceValid = false;
+  ctx->pstarInRows = false, ctx->rowsValid = false, ctx->rowsCurrent = false, ctx->rowColValid = false;
+  ctx->prePredicted = false;
+  const int s = ctx->cur;
+  if (e) {
+    const N spacing = N(ctx->desc.h) * N(p->scale) / 2;  // ompsph.hpp:93
+    hipLaunchKernelGGL((k_scene_emit<N>), grid_for(e), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n), uint32_t(e),
+                       uint32_t(ctx->sources.size()), ctx->sceneSources.as<const SceneSource<N>>(), spacing, arrays<N>(ctx, s, s));
+    LAUNCH_CHECK(ctx);
+    ctx->n += e;
+  }
+  ctx->pcur = s;
+  if (ctx->drains.empty()) return PBF_OK;
+  const uint32_t n = uint32_t(ctx->n), nb = (n + DRAIN_TILE - 1) / DRAIN_TILE, nd = uint32_t(ctx->drains.size());
+  if (int rc = ensure(ctx, ctx->drainCounts, (ctx->cap / DRAIN_TILE + 2) * 4)) return rc;
+  if (!ctx->hostScene) {
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostScene), 64, hipHostMallocDefault));
+    std::memset(ctx->hostScene, 0, 64);
+  }
+  const SceneDrain<N> *drains = ctx->sceneDrains.as<const SceneDrain<N>>();
+  uint32_t *counts = ctx->drainCounts.as<uint32_t>();
+  const uint32_t seq = ++ctx->sceneSeq ? ctx->sceneSeq : ++ctx->sceneSeq;  // (never 0: the pinned word starts there)
+  hipLaunchKernelGGL((k_drain_count<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pos4[s].as<const vec4<N>>(),
+                     ctx->type[s].as<const uint8_t>(), drains, nd, counts);
+  hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, counts, ctx->hostScene, seq);
+  LAUNCH_CHECK(ctx);
+  if (int rc = wait_for_word(ctx, ctx->hostScene + 1, seq, "drain read-back")) return rc;
+  ctx->sceneHostSyncs++;
+  const uint32_t kept = static_cast<volatile uint32_t *>(ctx->hostScene)[0];
+  if (kept > n) return fail(ctx, PBF_ERR_HIP, "drain read-back: more survivors than particles");
+  if (kept == n) return PBF_OK;
+  if (kept) {
+    hipLaunchKernelGGL((k_drain_move<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, arrays<N>(ctx, s, s), arrays<N>(ctx, 1 - s, 1 - s),
+                       drains, nd, counts);
+    LAUNCH_CHECK(ctx);
+    ctx->cur = 1 - s, ctx->pcur = 1 - s;
+  }
+  ctx->n = kept;
+  return PBF_OK;
+}
+
 template <typename N> int step_impl(pbf_ctx *ctx, const pbf_params *p) {
+  if (scene_on(ctx))  // ompsph.hpp:93-118, before the "depleted" test as there: a source refills an empty state
+    if (int rc = stage_scene<N>(ctx, p)) return rc;
   if (ctx->n == 0) return PBF_OK;  // "Particles depleted" (ompsph.hpp:122-126)
   if (ctx->prePredicted) {
     ctx->prePredicted = false;  // the previous step of this pbf_steps call has predicted already (k_finalise_predict)
@@ -1144,7 +1238,7 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
   if (int rc = drop_histogram(ctx)) return rc;
   ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->surfaceValid = false;
   ctx->ghostsPending = false, ctx->slabActive = false, ctx->prePredicted = false;
-  ctx->n = n;
+  ctx->n = n, ctx->uploaded = n;
   ctx->hasObstacles = false;
   if (n == 0) return PBF_OK;
   std::vector<vec4<N>> P(n), V(n), C(n);
@@ -1342,7 +1436,9 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->pstar[0], &ctx->pstar[1], &ctx->pstar[2], &ctx->count, &ctx->table,   &ctx->blockSums,
                    &ctx->permTmp, &ctx->wells,   &ctx->staging, &ctx->bricks, &ctx->brickCtl, &ctx->bigCells,
                    &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->meshV, &ctx->meshN,
-                   &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB};
+                   &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB,
+                   &ctx->sceneSources, &ctx->sceneDrains, &ctx->drainCounts, &ctx->queryPoints, &ctx->queryCounts,
+                   &ctx->queryIds};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
@@ -1353,6 +1449,7 @@ void pbf_destroy(pbf_ctx *ctx) {
   if (ctx->copyStream) (void)hipStreamDestroy(ctx->copyStream);
   if (ctx->evPacked) (void)hipEventDestroy(ctx->evPacked);
   if (ctx->hostCounts) (void)hipHostFree(ctx->hostCounts);
+  if (ctx->hostScene) (void)hipHostFree(ctx->hostScene);
   if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
   if (ctx->regPtr) (void)hipHostUnregister(ctx->regPtr);
   if (ctx->ownStream) (void)hipStreamDestroy(ctx->stream);
@@ -1412,7 +1509,7 @@ int pbf_upload_aos(pbf_ctx *ctx, size_t n, const void *particles, const pbf_aos_
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
-  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->n = n, ctx->surfaceValid = false;
+  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->n = n, ctx->uploaded = n, ctx->surfaceValid = false;
   ctx->ghostsPending = false, ctx->slabActive = false;
   ctx->hasObstacles = false;
   if (n == 0) return PBF_OK;
@@ -1559,7 +1656,7 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p) {
 // seen before, captured the first time it comes by, eager whenever capturing is not possible.
 int step_maybe_graphed(pbf_ctx *ctx, const pbf_params *p) {
   const bool timing = (ctx->desc.flags & PBF_FLAG_STAGE_TIMING) != 0 && ctx->timingMask != 0;
-  if (ctx->graphMode <= 0 || timing || p->n_wells > 0 || ctx->n == 0 || ctx->slabConfigured)
+  if (ctx->graphMode <= 0 || timing || p->n_wells > 0 || ctx->n == 0 || ctx->slabConfigured || scene_on(ctx))
     return DISPATCH(ctx, step_impl, ctx, p);
   const GraphKey key = graph_key(ctx, p);
   auto it = ctx->graphs.find(key);
@@ -1624,7 +1721,8 @@ int pbf_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   // state in between).  Not with stage timing on either entry, hipGraph replay, slabs or a step that may stop early.
   const bool timed = (ctx->desc.flags & PBF_FLAG_STAGE_TIMING) != 0 &&
                      (((ctx->timingMask >> ST_PREDICT) & 1u) != 0 || ((ctx->timingMask >> ST_FINALISE) & 1u) != 0);
-  const bool fusable = ctx->fusePredict && !timed && ctx->graphMode <= 0 && !ctx->slabActive && ctx->n != 0;
+  // (nor across the scene stage: sources and drains change the set between finalise(t) and predict(t + 1))
+  const bool fusable = ctx->fusePredict && !timed && ctx->graphMode <= 0 && !ctx->slabActive && ctx->n != 0 && !scene_on(ctx);
   for (uint32_t i = 0; i < count; ++i) {
     ctx->fuseNextPredict = fusable && i + 1 < count;
     if (int rc = step_maybe_graphed(ctx, p)) {
@@ -1672,6 +1770,137 @@ int pbf_stage_delta(pbf_ctx *ctx, const pbf_params *p) {
 int pbf_stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = check(ctx, p, true)) return rc;
   return DISPATCH(ctx, stage_finalise, ctx, p);
+}
+int pbf_stage_scene(pbf_ctx *ctx, const pbf_params *p) {
+  if (int rc = check(ctx, p, false)) return rc;
+  if (int rc = drop_ghosts(ctx)) return rc;
+  return DISPATCH(ctx, stage_scene, ctx, p);
+}
+
+}  // extern "C"
+
+namespace {
+template <typename N> int upload_sources(pbf_ctx *ctx, const std::vector<pbf_source> &src, uint32_t &total) {
+  std::vector<SceneSource<N>> img(src.size());
+  uint64_t at = 0;
+  for (size_t k = 0; k < src.size(); ++k) {
+    SceneSource<N> &d = img[k];
+    for (int a = 0; a < 3; ++a) d.centre[a] = N(src[k].centre[a]), d.velocity[a] = N(src[k].velocity[a]);
+    for (int a = 0; a < 4; ++a) d.colour[a] = N(src[k].colour[a]);
+    const N size = std::sqrt(static_cast<N>(src[k].rate));  // ompsph.hpp:95-97
+    if (!(size < N(32768))) return fail(ctx, PBF_ERR_INVALID, "pbf_set_sources: rate beyond 2^30 particles per step");
+    d.tag = src[k].tag, d.width = uint32_t(std::floor(size)), d.depth = uint32_t(std::ceil(size)), d.first = uint32_t(at), d.pad = 0;
+    at += uint64_t(d.width) * d.depth;
+    if (at >= (uint64_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "pbf_set_sources: more than 2^31 particles per step");
+  }
+  if (!img.empty()) {
+    if (int rc = ensure(ctx, ctx->sceneSources, img.size() * sizeof(SceneSource<N>))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a step in flight may still read the previous image)
+    HIPCHK(ctx, hipMemcpy(ctx->sceneSources.p, img.data(), img.size() * sizeof(SceneSource<N>), hipMemcpyHostToDevice));
+  }
+  total = uint32_t(at);
+  return PBF_OK;
+}
+template <typename N> int upload_drains(pbf_ctx *ctx, const std::vector<pbf_drain> &drn) {
+  std::vector<SceneDrain<N>> img(drn.size());
+  for (size_t k = 0; k < drn.size(); ++k) {
+    for (int a = 0; a < 3; ++a) img[k].centre[a] = N(drn[k].centre[a]);
+    img[k].width = N(drn[k].width);
+  }
+  if (img.empty()) return PBF_OK;
+  if (int rc = ensure(ctx, ctx->sceneDrains, img.size() * sizeof(SceneDrain<N>))) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  HIPCHK(ctx, hipMemcpy(ctx->sceneDrains.p, img.data(), img.size() * sizeof(SceneDrain<N>), hipMemcpyHostToDevice));
+  return PBF_OK;
+}
+template <typename N>
+int query_impl(pbf_ctx *ctx, const pbf_params *p, size_t np, const double *points, uint32_t *counts, uint64_t *ids, size_t cap) {
+  // make_consts leaves its grid in the ctx: keep the last step's, and refuse params that describe another one (the table,
+  // the keys and the arrays on the device belong to the step's grid; a larger tableN would index beyond them)
+  const uint32_t tableN = ctx->tableN;
+  uint64_t extent[3];
+  double minExtent[3];
+  std::memcpy(extent, ctx->extent, sizeof(extent)), std::memcpy(minExtent, ctx->minExtent, sizeof(minExtent));
+  StepConsts<N> c;
+  const int made = make_consts<N>(ctx, p, c);
+  const bool sameGrid = made == PBF_OK && c.tableN == tableN && std::memcmp(extent, ctx->extent, sizeof(extent)) == 0 &&
+                        std::memcmp(minExtent, ctx->minExtent, sizeof(minExtent)) == 0;
+  ctx->tableN = tableN;
+  std::memcpy(ctx->extent, extent, sizeof(extent)), std::memcpy(ctx->minExtent, minExtent, sizeof(minExtent));
+  if (made != PBF_OK) return made;
+  if (!sameGrid) return fail(ctx, PBF_ERR_STATE, "pbf_query_cells: bounds / scale differ from the last step's");
+  std::vector<N> pts(3 * np);
+  for (size_t k = 0; k < 3 * np; ++k) pts[k] = N(points[k]);
+  if (int rc = ensure(ctx, ctx->queryPoints, pts.size() * sizeof(N))) return rc;
+  if (int rc = ensure(ctx, ctx->queryCounts, np * 4)) return rc;
+  if (int rc = ensure(ctx, ctx->queryIds, std::max<size_t>(np * cap, 1) * 8)) return rc;
+  if (int rc = join_diffuse(ctx)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->queryPoints.p, pts.data(), pts.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
+  const int s = ctx->cur;
+  hipLaunchKernelGGL((k_query_cells<N>), dim3(unsigned(np)), dim3(64), 0, ctx->stream, c, ctx->queryPoints.as<const N>(),
+                     ctx->table.as<const uint32_t>(), ctx->type[s].as<const uint8_t>(), ctx->id[s].as<const uint64_t>(),
+                     ctx->queryCounts.as<uint32_t>(), ctx->queryIds.as<uint64_t>(), uint32_t(cap));
+  LAUNCH_CHECK(ctx);
+  std::vector<uint64_t> rows(ids && cap ? np * cap : 0);
+  HIPCHK(ctx, hipMemcpyAsync(counts, ctx->queryCounts.p, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (!rows.empty()) HIPCHK(ctx, hipMemcpyAsync(rows.data(), ctx->queryIds.p, np * cap * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pts and rows are temporaries; the caller reads the answers)
+  if (!rows.empty())  // only what the kernel wrote reaches the caller: the rest of each row stays as it was
+    for (size_t q = 0; q < np; ++q)
+      std::memcpy(ids + q * cap, rows.data() + q * cap, std::min<size_t>(counts[q], cap) * 8);
+  return PBF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pbf_set_sources(pbf_ctx *ctx, size_t n, const pbf_source *sources) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (n && !sources) return fail(ctx, PBF_ERR_INVALID, "pbf_set_sources: n > 0 but sources == NULL");
+  for (size_t k = 0; k < n; ++k) {
+    bool ok = std::isfinite(sources[k].rate) && sources[k].rate >= 0;
+    for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(sources[k].centre[a]) && std::isfinite(sources[k].velocity[a]);
+    for (int a = 0; a < 4; ++a) ok = ok && std::isfinite(sources[k].colour[a]);
+    if (!ok) return fail(ctx, PBF_ERR_INVALID, "pbf_set_sources: rate must be finite and >= 0, centre / velocity / colour finite");
+  }
+  if (n && ctx->comm) return fail(ctx, PBF_ERR_STATE, kSceneSlabError);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<pbf_source> next(sources, sources + n);
+  uint32_t total = 0;
+  if (int rc = ctx->fp64 ? upload_sources<double>(ctx, next, total) : upload_sources<float>(ctx, next, total)) return rc;
+  ctx->sources.swap(next), ctx->emitTotal = total;
+  return PBF_OK;
+}
+int pbf_set_drains(pbf_ctx *ctx, size_t n, const pbf_drain *drains) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (n && !drains) return fail(ctx, PBF_ERR_INVALID, "pbf_set_drains: n > 0 but drains == NULL");
+  for (size_t k = 0; k < n; ++k) {
+    bool ok = std::isfinite(drains[k].width) && drains[k].width >= 0;
+    for (int a = 0; a < 3; ++a) ok = ok && std::isfinite(drains[k].centre[a]);
+    if (!ok) return fail(ctx, PBF_ERR_INVALID, "pbf_set_drains: width must be finite and >= 0, centre finite");
+  }
+  if (n && ctx->comm) return fail(ctx, PBF_ERR_STATE, kSceneSlabError);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<pbf_drain> next(drains, drains + n);
+  if (int rc = ctx->fp64 ? upload_drains<double>(ctx, next) : upload_drains<float>(ctx, next)) return rc;
+  ctx->drains.swap(next);
+  return PBF_OK;
+}
+uint64_t pbf_scene_host_syncs(const pbf_ctx *ctx) { return ctx ? ctx->sceneHostSyncs : 0; }
+
+int pbf_query_cells(pbf_ctx *ctx, const pbf_params *p, size_t n_points, const double *points, uint32_t *counts, uint64_t *ids,
+                    size_t cap_per_point) {
+  if (int rc = check(ctx, p, false)) return rc;
+  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
+    return fail(ctx, PBF_ERR_STATE, "pbf_query_cells is not supported in slab mode");
+  if (!ctx->sorted) return fail(ctx, PBF_ERR_STATE, "pbf_query_cells needs a step first (no valid cell table)");
+  if (n_points == 0) return PBF_OK;
+  if (!points || !counts || (cap_per_point && !ids)) return fail(ctx, PBF_ERR_INVALID, "pbf_query_cells: NULL argument");
+  if (n_points >= (size_t(1) << 31) || cap_per_point >= (size_t(1) << 31))
+    return fail(ctx, PBF_ERR_INVALID, "pbf_query_cells: too many points / ids per point");
+  for (size_t k = 0; k < 3 * n_points; ++k)
+    if (!std::isfinite(points[k])) return fail(ctx, PBF_ERR_INVALID, "pbf_query_cells: points must be finite");
+  return DISPATCH(ctx, query_impl, ctx, p, n_points, points, counts, ids, cap_per_point);
 }
 
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
@@ -2097,25 +2326,8 @@ template <typename N, bool FAST> int slab_extras_impl(pbf_ctx *ctx, const pbf_pa
   return PBF_OK;
 }
 
-// Spin on the pinned word k_slab_counts writes last.  A kernel fault or a lost device would leave it unwritten for ever:
-// every ~2 ms of spinning the stream is queried, and an error (or an idle stream without the word) ends the wait.
-int wait_for_counts(pbf_ctx *ctx, uint32_t seq) {
-  volatile uint32_t *h = ctx->hostCounts;
-  for (uint64_t spin = 1;; ++spin) {
-    if (h[7] == seq) return PBF_OK;
-    if ((spin & 0xFFFFu) == 0) {
-      const hipError_t e = hipStreamQuery(ctx->stream);
-      if (e == hipSuccess) {
-        if (h[7] == seq) return PBF_OK;
-        return fail(ctx, PBF_ERR_HIP, "slab read-back: the stream went idle without delivering the counts");
-      }
-      if (e != hipErrorNotReady) {
-        ctx->err = std::string("slab read-back: ") + hipGetErrorString(e);
-        return PBF_ERR_HIP;
-      }
-    }
-  }
-}
+// Spin on the pinned word k_slab_counts writes last (wait_for_word).
+int wait_for_counts(pbf_ctx *ctx, uint32_t seq) { return wait_for_word(ctx, ctx->hostCounts + 7, seq, "slab read-back"); }
 
 // One step of the slab protocol, everything on the solver's stream (round 3: ONE select pass, no compaction, no
 // re-histogram, finalise + predict fused between the steps of one pbf_slab_steps call):
@@ -2379,6 +2591,7 @@ int pbf_slab_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   if (!ctx->comm) return fail(ctx, PBF_ERR_STATE, "pbf_slab_step needs pbf_slab_attach first");
   if (surface_on(ctx))
     return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_set_surface_tension(ctx, 0, 0) turns it off)");
+  if (scene_on(ctx)) return fail(ctx, PBF_ERR_STATE, kSceneSlabError);
   // finalise(t) + predict(t + 1) as one kernel between two steps of THIS call (same parameters, same cuts, nothing looks
   // at the state in between) — like pbf_steps
   const bool timed = (ctx->desc.flags & PBF_FLAG_STAGE_TIMING) != 0 &&

@@ -2624,4 +2624,167 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_math64(unsigned long long *_
   if (badB) atomicAdd(&bad[3], badB);
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Scene dynamics on resident state: sources, drains (ompsph.hpp:93-118) and cell queries (ompsph.hpp:167-186).
+// ------------------------------------------------------------------------------------------------
+// One source of the scene (sph.hpp:62-67), its doubles rounded to N; width x depth = floor x ceil of sqrt(N(rate))
+// (ompsph.hpp:95-97); `first` = emitted particles of the sources before it.
+template <typename N> struct SceneSource {
+  N centre[3], velocity[3], colour[4];
+  uint64_t tag;
+  uint32_t width, depth, first, pad;
+};
+template <typename N> struct SceneDrain {
+  N centre[3], width;
+};
+
+// ompsph.hpp:93-105: the sheet of every source, complete records appended at [at, at + total).  One lane per emitted
+// particle, x outer and z inner as the reference's loops; the arithmetic in its order (corner = centre - (w, 0, d) * 0.5 *
+// spacing, position = corner + (x, 0, z) * spacing), so that the bits are the host loop's.
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_scene_emit(uint32_t at, uint32_t total, uint32_t nSources,
+                                                      const SceneSource<N> *__restrict__ sources, N spacing,
+                                                      ParticleArrays<N> dst) {
+  const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+  if (j >= total) return;
+  uint32_t k = 0;
+  while (k + 1 < nSources && sources[k + 1].first <= j) ++k;  // (sources without particles share their successor's `first`)
+  const SceneSource<N> s = sources[k];
+  const uint32_t local = j - s.first, x = local / s.depth, z = local % s.depth;
+  const N hx = N(s.width) * N(0.5) * spacing, hy = N(0) * N(0.5) * spacing, hz = N(s.depth) * N(0.5) * spacing;
+  const N ox = s.centre[0] - hx, oy = s.centre[1] - hy, oz = s.centre[2] - hz;
+  const uint32_t d = at + j;
+  dst.pos4[d] = make_vec4<N>(ox + N(x) * spacing, oy + N(0) * spacing, oz + N(z) * spacing, N(1));
+  dst.vel4[d] = make_vec4<N>(s.velocity[0], s.velocity[1], s.velocity[2], N(0));
+  dst.col4[d] = make_vec4<N>(s.colour[0], s.colour[1], s.colour[2], s.colour[3]);
+  dst.id[d] = s.tag;
+  dst.type[d] = 0;
+}
+
+// ompsph.hpp:107-118: a fluid particle leaves when glm::distance(centre, position) < width for any drain — the root of the
+// plain sum of squares (correctly rounded, no contraction), strictly smaller; obstacles never.
+template <typename N>
+__device__ inline bool scene_drained(const vec4<N> &p, uint8_t type, const SceneDrain<N> *__restrict__ drains, uint32_t nDrains) {
+  if (type == TYPE_OBSTACLE) return false;
+  for (uint32_t k = 0; k < nDrains; ++k) {
+    const N dx = p.x - drains[k].centre[0], dy = p.y - drains[k].centre[1], dz = p.z - drains[k].centre[2];
+    if (sqrt(dx * dx + dy * dy + dz * dz) < drains[k].width) return true;
+  }
+  return false;
+}
+
+// Stable compaction of the survivors (std::remove_if keeps their order, and the counting sort ranks cell-mates by source
+// index): count per tile -> one scan over the tiles -> move.  A tile = DRAIN_TILE consecutive particles, a wave takes
+// 64 x DRAIN_ITEMS of them in rounds of 64 (lane = particle: every 16-byte load of a round is one contiguous run).
+constexpr int DRAIN_ITEMS = 4;
+constexpr int DRAIN_TILE = BLOCK * DRAIN_ITEMS;
+
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_drain_count(uint32_t n, const vec4<N> *__restrict__ pos4,
+                                                       const uint8_t *__restrict__ type,
+                                                       const SceneDrain<N> *__restrict__ drains, uint32_t nDrains,
+                                                       uint32_t *__restrict__ counts) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t waveBase = blockIdx.x * DRAIN_TILE + wave * 64u * DRAIN_ITEMS;
+  uint32_t kept = 0;
+#pragma unroll
+  for (int j = 0; j < DRAIN_ITEMS; ++j) {
+    const uint32_t i = waveBase + j * 64u + lane;
+    if (i < n && !scene_drained<N>(pos4[i], type[i], drains, nDrains)) ++kept;
+  }
+  uint32_t total;
+  block_excl_scan(kept, &total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// exclusive scan of the tiles' survivor counts in place; the total goes into the host's pinned words, followed — behind a
+// system-scope fence — by the sequence number the host polls (the k_slab_counts hand-over)
+__global__ __launch_bounds__(BLOCK) void k_drain_scan(uint32_t nb, uint32_t *__restrict__ counts,
+                                                      volatile uint32_t *__restrict__ host, uint32_t seq) {
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < nb; base += BLOCK) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t v = i < nb ? counts[i] : 0u;
+    uint32_t t;
+    const uint32_t ex = block_excl_scan(v, &t);
+    if (i < nb) counts[i] = carry + ex;
+    carry += t;
+  }
+  if (threadIdx.x == 0) {
+    host[0] = carry;
+    __threadfence_system();
+    host[1] = seq;
+    __threadfence_system();
+  }
+}
+
+// the survivors' complete records {pos4, vel4, col4, id, type}, in array order, into the other array set
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_drain_move(uint32_t n, ParticleArrays<N> src, ParticleArrays<N> dst,
+                                                      const SceneDrain<N> *__restrict__ drains, uint32_t nDrains,
+                                                      const uint32_t *__restrict__ bases) {
+  __shared__ uint32_t waveTot[BLOCK / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t waveBase = blockIdx.x * DRAIN_TILE + wave * 64u * DRAIN_ITEMS;
+  const uint64_t below = (1ull << lane) - 1ull;
+  vec4<N> p[DRAIN_ITEMS];
+  uint64_t keep[DRAIN_ITEMS];
+  uint32_t t = 0;
+#pragma unroll
+  for (int j = 0; j < DRAIN_ITEMS; ++j) {
+    const uint32_t i = waveBase + j * 64u + lane;
+    bool k = false;
+    if (i < n) {
+      p[j] = src.pos4[i];
+      k = !scene_drained<N>(p[j], src.type[i], drains, nDrains);
+    }
+    keep[j] = __ballot(k);
+    t += uint32_t(__builtin_popcountll(keep[j]));
+  }
+  if (lane == 0) waveTot[wave] = t;
+  __syncthreads();
+  uint32_t at = bases[blockIdx.x];
+  for (uint32_t w = 0; w < wave; ++w) at += waveTot[w];
+#pragma unroll
+  for (int j = 0; j < DRAIN_ITEMS; ++j) {
+    const uint32_t i = waveBase + j * 64u + lane;
+    if ((keep[j] >> lane) & 1ull) {
+      const uint32_t d = at + uint32_t(__builtin_popcountll(keep[j] & below));
+      dst.pos4[d] = p[j], dst.vel4[d] = src.vel4[i], dst.col4[d] = src.col4[i];
+      dst.id[d] = src.id[i], dst.type[d] = src.type[i];
+    }
+    at += uint32_t(__builtin_popcountll(keep[j]));
+  }
+}
+
+// ompsph.hpp:167-186: one wave per query point.  The cell code of point / scale - minExtent with k_predict's cell_coord
+// arithmetic; when code + 1 < table length, the cell's run of the sorted arrays 64 at a time, the ids of its FLUID
+// particles compacted by ballot into ids[point * cap ..] (the first `cap` of them), the full count into counts[point].
+template <typename N>
+__global__ __launch_bounds__(64) void k_query_cells(StepConsts<N> c, const N *__restrict__ points,
+                                                    const uint32_t *__restrict__ table, const uint8_t *__restrict__ type,
+                                                    const uint64_t *__restrict__ id, uint32_t *__restrict__ counts,
+                                                    uint64_t *__restrict__ ids, uint32_t cap) {
+  const uint32_t q = blockIdx.x, lane = threadIdx.x;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const N sx = points[3 * q] / c.scale - c.minExtent[0], sy = points[3 * q + 1] / c.scale - c.minExtent[1],
+          sz = points[3 * q + 2] / c.scale - c.minExtent[2];
+  const uint32_t code = morton_encode(static_cast<uint32_t>(cell_coord(sx / c.h)), static_cast<uint32_t>(cell_coord(sy / c.h)),
+                                      static_cast<uint32_t>(cell_coord(sz / c.h)));
+  uint32_t found = 0;
+  if (uint64_t(code) + 1u < uint64_t(c.tableN)) {
+    const uint32_t lo = table[code], hi = table[code + 1u];
+    for (uint32_t base = lo; base < hi; base += 64u) {
+      const uint32_t a = base + lane;
+      const bool fluid = a < hi && type[a] == 0;
+      const uint64_t b = __ballot(fluid);
+      const uint32_t r = found + uint32_t(__builtin_popcountll(b & below));
+      if (fluid && r < cap) ids[size_t(q) * cap + r] = id[a];
+      found += uint32_t(__builtin_popcountll(b));
+    }
+  }
+  if (lane == 0) counts[q] = found;
+}
+
 }  // namespace pbf

@@ -5,8 +5,10 @@
 // compiled in (src/benchmark.cpp:23-25).
 #pragma once
 
+#include <array>
 #include <cstddef>
 #include <iostream>
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -33,6 +35,13 @@ struct Args {
   bool allDevices = false;                // --all-devices: EVERY device matching -d becomes one x-slab (RCCL halo)
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
+
+  struct SourceArg {
+    std::array<double, 7> v;  // x, y, z, vx, vy, vz, rate
+    unsigned long long tag;
+  };
+  std::vector<SourceArg> sources;              // --source=x,y,z,vx,vy,vz,rate[,tag] (repeatable): an inlet (sph::Source)
+  std::vector<std::array<double, 4>> drains;   // --drain=x,y,z,width (repeatable): an outlet (sph::Drain)
 
   Args(size_t defaultIterations, std::string defaultOutput)
       : iterations(defaultIterations), output(std::move(defaultOutput)) {}
@@ -68,7 +77,21 @@ struct Args {
           "                                        exchange over RCCL (implies --resident --no-surface)\n"
           "      --slabs=[K]                       K slabs on the first matching device (in-process exchange; tests)\n"
           "      --surface-tension=[g[,b]]         Opt-in surface tension (cohesion g) and adhesion to obstacles (b) after\n"
-          "                                        Akinci et al. 2013; not in the reference. Single device only\n";
+          "                                        Akinci et al. 2013; not in the reference. Single device only\n"
+          "      --source=[x,y,z,vx,vy,vz,rate[,tag]]  An inlet (repeatable): a floor x ceil sheet of sqrt(rate) particles\n"
+          "                                        per frame at the world point, with that velocity. With --resident\n"
+          "                                        emitted on the GPU, otherwise by advance(). Single device only\n"
+          "      --drain=[x,y,z,width]             An outlet (repeatable): fluid closer than width to the point leaves\n";
+  }
+
+  static std::vector<double> numbers(const std::string &list) {  // "a,b,c" -> {a, b, c}
+    std::vector<double> out;
+    for (size_t at = 0; at <= list.size();) {
+      const size_t comma = std::min(list.find(',', at), list.size());
+      out.push_back(std::stod(list.substr(at, comma - at)));
+      at = comma + 1;
+    }
+    return out;
   }
 
   // returns false if the program should exit (help / parse error), like the reference's parse()
@@ -111,6 +134,31 @@ struct Args {
           cohesion = std::stod(v.substr(0, comma));
           adhesion = comma == std::string::npos ? 0.0 : std::stod(v.substr(comma + 1));
           if (!(cohesion >= 0 && adhesion >= 0)) throw std::runtime_error("--surface-tension: values must be >= 0");
+        }
+        else if (value(i, a, "", "--source", v)) {
+          // (the tag is an id: parsed as an integer of its own, not through a double)
+          size_t commas = 0, last = std::string::npos;
+          for (size_t k = 0; k < v.size(); ++k)
+            if (v[k] == ',') ++commas, last = k;
+          if (commas != 6 && commas != 7) throw std::runtime_error("--source: x,y,z,vx,vy,vz,rate[,tag]");
+          unsigned long long tag = 1000000ull + sources.size();
+          if (commas == 7) {
+            const std::string t = v.substr(last + 1);
+            size_t used = 0;
+            if (t.empty() || t[0] == '-') throw std::runtime_error("--source: tag must be a non-negative integer");
+            tag = std::stoull(t, &used);
+            if (used != t.size()) throw std::runtime_error("--source: tag must be a non-negative integer");
+            v = v.substr(0, last);
+          }
+          const std::vector<double> f = numbers(v);
+          if (!(f[6] >= 0)) throw std::runtime_error("--source: rate must be >= 0");
+          sources.push_back({{f[0], f[1], f[2], f[3], f[4], f[5], f[6]}, tag});
+        }
+        else if (value(i, a, "", "--drain", v)) {
+          const std::vector<double> f = numbers(v);
+          if (f.size() != 4) throw std::runtime_error("--drain: x,y,z,width");
+          if (!(f[3] >= 0)) throw std::runtime_error("--drain: width must be >= 0");
+          drains.push_back({f[0], f[1], f[2], f[3]});
         }
         else if (value(i, a, "-i", "--impl", v)) impl = v;
         else if (value(i, a, "-d", "--devices", v)) devices.push_back(v);

@@ -109,8 +109,26 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cerr << "--surface-tension is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
   }
+  // + inlets and outlets (sph::Scene::sources / drains): with --resident they go to the device (hip_impl::Solver::step),
+  // without it into the Scene advance() gets
+  sph::Scene<T, N, sph::vec> scene;
+  size_t emittedPerFrame = 0;
+  for (const auto &a : args.sources) {
+    const auto &f = a.v;
+    scene.sources.push_back({T(a.tag), {N(f[0]), N(f[1]), N(f[2])}, {N(f[3]), N(f[4]), N(f[5])}, {N(0.2), N(0.6), N(1), N(1)}, N(f[6])});
+    const N size = std::sqrt(N(f[6]));  // ompsph.hpp:95-97
+    emittedPerFrame += size_t(std::floor(size)) * size_t(std::ceil(size));
+  }
+  for (const auto &f : args.drains) scene.drains.push_back({T(0), {N(f[0]), N(f[1]), N(f[2])}, N(f[3]), N(0)});
+  const bool dynamic = !scene.sources.empty() || !scene.drains.empty();
+  if (dynamic && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--source / --drain are single-device features: they cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
   sph::hip_impl::Solver<T, N> solver(N(0.1), devices, flags);
   if (surfaceTension) solver.surfaceTension(N(args.cohesion), N(args.adhesion));
+  // the resident arrays grow by what the inlets emit: room for every frame of the run
+  if (args.resident && emittedPerFrame) solver.reserve(particles.size() + (args.warmup + args.iterations) * emittedPerFrame);
   sph::Result<T, N, sph::vec> result;
   auto frameParam = [&](size_t frame) { return moving ? sph::applyMotionSinXCosZ(param, frame) : param; };
 
@@ -119,11 +137,11 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   if (args.resident) solver.upload(particles, &param);
   auto one = [&](size_t frame) {
     if (args.resident) {
-      solver.step(frameParam(frame));
-      if (param.surface) result.mesh = solver.surface(frameParam(frame));
+      solver.step(frameParam(frame), scene);
+      if (param.surface && solver.count()) result.mesh = solver.surface(frameParam(frame));
       solver.sync();  // per-frame time like the reference's blocking advance()
     } else {
-      result = solver.advance(frameParam(frame), {}, particles);
+      result = solver.advance(frameParam(frame), scene, particles);
     }
   };
   for (size_t frame = 0; frame < args.warmup; ++frame) {

@@ -191,6 +191,8 @@ class Solver final : public sph::Solver<T, N, V> {
   pbf_ctx *ctx_ = nullptr;
   const N h_;
   std::vector<double> wells_;
+  std::vector<pbf_source> sources_;  // what step() last pushed to the context (pbf_set_sources / pbf_set_drains)
+  std::vector<pbf_drain> drains_;
   // ---- several devices (slabs): ctx_ aliases slabs_[0] ----------------------------------------
   std::vector<int> devices_;
   std::vector<pbf_ctx *> slabs_;
@@ -382,12 +384,16 @@ public:
     }
     attached_ = true;
   }
+  // The whole Scene rides along: wells in the params, sources and drains pushed to the context when they differ from what
+  // it last got (emitted / drained on the device at the top of each of the `count` steps, as `count` advance() calls would).
   void step(const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene = {}, uint32_t count = 1) {
     const pbf_params p = params(config, scene);
     if (!multi()) {
+      pushScene(scene);
       check(pbf_steps(ctx_, &p, count), "pbf_steps");
       return;
     }
+    if (!scene.sources.empty() || !scene.drains.empty()) throw std::runtime_error("sources and drains are a single-device feature");
     if (!attached_) throw std::runtime_error("step() before upload()");
     for (uint32_t k = 0; k < count; ++k) {
       if (rebalanceEvery_ && frame_ && frame_ % rebalanceEvery_ == 0) rebalance();
@@ -408,6 +414,11 @@ public:
     cuts_ = nw;
     for (size_t g = 0; g < slabs_.size(); ++g) checkOn(g, pbf_slab_set_cuts(slabs_[g], cuts_.data()), "pbf_slab_set_cuts");
     return true;
+  }
+  // Particle capacity for what sources will emit on the resident path; before upload().
+  void reserve(size_t capacity) {
+    if (multi()) throw std::runtime_error("reserve() is a single-device call (upload() sizes the slabs itself)");
+    check(pbf_reserve(ctx_, capacity), "pbf_reserve");
   }
   void sync() {
     if (!multi()) check(pbf_sync(ctx_), "pbf_sync");
@@ -466,10 +477,13 @@ public:
       std::this_thread::sleep_for(std::chrono::milliseconds(5));
       return {};
     }
+    // (sources and drains were applied above, on the host: the device step gets the wells alone)
+    sph::Scene<T, N, V> wellsOnly;
+    wellsOnly.wells = scene.wells;
     if (multi()) {
       if (!scene.queries.empty()) throw std::runtime_error("queries are a single-device feature");
       upload(xs, &config);
-      step(config, scene, 1);
+      step(config, wellsOnly, 1);
       sph::Result<T, N, V> result;
       if (config.surface) result.mesh = surface(config, scene);  // every slab its part of the lattice, concatenated
       download(xs);
@@ -478,11 +492,11 @@ public:
     PhaseClock clk(phase_);
     upload(xs);
     clk.lap(0);
-    step(config, scene, 1);
+    step(config, wellsOnly, 1);
     if (phase_.on) sync();
     clk.lap(1);
     sph::Result<T, N, V> result;
-    if (!scene.queries.empty()) result.queries = query(config, scene);
+    if (!scene.queries.empty()) result.queries = queryHost(config, scene);
     if (config.surface) {  // ompsph.hpp:277-477
       // the mesh lands in page-locked staging (one DMA); its three vectors are then built on host threads WHILE the
       // particles travel back over PCIe
@@ -582,12 +596,63 @@ private:
   };
 
 public:
+  // ids of the fluid particles in the cell that holds each query point (ompsph.hpp:167-186), answered on the device from
+  // the keys and table of the last step (pbf_query_cells); the cells are those of the predicted positions, as in the
+  // reference.  Single device.
+  std::vector<sph::QueryResult<T, N, V>> query(const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene) {
+    if (multi()) throw std::runtime_error("queries are a single-device feature");
+    const size_t nq = scene.queries.size();
+    std::vector<sph::QueryResult<T, N, V>> out(nq);
+    if (!nq) return out;
+    const pbf_params p = params(config, scene);
+    std::vector<double> pts(3 * nq);
+    for (size_t i = 0; i < nq; ++i)
+      pts[3 * i] = scene.queries[i].point.x, pts[3 * i + 1] = scene.queries[i].point.y, pts[3 * i + 2] = scene.queries[i].point.z;
+    std::vector<uint32_t> counts(nq);
+    size_t cap = 64;  // (a cell of the rest state holds ~8 particles; a fuller one is asked for again with its own count)
+    std::vector<uint64_t> ids(nq * cap);
+    check(pbf_query_cells(ctx_, &p, nq, pts.data(), counts.data(), ids.data(), cap), "pbf_query_cells");
+    const size_t most = *std::max_element(counts.begin(), counts.end());
+    if (most > cap) {
+      cap = most, ids.resize(nq * cap);
+      check(pbf_query_cells(ctx_, &p, nq, pts.data(), counts.data(), ids.data(), cap), "pbf_query_cells");
+    }
+    for (size_t i = 0; i < nq; ++i) {
+      const uint64_t *row = ids.data() + i * cap;
+      out[i] = {scene.queries[i].id, scene.queries[i].point, std::vector<T>(row, row + counts[i])};
+    }
+    return out;
+  }
 
 private:
-  // ids of the fluid particles in the cell that holds each query point (ompsph.hpp:167-186);
-  // the cells are those of the predicted positions, as in the reference.
-  std::vector<sph::QueryResult<T, N, V>> query(const sph::SphParams<T, N, V> &config,
-                                               const sph::Scene<T, N, V> &scene) {
+  void pushScene(const sph::Scene<T, N, V> &scene) {
+    std::vector<pbf_source> src(scene.sources.size());
+    for (size_t k = 0; k < src.size(); ++k) {
+      const auto &q = scene.sources[k];
+      src[k] = pbf_source{uint64_t(q.tag), {q.centre.x, q.centre.y, q.centre.z}, {q.velocity.x, q.velocity.y, q.velocity.z},
+                          {q.colour.x, q.colour.y, q.colour.z, q.colour.w}, double(q.rate)};
+    }
+    std::vector<pbf_drain> drn(scene.drains.size());
+    for (size_t k = 0; k < drn.size(); ++k) {
+      const auto &q = scene.drains[k];
+      drn[k] = pbf_drain{{q.centre.x, q.centre.y, q.centre.z}, double(q.width)};
+    }
+    auto same = [](const auto &a, const auto &b) {
+      return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
+    };
+    if (!same(src, sources_)) {
+      check(pbf_set_sources(ctx_, src.size(), src.data()), "pbf_set_sources");
+      sources_.swap(src);
+    }
+    if (!same(drn, drains_)) {
+      check(pbf_set_drains(ctx_, drn.size(), drn.data()), "pbf_set_drains");
+      drains_.swap(drn);
+    }
+  }
+
+  // advance()'s own query: downloads keys, ids and types and bisects them on the host
+  std::vector<sph::QueryResult<T, N, V>> queryHost(const sph::SphParams<T, N, V> &config,
+                                                   const sph::Scene<T, N, V> &scene) {
     const size_t n = pbf_count(ctx_);
     std::vector<uint32_t> keys(n);
     std::vector<uint64_t> ids(n);
