@@ -20,6 +20,7 @@
 #include "pbf_tiles.hpp"
 #include "pbf_mc.hpp"
 #include "pbf_comm.hpp"
+#include "pbf_state.hpp"
 
 using namespace pbf;
 
@@ -50,17 +51,17 @@ struct EventPair {
 }  // namespace
 
 // hipGraph replay of the resident step (option "graph"): everything host-side that one step reads AND leaves behind —
-// which physical buffer plays which role, the validity flags — so that a replayed graph can put the context into the
-// state the captured step left it in.  Also the key under which a captured step is found again.
+// which physical buffer plays which role, the whole derived state — so that a replayed graph (or the rollback of a failed
+// capture) can put the context into the state the captured step left (found) it in.  Inside a GraphKey it is also the key
+// under which a captured step is found again; there `st` is reduced to DerivedState::step_key.
 struct StepState {
-  int cur, pcur;
-  uint32_t flags;  // sorted | counted << 1 | nbrValid << 2 | qposValid << 3 | hasObstacles << 4
-  uint32_t tableN, countedTableN, gatherSeq;
+  DerivedState st;
+  bool hasObstacles;
+  uint32_t tableN, gatherSeq;
   uint64_t extent[3];
   double minExtent[3];
-  void *bufs[15];  // pos4[2] vel4[2] col4[2] id[2] type[2] key[2] pstar[3]
+  void *bufs[15];  // pos4[2] vel4[2] col4[2] id[2] type[2] key[2] pstar[3]: a step swaps them around
   size_t caps[15];
-  bool operator<(const StepState &o) const { return std::memcmp(this, &o, sizeof(StepState)) < 0; }
 };
 struct GraphEntry {
   hipGraphExec_t exec = nullptr;
@@ -86,10 +87,7 @@ struct pbf_ctx {
   size_t n = 0;
   size_t cap = 0;        // particle capacity of the SoA buffers
   bool hasObstacles = false;
-  bool sorted = false;   // keys/table valid for the current arrays
-  bool counted = false;  // cell histogram of the current keys is in `count` (set by predict, consumed by sort)
-  int cur = 0;           // which of the two particle-array sets is live
-  int pcur = 0;          // which pstar buffer is live
+  DerivedState st;       // which buffer holds the truth: roles and validity flags, changed through its events only (pbf_state.hpp)
   // two sets (sort scatters from one into the other)
   DevBuf pos4[2], vel4[2], col4[2], id[2], type[2], key[2];
   DevBuf pstar[3];       // [0],[1]: sort ping-pong partner of set 0/1 ; [2]: Jacobi partner
@@ -134,22 +132,12 @@ struct pbf_ctx {
   uint32_t rowSegShift = 0;
   uint32_t diffuseCap = 0;   // option "diffuse_cap" (diagnostic): records in k_diffuse_rows' tile, 0 = default
   int rowDiffuse = 1;        // option "row_diffuse": the diffusion runs on the row-major copy (k_diffuse_rows)
-  bool bricksValid = false;  // ctx->bricks lists the non-empty bricks of the current table
-  bool rowColValid = false;  // rowCol holds the colours of col4[cur] (set by the sort, consumed by the diffusion)
-  int rcur = 0;               // which rowPstar buffer is live
-  bool rowsValid = false;     // the row arrays describe this step's sorted set (built by the sort)
-  bool nbrRows = false;       // the current neighbour lists hold ROW slots (built by k_build_rows_op)
-  bool pstarInRows = false;   // the current {pStar, lambda} live in rowPstar[rcur] ONLY: pstar[pcur] is stale (materialise_pstar)
-  bool rowsCurrent = false;   // rowPstar[rcur] holds the current {pStar, lambda} (false once a Morton-path stage has moved on)
   uint32_t rowShift = 0;      // the row grid is the cube [0, 1 << rowShift)^3
   uint64_t nbrExtraAt = 0;   // ... + behind them a pool of NBR_EXTRA-slot chunks for the particles that need more (NbrLists)
   uint32_t nbrChunks = 0, nbrChunksOpt = 0;
-  bool nbrValid = false;     // the lists describe pstar[pcur] as it is now
-  bool omegaValid = false;   // pstar[2] holds the vorticity of the last extras pass (PBF_BUF_OMEGA), same order as the arrays
   // pbf_set_surface_tension (opt-in, Akinci 2013): coefficients, the two Jacobi fields of its passes (allocated on first use)
   double cohesion = 0, adhesion = 0;
-  DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE)
-  bool surfaceValid = false;   // surfB holds the record of the last surface-tension pass; invalidated with omegaValid
+  DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE, while st.surfaceValid)
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
   // the compaction's per-tile counts and total, the pinned words of the drained count's read-back {total, sequence number}
   std::vector<pbf_source> sources;
@@ -178,7 +166,6 @@ struct pbf_ctx {
   uint64_t graphReplays = 0, graphCaptures = 0;
   pbf_params lastParams{};   // the params of the last stage call (entry points without a params argument derive their consts from it)
   bool haveParams = false;
-  bool qposValid = false;    // qpos is the quantised copy of pstar[pcur] (written by the sort, delta-p and the slab refresh)
   bool reuseLists = true;    // option "reuse_lists"
   // option "split_build": 0 = lambda builds the neighbour lists while it gathers on fp32 candidates (k_gather_lists<SAVE>);
   // 4 / 5 = the build is a launch of its own (k_build_lists_q on quantised pairs, 2 / 4 pair loads per trip) followed by a
@@ -204,9 +191,8 @@ struct pbf_ctx {
   DevBuf diffSum, diffCnt;   // the overlapped diffusion's own per-cell scratch
   bool fuseDiffuse = false;  // option "fuse_diffuse": pbf_step folds the diffuse walk into the first lambda launch
                              // (bit-identical; measured 2 % SLOWER at 1 M — the colour loads stall the filter loop — so off)
-  bool fuseDiffuseNow = false;
-  // pbf_steps: the NEXT step's predict rides on this step's finalise (k_finalise_predict) / has already been done
-  bool fuseNextPredict = false, prePredicted = false;
+  // pbf_steps' request to the step it starts: the NEXT step's predict rides on this step's finalise (k_finalise_predict)
+  bool fuseNextPredict = false;
   DevBuf bricks, brickCtl;  // non-empty brick list; brickCtl = {nActive, ticket[kTickets], nBigCells}
   DevBuf bigCells;          // cells with more than BIG_CELL members this step (k_sort_big_cells)
   uint32_t gatherSeq = 0;   // which ticket word the next persistent gather launch uses
@@ -217,7 +203,6 @@ struct pbf_ctx {
   uint32_t tileCap = 0, listMax = 0;  // 0 = defaults (env PBF_TILE_CAP / PBF_LIST_MAX override)
   size_t tableCap = 0;   // entries allocated in count/table
   uint32_t tableN = 0;
-  uint32_t countedTableN = 0;
   uint64_t extent[3] = {0, 0, 0};
   double minExtent[3] = {0, 0, 0};
 
@@ -369,8 +354,8 @@ template <typename N> int make_consts(pbf_ctx *ctx, const pbf_params *p, StepCon
 
 // A histogram that was built but never consumed (predict without sort) must not leak into the next one.
 int drop_histogram(pbf_ctx *ctx) {
-  if (ctx->counted && ctx->count.p) HIPCHK(ctx, hipMemsetAsync(ctx->count.p, 0, ctx->count.cap, ctx->stream));
-  ctx->counted = false;
+  if (ctx->st.counted && ctx->count.p) HIPCHK(ctx, hipMemsetAsync(ctx->count.p, 0, ctx->count.cap, ctx->stream));
+  ctx->st.histogram_dropped();
   return PBF_OK;
 }
 
@@ -495,34 +480,27 @@ template <typename N> int stage_predict(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = drop_histogram(ctx)) return rc;
   if (int rc = upload_wells(ctx, p)) return rc;
   StageTimer t(ctx, ST_PREDICT);
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
   hipLaunchKernelGGL((k_predict<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c,
                      ctx->pos4[s].as<const vec4<N>>(), ctx->vel4[s].as<vec4<N>>(), ctx->type[s].as<const uint8_t>(),
                      ctx->wells.as<const N>(), ctx->pstar[s].as<vec4<N>>(), ctx->key[s].as<uint32_t>(),
                      ctx->count.as<uint32_t>());
   LAUNCH_CHECK(ctx);
-  ctx->pcur = s;
-  ctx->sorted = false;
-  ctx->nbrValid = false;
-  ctx->qposValid = false;
-  ctx->omegaValid = false, ctx->surfaceValid = false;
-  ctx->pstarInRows = false, ctx->rowsValid = false, ctx->rowsCurrent = false;
-  ctx->counted = true;
-  ctx->countedTableN = c.tableN;
+  ctx->st.predicted(c.tableN, /*ahead=*/false);
   return PBF_OK;
 }
 
 bool row_mode(const pbf_ctx *ctx);
 
 // list of the non-empty 4 x 4 x 4 bricks for the persistent brick kernels (k_diffuse_bricks, pbf_tiles.hpp): built by the sort
-// stage when one of them is going to run, otherwise by whoever turns out to need it
+// stage when one of them is going to run (its counter word is zero then), otherwise by whoever turns out to need it
 void brick_list(pbf_ctx *ctx, uint32_t tableN, bool counterIsZero = false) {
-  if (ctx->bricksValid) return;
+  if (ctx->st.bricksValid) return;
   if (!counterIsZero) (void)hipMemsetAsync(ctx->brickCtl.p, 0, 4, ctx->stream);
   const uint32_t home = Brick<kBrickZ>::HOME, nBricks = (tableN + home - 1) / home;
   hipLaunchKernelGGL(k_brick_list, grid_for(nBricks), dim3(BLOCK), 0, ctx->stream, ctx->table.as<const uint32_t>(), tableN, home,
                      nBricks, ctx->bricks.as<uint32_t>(), ctx->brickCtl.as<uint32_t>());
-  ctx->bricksValid = true;
+  ctx->st.bricks_listed();
 }
 
 // one to two exclusive scans in three launches (k_scan_sums zeroes `nZero` control words on its way)
@@ -540,24 +518,22 @@ ScanJobs scan_job(const uint32_t *count, uint32_t len, uint32_t *sums, uint32_t 
 
 template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   // the scatter consumes the histogram k_predict built (atomicSub back to zero): never run it twice
-  if (!ctx->counted) return fail(ctx, PBF_ERR_STATE, "pbf_stage_sort needs pbf_stage_predict first");
+  if (!ctx->st.counted) return fail(ctx, PBF_ERR_STATE, "pbf_stage_sort needs pbf_stage_predict first");
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
-  if (c.tableN != ctx->countedTableN) return fail(ctx, PBF_ERR_STATE, "bounds changed between predict and sort");
+  if (c.tableN != ctx->st.countedTableN) return fail(ctx, PBF_ERR_STATE, "bounds changed between predict and sort");
   StageTimer t(ctx, ST_SORT);
   const uint32_t len = c.tableN + 2;
-  const uint32_t nb = (len + SCAN_TILE - 1) / SCAN_TILE;
   uint32_t *count = ctx->count.as<uint32_t>(), *table = ctx->table.as<uint32_t>(),
            *sums = ctx->blockSums.as<uint32_t>();
   ScanJobs jobs = scan_job(count, len, sums, table);
   int njobs = 1;
-  (void)nb;
-  const int s = ctx->cur, d = 1 - s;
+  const int s = ctx->st.cur, d = 1 - s;
   // option "row_major": the box cells' populations in cell-row-major order and their scan (the row table), read off the
   // Morton table; k_rank_move below then writes the iterations' row-major copy on its way
   RowArrays<N> row{};
-  ctx->rowsValid = false, ctx->pstarInRows = false, ctx->rowsCurrent = false, ctx->rowColValid = false;
-  if (row_mode(ctx)) {
+  const bool rows = row_mode(ctx), rowDiffuse = rows && ctx->cellDiffuse && ctx->rowDiffuse > 0;
+  if (rows) {
     // the cube that holds every cell the Morton table knows: P = 2^(bits of tableN / 3, rounded up)
     uint32_t pshift = 1;
     while (pshift < 10 && (uint64_t(1) << (3 * pshift)) < uint64_t(c.tableN)) ++pshift;
@@ -574,7 +550,6 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
     if (int rc = ensure(ctx, ctx->rowXYZ, ctx->cap * 4)) return rc;
     if (int rc = ensure(ctx, ctx->rowType, ctx->cap)) return rc;
     if (int rc = ensure(ctx, ctx->rowSlotOf, ctx->cap * 4)) return rc;
-    const bool rowDiffuse = ctx->cellDiffuse && ctx->rowDiffuse > 0;
     const uint32_t segShift = std::min<uint32_t>(pshift, 6u);  // segments of 64 x cells (the whole row in a smaller cube)
     const size_t nSegTotal = ncells >> segShift;
     if (rowDiffuse) {
@@ -593,14 +568,11 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
     if (rowDiffuse)  // the x-segments that hold a particle (at most one per particle), for k_diffuse_rows
       hipLaunchKernelGGL(k_row_segments, grid_for(nSegTotal), dim3(BLOCK), 0, ctx->stream, pshift, segShift,
                          ctx->linTable.as<const uint32_t>(), ctx->rowSegs.as<uint32_t>(), ctx->linCount.as<uint32_t>() + ncells + 2);
-    ctx->rcur = 0;
     row = RowArrays<N>{ctx->rowPstar[0].as<vec4<N>>(), ctx->rowMass.as<N>(), ctx->rowQpos.as<uint2>(), ctx->rowXYZ.as<uint32_t>(),
                        ctx->rowType.as<uint8_t>(), ctx->rowSlotOf.as<uint32_t>(),
                        rowDiffuse ? ctx->rowCol.as<vec4<N>>() : nullptr, rowDiffuse ? ctx->rowMortonOf.as<uint32_t>() : nullptr,
                        ctx->linTable.as<const uint32_t>(), ctx->linCount.as<uint32_t>() + ncells + 1, pshift};
     ctx->rowShift = pshift, ctx->rowSegShift = segShift;
-    ctx->rowColValid = rowDiffuse;
-    ctx->rowsValid = true, ctx->rowsCurrent = true;
   }
   if (njobs == 1) launch_scans(ctx, jobs, 1, ctx->brickCtl.as<uint32_t>(), kTickets + 2);  // (Morton order only)
   uint32_t *nBig = ctx->brickCtl.as<uint32_t>() + kTickets + 1;
@@ -618,23 +590,16 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   hipLaunchKernelGGL((k_rank_move<N>), grid_for(nLive), dim3(BLOCK), 0, ctx->stream, c, uint32_t(nLive), c.tableN,
                      ctx->permTmp.as<const uint32_t>(), table, arrays<N>(ctx, s, s), arrays<N>(ctx, d, d),
                      ctx->slabActive ? ctx->slotOf.as<uint32_t>() : nullptr, ctx->qpos.as<uint2>(), row);
+  LAUNCH_CHECK(ctx);
   ctx->n = nLive;
   ctx->gatherSeq = 0;  // (fresh tickets)
-  ctx->bricksValid = false;
-  if (!ctx->rowColValid) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
-  LAUNCH_CHECK(ctx);
-  ctx->cur = d;
-  ctx->pcur = d;
-  ctx->sorted = true;
-  ctx->nbrValid = false;
-  ctx->qposValid = true;
-  if (ctx->rowsValid) ctx->pstarInRows = true, ctx->qposValid = false;  // (the sort wrote the row copy only)
-  ctx->counted = false;
+  ctx->st.sorted_now(rows, rowDiffuse);
+  if (!rowDiffuse) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
   return PBF_OK;
 }
 
 // the Jacobi partner of pstar[pcur]: any of the three buffers that is neither live nor needed
-inline int other_pstar(const pbf_ctx *ctx) { return ctx->pcur == 2 ? ctx->cur : 2; }
+inline int other_pstar(const pbf_ctx *ctx) { return ctx->st.pcur == 2 ? ctx->st.cur : 2; }
 
 // Launch one gather stage.  gatherKind picks the kernel (option "gather" / env PBF_GATHER);
 // PBF_FLAG_NO_LDS always forces the plain per-particle global walk.
@@ -653,12 +618,12 @@ template <typename N> RowWalk row_walk(pbf_ctx *ctx) {
 }
 // whoever wants {pStar, lambda} in the Morton-sorted array (stage-level read-backs, the extras, the surface) gets it here
 template <typename N> int materialise_pstar(pbf_ctx *ctx) {
-  if (!ctx->pstarInRows) return PBF_OK;
+  if (!ctx->st.pstarInRows) return PBF_OK;
   hipLaunchKernelGGL((k_rows_to_morton<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
-                     ctx->rowPstar[ctx->rcur].as<const vec4<N>>(), ctx->rowSlotOf.as<const uint32_t>(),
-                     ctx->pstar[ctx->pcur].as<vec4<N>>());
+                     ctx->rowPstar[ctx->st.rcur].as<const vec4<N>>(), ctx->rowSlotOf.as<const uint32_t>(),
+                     ctx->pstar[ctx->st.pcur].as<vec4<N>>());
   LAUNCH_CHECK(ctx);
-  ctx->pstarInRows = false;
+  ctx->st.materialised();
   return PBF_OK;
 }
 
@@ -680,7 +645,7 @@ NbrLists nbr_lists(pbf_ctx *ctx, bool build) {
 
 template <typename N, typename Op>
 int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, GatherMode mode = GATHER_PLAIN) {
-  const uint32_t *key = ctx->key[ctx->cur].as<const uint32_t>();
+  const uint32_t *key = ctx->key[ctx->st.cur].as<const uint32_t>();
   const uint32_t *table = ctx->table.as<const uint32_t>();
   if ((ctx->desc.flags & PBF_FLAG_NO_LDS) || ctx->gatherKind == 0) {
     // `padLds` bytes of unused dynamic LDS cap the workgroups per CU: fewer resident waves keep the
@@ -712,9 +677,9 @@ int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, 
       };
       if (mode == GATHER_SAVE_LISTS) {
         uint2 *qp = ctx->qpos.as<uint2>();
-        if (!ctx->qposValid) {
+        if (!ctx->st.qposValid) {
           hipLaunchKernelGGL((k_quantise<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, Op::src(args), qp);
-          ctx->qposValid = true;
+          ctx->st.quantised();
         }
         StageTimer tb(ctx, ST_BUILD);
         const size_t lds = B::HDR2 + size_t(cap + WAYS) * sizeof(uint2) + size_t(LMAX + WAYS) * TILE_THREADS * 2;
@@ -762,9 +727,9 @@ int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, 
                uint64_t(ctx->n) * sizeof(typename Op::Src) <= 0xFFFFFFFFull) {  // (k_build_lists: 32-bit offsets)  // build the lists, then run the op list-driven
       if constexpr (Op::kTileable && Op::kFilter) {  // (the ops that filter on pStar itself: lambda, delta-p)
         uint2 *qp = ctx->qpos.as<uint2>();
-        if (!ctx->qposValid) {  // (only after a stage that moved pStar without refreshing its quantised copy)
+        if (!ctx->st.qposValid) {  // (only after a stage that moved pStar without refreshing its quantised copy)
           hipLaunchKernelGGL((k_quantise<N>), g, b, 0, ctx->stream, c, Op::src(args), qp);
-          ctx->qposValid = true;
+          ctx->st.quantised();
         }
         if (ctx->splitBuild == 8) {  // the op rides on the build
           // (staging depth 32 and four survivors per drain trip: measured best of 16 / 24 / 32 x 2 / 4 / 6 / 8)
@@ -814,7 +779,7 @@ int join_diffuse(pbf_ctx *ctx) {
 template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool overlap = false) {
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
-  const int s = ctx->cur, d = 1 - s;  // col4[d] is free after the sort
+  const int s = ctx->st.cur, d = 1 - s;  // col4[d] is free after the sort
   typename DiffuseOp<N>::Args args{ctx->col4[s].as<const vec4<N>>(), ctx->col4[d].as<vec4<N>>(),
                                    ctx->type[s].as<const uint8_t>()};
   const bool timed = (ctx->desc.flags & PBF_FLAG_STAGE_TIMING) != 0 && ((ctx->timingMask >> ST_DIFFUSE) & 1u) != 0;
@@ -822,9 +787,9 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
   // one-workgroup-per-CU launch is then longer than the iteration it hides behind) — measured, profiles/r03_matrix.txt
   overlap = overlap && ctx->overlapDiffuse && ctx->cellDiffuse && !(ctx->desc.flags & PBF_FLAG_NO_LDS) && !timed &&
             (ctx->overlapDiffuseForced || ctx->n >= (size_t(1) << 19));
-  ctx->omegaValid = false, ctx->surfaceValid = false;  // (the per-cell sums may be parked in pStar's idle Jacobi partner)
+  bool parked = false;  // the per-cell sums went through pStar's idle Jacobi partner and the list lengths
   StageTimer t(ctx, ST_DIFFUSE);
-  if (ctx->cellDiffuse && ctx->rowColValid && ctx->rowsValid && ctx->rowDiffuse) {
+  if (ctx->cellDiffuse && ctx->st.diffuse_on_rows() && ctx->rowDiffuse) {
     // the row-major copy: one wave per segment of 64 x cells, runs staged through LDS, sums applied in place (k_diffuse_rows).
     // On the solver's own stream: the launch is short, nothing is gained by hiding it
     const uint32_t ncells = 1u << (3u * ctx->rowShift);
@@ -845,7 +810,6 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
                        ctx->rowMortonOf.as<const uint32_t>(), ctx->rowSegs.as<const uint32_t>(),
                        ctx->linCount.as<const uint32_t>() + ncells + 2, ctx->rowSegShift, args.colOut, cap, uint32_t(ctx->n));
     LAUNCH_CHECK(ctx);
-    ctx->rowColValid = false;  // (col4 moves on: the copy is the pre-diffusion state)
   } else if (ctx->cellDiffuse && !(ctx->desc.flags & PBF_FLAG_NO_LDS)) {
     brick_list(ctx, c.tableN);
     // sums per cell, parked in buffers that are idle here (the Jacobi partner of pStar and the list lengths) — or, when
@@ -888,13 +852,13 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
     if (overlap) {
       HIPCHK(ctx, hipEventRecord(ctx->evJoin, st));
       ctx->diffusePending = true;
-    } else {
-      ctx->nbrValid = false;
     }
+    parked = !overlap;
   } else if (int rc = launch_gather<N, DiffuseOp<N>>(ctx, c, args)) {
     return rc;
   }
   std::swap(ctx->col4[s], ctx->col4[d]);
+  ctx->st.diffused(parked);
   return PBF_OK;
 }
 
@@ -908,110 +872,71 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
 #ifndef PBF_ROWS_FW
 #define PBF_ROWS_FW 4
 #endif
-template <typename N> int stage_lambda(pbf_ctx *ctx, const pbf_params *p) {
+// fuseDiffuse (pbf_step, option "fuse_diffuse"): the colour diffusion rides on this launch's walk
+template <typename N, bool FAST> int lambda_impl(pbf_ctx *ctx, const pbf_params *p, bool fuseDiffuse) {
+  using Op = LambdaOp<N, FAST>;
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   StageTimer t(ctx, ST_LAMBDA);
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
   // the survivors of lambda's filter are exactly delta's (same pStar): hand them over through HBM
   const bool lists = (ctx->gatherKind == 1 || ctx->gatherKind == 3) && ctx->reuseLists && !(ctx->desc.flags & PBF_FLAG_NO_LDS);
-  const GatherMode save = lists ? GATHER_SAVE_LISTS : GATHER_PLAIN;
-  ctx->nbrValid = lists;
-  if (lists && ctx->rowsValid && ctx->rowsCurrent && row_mode(ctx) && !ctx->fuseDiffuseNow) {  // the build + lambda on the row-major copy
-    const dim3 g = grid_for(ctx->n), b(BLOCK);
-    const RowWalk rw = row_walk<N>(ctx);
-    if (ctx->fast) {
-      typename LambdaOp<N, true>::Args a{ctx->rowPstar[ctx->rcur].as<vec4<N>>(), nullptr, ctx->rowType.as<const uint8_t>(), ctx->rowMass.as<const N>()};
-      hipLaunchKernelGGL((k_build_rows_op<N, LambdaOp<N, true>, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW>), g, b, 0, ctx->stream, c, a, ctx->rowQpos.as<const uint2>(), rw, nbr_lists(ctx, true));
-    } else {
-      typename LambdaOp<N, false>::Args a{ctx->rowPstar[ctx->rcur].as<vec4<N>>(), nullptr, ctx->rowType.as<const uint8_t>(), ctx->rowMass.as<const N>()};
-      hipLaunchKernelGGL((k_build_rows_op<N, LambdaOp<N, false>, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW>), g, b, 0, ctx->stream, c, a, ctx->rowQpos.as<const uint2>(), rw, nbr_lists(ctx, true));
-    }
+  if (lists && ctx->st.rows_usable() && row_mode(ctx) && !fuseDiffuse) {  // the build + lambda on the row-major copy
+    typename Op::Args a{ctx->rowPstar[ctx->st.rcur].as<vec4<N>>(), nullptr, ctx->rowType.as<const uint8_t>(), ctx->rowMass.as<const N>()};
+    hipLaunchKernelGGL((k_build_rows_op<N, Op, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, a,
+                       ctx->rowQpos.as<const uint2>(), row_walk<N>(ctx), nbr_lists(ctx, true));
     LAUNCH_CHECK(ctx);
-    ctx->pstarInRows = true, ctx->nbrRows = true;
+    ctx->st.lambda_done(lists, /*rows=*/true);
     return PBF_OK;
   }
   if (int rc = materialise_pstar<N>(ctx)) return rc;  // (a Morton-path launch after row-major ones: options changed mid-step)
-  ctx->rowsCurrent = false, ctx->nbrRows = false;
-  if (lists && ctx->fuseDiffuseNow) {  // pbf_step: the colour diffusion rides on this launch's walk
-    ctx->fuseDiffuseNow = false;
-    const int d = 1 - s;
-    typename DiffuseOp<N>::Args xa{ctx->col4[s].as<const vec4<N>>(), ctx->col4[d].as<vec4<N>>(),
-                                   ctx->type[s].as<const uint8_t>()};
-    const uint32_t *key = ctx->key[s].as<const uint32_t>(), *table = ctx->table.as<const uint32_t>();
-    const NbrLists ls = nbr_lists(ctx, true);
-    if (ctx->fast) {
-      typename LambdaOp<N, true>::Args a{ctx->pstar[ctx->pcur].as<vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                         ctx->type[s].as<const uint8_t>()};
-      hipLaunchKernelGGL((k_gather_lists<N, LambdaOp<N, true>, 16, true, DiffuseOp<N>>), grid_for(ctx->n), dim3(BLOCK), 0,
-                         ctx->stream, c, a, key, table, ls, xa);
-    } else {
-      typename LambdaOp<N, false>::Args a{ctx->pstar[ctx->pcur].as<vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                          ctx->type[s].as<const uint8_t>()};
-      hipLaunchKernelGGL((k_gather_lists<N, LambdaOp<N, false>, 16, true, DiffuseOp<N>>), grid_for(ctx->n), dim3(BLOCK), 0,
-                         ctx->stream, c, a, key, table, ls, xa);
-    }
-    LAUNCH_CHECK(ctx);
-    std::swap(ctx->col4[s], ctx->col4[d]);
-    return PBF_OK;
-  }
-  if (ctx->fast) {
-    typename LambdaOp<N, true>::Args args{ctx->pstar[ctx->pcur].as<vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                          ctx->type[s].as<const uint8_t>()};
-    return launch_gather<N, LambdaOp<N, true>>(ctx, c, args, save);
-  }
-  typename LambdaOp<N, false>::Args args{ctx->pstar[ctx->pcur].as<vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                         ctx->type[s].as<const uint8_t>()};
-  return launch_gather<N, LambdaOp<N, false>>(ctx, c, args, save);
+  ctx->st.lambda_done(lists, /*rows=*/false);
+  typename Op::Args a{ctx->pstar[ctx->st.pcur].as<vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(), ctx->type[s].as<const uint8_t>()};
+  if (!lists || !fuseDiffuse) return launch_gather<N, Op>(ctx, c, a, lists ? GATHER_SAVE_LISTS : GATHER_PLAIN);
+  const int d = 1 - s;
+  typename DiffuseOp<N>::Args xa{ctx->col4[s].as<const vec4<N>>(), ctx->col4[d].as<vec4<N>>(),
+                                 ctx->type[s].as<const uint8_t>()};
+  hipLaunchKernelGGL((k_gather_lists<N, Op, 16, true, DiffuseOp<N>>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, a,
+                     ctx->key[s].as<const uint32_t>(), ctx->table.as<const uint32_t>(), nbr_lists(ctx, true), xa);
+  LAUNCH_CHECK(ctx);
+  std::swap(ctx->col4[s], ctx->col4[d]);
+  ctx->st.diffused(/*parked=*/false);
+  return PBF_OK;
+}
+template <typename N> int stage_lambda(pbf_ctx *ctx, const pbf_params *p, bool fuseDiffuse = false) {
+  return ctx->fast ? lambda_impl<N, true>(ctx, p, fuseDiffuse) : lambda_impl<N, false>(ctx, p, fuseDiffuse);
 }
 
-template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
+template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
+  using Op = DeltaOp<N, FAST>;
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   StageTimer t(ctx, ST_DELTA);
-  if (ctx->nbrValid && ctx->nbrRows && ctx->rowsValid && ctx->rowsCurrent) {  // list-driven delta-p on the row-major copy
-    ctx->nbrValid = false, ctx->omegaValid = false, ctx->surfaceValid = false;
+  const int s = ctx->st.cur;
+  if (ctx->st.delta_on_rows()) {  // list-driven delta-p on the row-major copy
     const dim3 g = grid_for(ctx->n), b(BLOCK);
     const RowWalk rw = row_walk<N>(ctx);
-    const int rin = ctx->rcur, rout = 1 - rin;
+    const int rin = ctx->st.rcur, rout = 1 - rin;
     const NbrLists ls = nbr_lists(ctx, false);
-    const uint32_t *key = ctx->key[ctx->cur].as<const uint32_t>(), *table = ctx->table.as<const uint32_t>();
-    if (ctx->fast) {
-      typename DeltaOp<N, true>::Args a{ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()};
-      if (ctx->pipeline > 0) hipLaunchKernelGGL((k_gather_from_lists<N, DeltaOp<N, true>, true, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
-      else hipLaunchKernelGGL((k_gather_from_lists<N, DeltaOp<N, true>, false, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
-    } else {
-      typename DeltaOp<N, false>::Args a{ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()};
-      if (ctx->pipeline > 0) hipLaunchKernelGGL((k_gather_from_lists<N, DeltaOp<N, false>, true, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
-      else hipLaunchKernelGGL((k_gather_from_lists<N, DeltaOp<N, false>, false, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
-    }
+    const uint32_t *key = ctx->key[s].as<const uint32_t>(), *table = ctx->table.as<const uint32_t>();
+    typename Op::Args a{ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()};
+    if (ctx->pipeline > 0) hipLaunchKernelGGL((k_gather_from_lists<N, Op, true, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
+    else hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
     LAUNCH_CHECK(ctx);
-    ctx->rcur = rout;
-    ctx->pstarInRows = true;
-    ctx->qposValid = false;  // (the Morton-order quantised copy is stale now; the row copy is current)
+    ctx->st.pstar_moved(/*rows=*/true, rout);
     return PBF_OK;
   }
   if (int rc = materialise_pstar<N>(ctx)) return rc;
-  ctx->rowsCurrent = false;
-  const int s = ctx->cur, in = ctx->pcur, out = other_pstar(ctx);
-  const GatherMode from = (ctx->nbrValid && !ctx->nbrRows) ? GATHER_FROM_LISTS : GATHER_PLAIN;
-  ctx->nbrValid = false;  // delta moves pStar: the lists are stale afterwards
-  ctx->omegaValid = false, ctx->surfaceValid = false;  // (and may write the buffer the last vorticity pass left its result in)
-  int rc;
+  const int in = ctx->st.pcur, out = other_pstar(ctx);
   // delta-p's epilogue also writes the quantised copy of the new pStar: the next iteration's list build needs it
-  uint2 *qp = ctx->qposValid ? ctx->qpos.as<uint2>() : nullptr;
-  if (ctx->fast) {
-    typename DeltaOp<N, true>::Args args{ctx->pstar[in].as<const vec4<N>>(), ctx->pstar[out].as<vec4<N>>(),
-                                         ctx->type[s].as<const uint8_t>(), qp};
-    rc = launch_gather<N, DeltaOp<N, true>>(ctx, c, args, from);
-  } else {
-    typename DeltaOp<N, false>::Args args{ctx->pstar[in].as<const vec4<N>>(), ctx->pstar[out].as<vec4<N>>(),
-                                          ctx->type[s].as<const uint8_t>(), qp};
-    rc = launch_gather<N, DeltaOp<N, false>>(ctx, c, args, from);
-  }
-  if (rc) return rc;
-  ctx->pcur = out;
-  return PBF_OK;
+  typename Op::Args a{ctx->pstar[in].as<const vec4<N>>(), ctx->pstar[out].as<vec4<N>>(), ctx->type[s].as<const uint8_t>(),
+                      ctx->st.qposValid ? ctx->qpos.as<uint2>() : nullptr};
+  const int rc = launch_gather<N, Op>(ctx, c, a, ctx->st.delta_from_lists() ? GATHER_FROM_LISTS : GATHER_PLAIN);
+  ctx->st.pstar_moved(/*rows=*/false, rc ? in : out);  // (launched or not: nothing derived from the old pStar is trusted any more)
+  return rc;
+}
+template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
+  return ctx->fast ? delta_impl<N, true>(ctx, p) : delta_impl<N, false>(ctx, p);
 }
 
 // Opt-in extras (pbf_params.vorticity / .xsph, pbf_set_surface_tension), absent from the reference: see VorticityOp /
@@ -1030,7 +955,7 @@ int ensure_surface(pbf_ctx *ctx) {
 // Surface tension and adhesion (Akinci et al. 2013), last among the extras: density -> A, normals -> B, velocity update.
 template <typename N, bool FAST> int surface_tension_impl(pbf_ctx *ctx, const StepConsts<N> &c) {
   if (int rc = ensure_surface(ctx)) return rc;
-  const int s = ctx->cur, o = 1 - s;
+  const int s = ctx->st.cur, o = 1 - s;
   const double h = ctx->desc.h;
   SurfArgs<N> a{};
   a.pstar = ctx->pstar[s].as<const vec4<N>>(), a.pos4 = ctx->pos4[s].as<const vec4<N>>();
@@ -1046,12 +971,11 @@ template <typename N, bool FAST> int surface_tension_impl(pbf_ctx *ctx, const St
   a.velIn = ctx->vel4[s].as<const vec4<N>>(), a.velOut = ctx->vel4[o].as<vec4<N>>();
   if (int rc = launch_gather<N, SurfaceTensionOp<N, FAST>>(ctx, c, a)) return rc;
   std::swap(ctx->vel4[s], ctx->vel4[o]);
-  ctx->surfaceValid = true;
   return PBF_OK;
 }
 
 template <typename N, bool FAST> int extras_impl(pbf_ctx *ctx, const pbf_params *p, const StepConsts<N> &c) {
-  const int s = ctx->cur, o = 1 - s;
+  const int s = ctx->st.cur, o = 1 - s;
   const uint8_t *type = ctx->type[s].as<const uint8_t>();
   const vec4<N> *ps = ctx->pstar[s].as<const vec4<N>>();
   if (p->vorticity) {
@@ -1061,14 +985,15 @@ template <typename N, bool FAST> int extras_impl(pbf_ctx *ctx, const pbf_params 
     typename VorticityForceOp<N, FAST>::Args a2{ps, omega, ctx->vel4[s].as<const vec4<N>>(), ctx->vel4[o].as<vec4<N>>(), type};
     if (int rc = launch_gather<N, VorticityForceOp<N, FAST>>(ctx, c, a2)) return rc;
     std::swap(ctx->vel4[s], ctx->vel4[o]);
-    ctx->omegaValid = true;
   }
   if (p->xsph) {
     typename XsphOp<N, FAST>::Args a3{ps, ctx->vel4[s].as<const vec4<N>>(), ctx->vel4[o].as<vec4<N>>(), type};
     if (int rc = launch_gather<N, XsphOp<N, FAST>>(ctx, c, a3)) return rc;
     std::swap(ctx->vel4[s], ctx->vel4[o]);
   }
-  if (surface_on(ctx)) return surface_tension_impl<N, FAST>(ctx, c);
+  if (surface_on(ctx))
+    if (int rc = surface_tension_impl<N, FAST>(ctx, c)) return rc;
+  ctx->st.extras_done(p->vorticity != 0, surface_on(ctx));
   return PBF_OK;
 }
 template <typename N> int extras(pbf_ctx *ctx, const pbf_params *p, const StepConsts<N> &c) {
@@ -1081,7 +1006,7 @@ template <typename N> int extras(pbf_ctx *ctx, const pbf_params *p, const StepCo
 template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
   if (ctx->fuseNextPredict && !extras_on(ctx, p)) {
     // finalise(t) + predict(t + 1) in one pass: everything stage_predict does, around one launch
     ctx->fuseNextPredict = false;
@@ -1090,41 +1015,32 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
     if (int rc = upload_wells(ctx, p)) return rc;
     if (int rc = join_diffuse(ctx)) return rc;  // (the side stream reads keys and types of this step)
     StageTimer t(ctx, ST_FINALISE);
-    if (ctx->pcur != s) {  // pStar is overwritten in place: make the live buffer pstar[cur] first
-      std::swap(ctx->pstar[ctx->pcur], ctx->pstar[s]);
-      ctx->pcur = s;
-    }
+    std::swap(ctx->pstar[ctx->st.pcur], ctx->pstar[s]);  // pStar is overwritten in place: make the live buffer pstar[cur] first
     hipLaunchKernelGGL((k_finalise_predict<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c,
                        ctx->type[s].as<const uint8_t>(), ctx->pstar[s].as<vec4<N>>(), ctx->pos4[s].as<vec4<N>>(),
                        ctx->vel4[s].as<vec4<N>>(), ctx->wells.as<const N>(), ctx->key[s].as<uint32_t>(),
-                       ctx->count.as<uint32_t>(), ctx->rowPstar[ctx->rcur].as<const vec4<N>>(),
-                       ctx->pstarInRows ? ctx->rowSlotOf.as<const uint32_t>() : nullptr);
-    ctx->pstarInRows = false, ctx->rowsValid = false, ctx->rowsCurrent = false;
+                       ctx->count.as<uint32_t>(), ctx->rowPstar[ctx->st.rcur].as<const vec4<N>>(),
+                       ctx->st.pstarInRows ? ctx->rowSlotOf.as<const uint32_t>() : nullptr);
+    ctx->st.predicted(c.tableN, /*ahead=*/true);
     LAUNCH_CHECK(ctx);
-    ctx->sorted = false, ctx->nbrValid = false, ctx->qposValid = false, ctx->omegaValid = false, ctx->surfaceValid = false;
-    ctx->counted = true, ctx->countedTableN = c.tableN;
-    ctx->prePredicted = true;
     return PBF_OK;
   }
   ctx->fuseNextPredict = false;
-  if (ctx->pstarInRows && extras_on(ctx, p))  // the extras read the Morton-sorted pStar
+  if (ctx->st.pstarInRows && extras_on(ctx, p))  // the extras read the Morton-sorted pStar
     if (int rc = materialise_pstar<N>(ctx)) return rc;
   StageTimer t(ctx, ST_FINALISE);
-  if (ctx->pstarInRows)
+  if (ctx->st.pstarInRows)
     hipLaunchKernelGGL((k_finalise<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, ctx->type[s].as<const uint8_t>(),
-                       ctx->rowPstar[ctx->rcur].as<const vec4<N>>(), ctx->pos4[s].as<vec4<N>>(), ctx->vel4[s].as<vec4<N>>(),
+                       ctx->rowPstar[ctx->st.rcur].as<const vec4<N>>(), ctx->pos4[s].as<vec4<N>>(), ctx->vel4[s].as<vec4<N>>(),
                        ctx->rowSlotOf.as<const uint32_t>());
   else
     hipLaunchKernelGGL((k_finalise<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, ctx->type[s].as<const uint8_t>(),
-                       ctx->pstar[ctx->pcur].as<const vec4<N>>(), ctx->pos4[s].as<vec4<N>>(), ctx->vel4[s].as<vec4<N>>(),
+                       ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<vec4<N>>(), ctx->vel4[s].as<vec4<N>>(),
                        static_cast<const uint32_t *>(nullptr));
   LAUNCH_CHECK(ctx);
   // keep pstar[cur] as the live buffer so that a later sort scatters pstar[cur] -> pstar[1-cur]
-  if (ctx->pcur != s) {
-    std::swap(ctx->pstar[ctx->pcur], ctx->pstar[s]);
-    ctx->pcur = s;
-  }
-  ctx->nbrValid = false;
+  std::swap(ctx->pstar[ctx->st.pcur], ctx->pstar[s]);
+  ctx->st.finalised();
   if (extras_on(ctx, p)) return extras<N>(ctx, p, c);
   return PBF_OK;
 }
@@ -1149,10 +1065,8 @@ template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
   if (ctx->downloadPending) (void)pbf_download_aos_end(ctx);
   if (int rc = join_diffuse(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;  // (a predict without its sort: it describes the set before this stage)
-  ctx->sorted = false, ctx->nbrValid = false, ctx->qposValid = false, ctx->omegaValid = false, ctx->surfaceValid = false;
-  ctx->pstarInRows = false, ctx->rowsValid = false, ctx->rowsCurrent = false, ctx->rowColValid = false;
-  ctx->prePredicted = false;
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
+  ctx->st.arrays_replaced(s);
   if (e) {
     const N spacing = N(ctx->desc.h) * N(p->scale) / 2;  // ompsph.hpp:93
     hipLaunchKernelGGL((k_scene_emit<N>), grid_for(e), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n), uint32_t(e),
@@ -1160,7 +1074,6 @@ template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
     LAUNCH_CHECK(ctx);
     ctx->n += e;
   }
-  ctx->pcur = s;
   if (ctx->drains.empty()) return PBF_OK;
   const uint32_t n = uint32_t(ctx->n), nb = (n + DRAIN_TILE - 1) / DRAIN_TILE, nd = uint32_t(ctx->drains.size());
   if (int rc = ensure(ctx, ctx->drainCounts, (ctx->cap / DRAIN_TILE + 2) * 4)) return rc;
@@ -1184,7 +1097,7 @@ template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
     hipLaunchKernelGGL((k_drain_move<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, arrays<N>(ctx, s, s), arrays<N>(ctx, 1 - s, 1 - s),
                        drains, nd, counts);
     LAUNCH_CHECK(ctx);
-    ctx->cur = 1 - s, ctx->pcur = 1 - s;
+    ctx->st.compacted(/*flipped=*/true);
   }
   ctx->n = kept;
   return PBF_OK;
@@ -1194,11 +1107,8 @@ template <typename N> int step_impl(pbf_ctx *ctx, const pbf_params *p) {
   if (scene_on(ctx))  // ompsph.hpp:93-118, before the "depleted" test as there: a source refills an empty state
     if (int rc = stage_scene<N>(ctx, p)) return rc;
   if (ctx->n == 0) return PBF_OK;  // "Particles depleted" (ompsph.hpp:122-126)
-  if (ctx->prePredicted) {
-    ctx->prePredicted = false;  // the previous step of this pbf_steps call has predicted already (k_finalise_predict)
-  } else if (int rc = stage_predict<N>(ctx, p)) {
-    return rc;
-  }
+  if (!ctx->st.take_prediction())  // (else the previous step of this pbf_steps call has predicted already: k_finalise_predict)
+    if (int rc = stage_predict<N>(ctx, p)) return rc;
   if (int rc = stage_sort<N>(ctx, p)) return rc;
   // diffuse (ompsph.hpp:188-207) visits exactly the candidates of the first lambda launch: fuse the two walks
   const bool fuse = ctx->fuseDiffuse && p->iteration > 0 && ctx->gatherKind == 1 && ctx->reuseLists &&
@@ -1206,9 +1116,8 @@ template <typename N> int step_impl(pbf_ctx *ctx, const pbf_params *p) {
   if (!fuse) {
     if (int rc = stage_diffuse<N>(ctx, p, /*overlap=*/p->iteration > 0)) return rc;
   }
-  ctx->fuseDiffuseNow = fuse;
   for (uint64_t it = 0; it < p->iteration; ++it) {
-    if (int rc = stage_lambda<N>(ctx, p)) return rc;
+    if (int rc = stage_lambda<N>(ctx, p, fuse && it == 0)) return rc;
     if (int rc = stage_delta<N>(ctx, p)) return rc;
   }
   if (int rc = stage_finalise<N>(ctx, p)) return rc;
@@ -1219,7 +1128,7 @@ int check(pbf_ctx *ctx, const pbf_params *p, bool needSorted) {
   if (!ctx) return PBF_ERR_INVALID;
   if (!p) return fail(ctx, PBF_ERR_INVALID, "params == NULL");
   if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
-  if (needSorted && !ctx->sorted) return fail(ctx, PBF_ERR_STATE, "stage needs pbf_stage_sort first");
+  if (needSorted && !ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "stage needs pbf_stage_sort first");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->lastParams = *p;
   ctx->haveParams = true;
@@ -1236,8 +1145,8 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
-  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->surfaceValid = false;
-  ctx->ghostsPending = false, ctx->slabActive = false, ctx->prePredicted = false;
+  ctx->st.arrays_replaced(0);
+  ctx->ghostsPending = false, ctx->slabActive = false;
   ctx->n = n, ctx->uploaded = n;
   ctx->hasObstacles = false;
   if (n == 0) return PBF_OK;
@@ -1263,7 +1172,7 @@ int download_impl(pbf_ctx *ctx, uint64_t *id, uint8_t *type, N *mass, N *pos, N 
   if (int rc = drop_ghosts(ctx)) return rc;
   const size_t n = ctx->n;
   if (n == 0) return PBF_OK;
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
   std::vector<vec4<N>> tmp(n);
   if (mass || pos) {
     HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->pos4[s].p, n * sizeof(vec4<N>), hipMemcpyDeviceToHost, ctx->stream));
@@ -1509,7 +1418,8 @@ int pbf_upload_aos(pbf_ctx *ctx, size_t n, const void *particles, const pbf_aos_
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
-  ctx->cur = 0, ctx->pcur = 0, ctx->sorted = false, ctx->n = n, ctx->uploaded = n, ctx->surfaceValid = false;
+  ctx->st.arrays_replaced(0);
+  ctx->n = n, ctx->uploaded = n;
   ctx->ghostsPending = false, ctx->slabActive = false;
   ctx->hasObstacles = false;
   if (n == 0) return PBF_OK;
@@ -1567,10 +1477,10 @@ int pbf_download_aos_begin(pbf_ctx *ctx, void *particles, const pbf_aos_layout *
   AosLayout L{l->stride, l->off_id, l->off_type, l->off_mass, l->off_pos, l->off_vel, l->off_colour};
   if (ctx->fp64)
     hipLaunchKernelGGL((k_pack_aos<double>), grid_for(n), dim3(BLOCK), 0, ctx->stream, uint32_t(n),
-                       ctx->staging.as<uint8_t>(), L, arrays<double>(ctx, ctx->cur, ctx->pcur));
+                       ctx->staging.as<uint8_t>(), L, arrays<double>(ctx, ctx->st.cur, ctx->st.pcur));
   else
     hipLaunchKernelGGL((k_pack_aos<float>), grid_for(n), dim3(BLOCK), 0, ctx->stream, uint32_t(n),
-                       ctx->staging.as<uint8_t>(), L, arrays<float>(ctx, ctx->cur, ctx->pcur));
+                       ctx->staging.as<uint8_t>(), L, arrays<float>(ctx, ctx->st.cur, ctx->st.pcur));
   LAUNCH_CHECK(ctx);
   if (!ctx->copyStream) {
     HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->copyStream, hipStreamNonBlocking));
@@ -1600,22 +1510,22 @@ int pbf_step(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = drop_ghosts(ctx)) return rc;
   return DISPATCH(ctx, step_impl, ctx, p);
 }
+
+}  // extern "C"
+
 namespace {
 
-DevBuf *role_buffers(pbf_ctx *ctx, DevBuf *out[15]) {
+void role_buffers(pbf_ctx *ctx, DevBuf *out[15]) {
   DevBuf *all[15] = {&ctx->pos4[0], &ctx->pos4[1], &ctx->vel4[0], &ctx->vel4[1], &ctx->col4[0], &ctx->col4[1],
                      &ctx->id[0],   &ctx->id[1],   &ctx->type[0], &ctx->type[1], &ctx->key[0],  &ctx->key[1],
                      &ctx->pstar[0], &ctx->pstar[1], &ctx->pstar[2]};
   for (int k = 0; k < 15; ++k) out[k] = all[k];
-  return nullptr;
 }
 StepState snapshot(pbf_ctx *ctx) {
   StepState s;
   std::memset(&s, 0, sizeof(s));  // (padding bytes take part in the comparison)
-  s.cur = ctx->cur, s.pcur = ctx->pcur;
-  s.flags = uint32_t(ctx->sorted) | uint32_t(ctx->counted) << 1 | uint32_t(ctx->nbrValid) << 2 | uint32_t(ctx->qposValid) << 3 |
-            uint32_t(ctx->hasObstacles) << 4;
-  s.tableN = ctx->tableN, s.countedTableN = ctx->countedTableN, s.gatherSeq = ctx->gatherSeq;
+  s.st = ctx->st, s.hasObstacles = ctx->hasObstacles;
+  s.tableN = ctx->tableN, s.gatherSeq = ctx->gatherSeq;
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) s.extent[k] = ctx->extent[k], s.minExtent[k] = ctx->minExtent[k];
@@ -1623,19 +1533,21 @@ StepState snapshot(pbf_ctx *ctx) {
   return s;
 }
 void restore(pbf_ctx *ctx, const StepState &s) {
-  ctx->cur = s.cur, ctx->pcur = s.pcur;
-  ctx->sorted = s.flags & 1u, ctx->counted = (s.flags >> 1) & 1u, ctx->nbrValid = (s.flags >> 2) & 1u;
-  ctx->qposValid = (s.flags >> 3) & 1u, ctx->hasObstacles = (s.flags >> 4) & 1u;
-  ctx->tableN = s.tableN, ctx->countedTableN = s.countedTableN, ctx->gatherSeq = s.gatherSeq;
+  ctx->st = s.st, ctx->hasObstacles = s.hasObstacles;  // (all of the derived state, not only what the key compares)
+  ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
   for (int k = 0; k < 15; ++k) b[k]->p = s.bufs[k], b[k]->cap = s.caps[k];
 }
-GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p) {
+GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   GraphKey k;
   std::memset(&k, 0, sizeof(k));
-  k.before = snapshot(ctx);
+  k.before = before;
+  // of the derived state only what a step's launch sequence depends on takes part (a key that also compared, say,
+  // omegaValid would capture the same step twice)
+  std::memset(static_cast<void *>(&k.before.st), 0, sizeof(k.before.st));
+  before.st.step_key(k.before.st);
   double v[11] = {p->dt, p->scale, p->constant_force[0], p->constant_force[1], p->constant_force[2], p->min_bound[0],
                   p->min_bound[1], p->min_bound[2], p->max_bound[0], p->max_bound[1], p->max_bound[2]};
   std::memcpy(k.params, v, sizeof(v));
@@ -1658,12 +1570,14 @@ int step_maybe_graphed(pbf_ctx *ctx, const pbf_params *p) {
   const bool timing = (ctx->desc.flags & PBF_FLAG_STAGE_TIMING) != 0 && ctx->timingMask != 0;
   if (ctx->graphMode <= 0 || timing || p->n_wells > 0 || ctx->n == 0 || ctx->slabConfigured || scene_on(ctx))
     return DISPATCH(ctx, step_impl, ctx, p);
-  const GraphKey key = graph_key(ctx, p);
+  const StepState before = snapshot(ctx);
+  const GraphKey key = graph_key(ctx, p, before);
   auto it = ctx->graphs.find(key);
   if (it != ctx->graphs.end()) {
     HIPCHK(ctx, hipGraphLaunch(it->second.exec, ctx->stream));
+    // (omegaValid / surfaceValid included: the extras' switches and coefficients are part of the key, so the replayed step
+    // ran those passes iff the captured one did)
     restore(ctx, it->second.after);
-    ctx->surfaceValid = surface_on(ctx);  // (the coefficients are part of the key: the replayed step ran the pass iff they are on)
     ctx->graphMisses = 0;
     ctx->graphReplays++;
     return PBF_OK;
@@ -1691,7 +1605,7 @@ int step_maybe_graphed(pbf_ctx *ctx, const pbf_params *p) {
     if (graph) (void)hipGraphDestroy(graph);
     (void)hipGetLastError();
     ctx->graphMode = 0;
-    restore(ctx, key.before);
+    restore(ctx, before);
     ctx->diffusePending = false;
     return DISPATCH(ctx, step_impl, ctx, p);
   }
@@ -1701,7 +1615,7 @@ int step_maybe_graphed(pbf_ctx *ctx, const pbf_params *p) {
   if (ei != hipSuccess) {
     (void)hipGetLastError();
     ctx->graphMode = 0;
-    restore(ctx, key.before);
+    restore(ctx, before);
     ctx->diffusePending = false;
     return DISPATCH(ctx, step_impl, ctx, p);
   }
@@ -1713,6 +1627,8 @@ int step_maybe_graphed(pbf_ctx *ctx, const pbf_params *p) {
 }
 
 }  // namespace
+
+extern "C" {
 
 int pbf_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   if (int rc = check(ctx, p, false)) return rc;
@@ -1726,7 +1642,8 @@ int pbf_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   for (uint32_t i = 0; i < count; ++i) {
     ctx->fuseNextPredict = fusable && i + 1 < count;
     if (int rc = step_maybe_graphed(ctx, p)) {
-      ctx->fuseNextPredict = ctx->prePredicted = false;
+      ctx->fuseNextPredict = false;
+      (void)ctx->st.take_prediction();
       return rc;
     }
   }
@@ -1836,7 +1753,7 @@ int query_impl(pbf_ctx *ctx, const pbf_params *p, size_t np, const double *point
   if (int rc = ensure(ctx, ctx->queryIds, std::max<size_t>(np * cap, 1) * 8)) return rc;
   if (int rc = join_diffuse(ctx)) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->queryPoints.p, pts.data(), pts.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
   hipLaunchKernelGGL((k_query_cells<N>), dim3(unsigned(np)), dim3(64), 0, ctx->stream, c, ctx->queryPoints.as<const N>(),
                      ctx->table.as<const uint32_t>(), ctx->type[s].as<const uint8_t>(), ctx->id[s].as<const uint64_t>(),
                      ctx->queryCounts.as<uint32_t>(), ctx->queryIds.as<uint64_t>(), uint32_t(cap));
@@ -1893,7 +1810,7 @@ int pbf_query_cells(pbf_ctx *ctx, const pbf_params *p, size_t n_points, const do
   if (int rc = check(ctx, p, false)) return rc;
   if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
     return fail(ctx, PBF_ERR_STATE, "pbf_query_cells is not supported in slab mode");
-  if (!ctx->sorted) return fail(ctx, PBF_ERR_STATE, "pbf_query_cells needs a step first (no valid cell table)");
+  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_query_cells needs a step first (no valid cell table)");
   if (n_points == 0) return PBF_OK;
   if (!points || !counts || (cap_per_point && !ids)) return fail(ctx, PBF_ERR_INVALID, "pbf_query_cells: NULL argument");
   if (n_points >= (size_t(1) << 31) || cap_per_point >= (size_t(1) << 31))
@@ -1912,22 +1829,22 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
   size_t avail = 0;
   const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4);
   switch (which) {
-    case PBF_BUF_KEYS: src = ctx->key[ctx->cur].p, avail = ctx->n * 4; break;
+    case PBF_BUF_KEYS: src = ctx->key[ctx->st.cur].p, avail = ctx->n * 4; break;
     case PBF_BUF_TABLE:
-      if (!ctx->sorted) return fail(ctx, PBF_ERR_STATE, "table not built yet");
+      if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "table not built yet");
       src = ctx->table.p, avail = size_t(ctx->tableN) * 4;
       break;
     case PBF_BUF_PSTAR:
       if (int rc = ctx->fp64 ? materialise_pstar<double>(ctx) : materialise_pstar<float>(ctx)) return rc;
-      src = ctx->pstar[ctx->pcur].p, avail = ctx->n * v;
+      src = ctx->pstar[ctx->st.pcur].p, avail = ctx->n * v;
       break;
     case PBF_BUF_NBR_COUNT: src = ctx->nbrCount.p, avail = (ctx->ghostsPending ? ctx->nOwned : ctx->n) * 4; break;
     case PBF_BUF_OMEGA:
-      if (!ctx->omegaValid) return fail(ctx, PBF_ERR_STATE, "no vorticity pass since the arrays last changed (pbf_params.vorticity)");
+      if (!ctx->st.omegaValid) return fail(ctx, PBF_ERR_STATE, "no vorticity pass since the arrays last changed (pbf_params.vorticity)");
       src = ctx->pstar[2].p, avail = ctx->n * v;
       break;
     case PBF_BUF_SURFACE:
-      if (!ctx->surfaceValid) return fail(ctx, PBF_ERR_STATE, "no surface-tension pass since the arrays last changed (pbf_set_surface_tension)");
+      if (!ctx->st.surfaceValid) return fail(ctx, PBF_ERR_STATE, "no surface-tension pass since the arrays last changed (pbf_set_surface_tension)");
       src = ctx->surfB.p, avail = std::min(ctx->n * v, ctx->surfB.cap);
       break;
     default: return fail(ctx, PBF_ERR_INVALID, "unknown buffer");
@@ -2024,12 +1941,12 @@ int run_select(pbf_ctx *ctx, const pbf_slab_cut *cut, void *sendL, void *sendR, 
   const uint32_t xo = ctx->slabConfigured ? ctx->xoff : 0u;  // the keys' x frame
   SlabCut s{cut->xlo - std::min(cut->xlo, xo), cut->xhi == 0xFFFFFFFFu ? cut->xhi : cut->xhi - std::min(cut->xhi, xo),
             cut->has_left ? 1u : 0u, cut->has_right ? 1u : 0u};
-  const int a = ctx->cur, b = 1 - a;
+  const int a = ctx->st.cur, b = 1 - a;
   uint32_t *counts = ctx->selCounts.as<uint32_t>(), *tot = ctx->selTotals.as<uint32_t>();
   hipLaunchKernelGGL((k_sel_count<MODE>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, s, ctx->key[a].as<const uint32_t>(),
                      ctx->type[a].as<const uint8_t>(), nb, counts);
   hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, counts, tot);
-  hipLaunchKernelGGL((k_sel_emit<N, MODE>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, s, arrays<N>(ctx, a, ctx->pcur),
+  hipLaunchKernelGGL((k_sel_emit<N, MODE>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, s, arrays<N>(ctx, a, ctx->st.pcur),
                      arrays<N>(ctx, b, b), nb, counts, sendL, sendR, cap, ctx->ghostSrcL.as<uint32_t>(),
                      ctx->ghostSrcR.as<uint32_t>());
   LAUNCH_CHECK(ctx);
@@ -2044,13 +1961,9 @@ template <typename N> int slab_migrate(pbf_ctx *ctx, const pbf_slab_cut *cut, vo
   uint32_t t[3];
   if (int rc = run_select<N, SEL_MIGRATE>(ctx, cut, sL, sR, cap, t)) return rc;
   if (t[1] > cap || t[2] > cap) return fail(ctx, PBF_ERR_INVALID, "migrant buffer too small");
-  if (ctx->n) {
-    ctx->cur = 1 - ctx->cur;  // the keeps were compacted into the other array set
-    ctx->pcur = ctx->cur;
-  }
+  ctx->st.compacted(/*flipped=*/ctx->n != 0);  // the keeps were compacted into the other array set
   ctx->n = t[0];
   ctx->nOwned = t[0];
-  ctx->sorted = false;
   out[0] = t[1], out[1] = t[2];
   return PBF_OK;
 }
@@ -2060,7 +1973,7 @@ template <typename N> int slab_add_migrants(pbf_ctx *ctx, const void *rL, uint32
   if (nL + nR)
     hipLaunchKernelGGL((k_append_migrants<N>), grid_for(nL + nR), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
                        static_cast<const MigrantRec<N> *>(rL), nL, static_cast<const MigrantRec<N> *>(rR), nR,
-                       ctx->shiftL, ctx->shiftR, arrays<N>(ctx, ctx->cur, ctx->pcur));
+                       ctx->shiftL, ctx->shiftR, arrays<N>(ctx, ctx->st.cur, ctx->st.pcur));
   LAUNCH_CHECK(ctx);
   ctx->n += nL + nR;
   ctx->nOwned = uint32_t(ctx->n);
@@ -2081,7 +1994,7 @@ template <typename N> int slab_add_ghosts(pbf_ctx *ctx, const void *rL, uint32_t
   if (nL + nR)
     hipLaunchKernelGGL((k_append_ghosts<N>), grid_for(nL + nR), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
                        static_cast<const GhostRec<N> *>(rL), nL, static_cast<const GhostRec<N> *>(rR), nR,
-                       ctx->shiftL, ctx->shiftR, arrays<N>(ctx, ctx->cur, ctx->pcur));
+                       ctx->shiftL, ctx->shiftR, arrays<N>(ctx, ctx->st.cur, ctx->st.pcur));
   ctx->gotL = nL, ctx->gotR = nR;
   ctx->ghostAt = uint32_t(ctx->n);
   ctx->n += nL + nR;
@@ -2089,10 +2002,9 @@ template <typename N> int slab_add_ghosts(pbf_ctx *ctx, const void *rL, uint32_t
   // histogram of the re-assembled set (owned + copies) for the sort
   if (ctx->n)
     hipLaunchKernelGGL(k_count_keys, grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n), ctx->tableN,
-                       ctx->key[ctx->cur].as<const uint32_t>(), ctx->count.as<uint32_t>());
+                       ctx->key[ctx->st.cur].as<const uint32_t>(), ctx->count.as<uint32_t>());
   LAUNCH_CHECK(ctx);
-  ctx->counted = true;
-  ctx->countedTableN = ctx->tableN;
+  ctx->st.histogram_current(ctx->tableN);
   ctx->slabActive = true;
   return PBF_OK;
 }
@@ -2100,10 +2012,10 @@ template <typename N> int slab_add_ghosts(pbf_ctx *ctx, const void *rL, uint32_t
 template <typename N> int slab_pack(pbf_ctx *ctx, void *sL, void *sR, const void *field = nullptr) {
   const uint32_t m = ctx->sentL + ctx->sentR;
   // {pStar, lambda}: from wherever it currently lives — the row-major copy while the iterations run on it
-  const bool rows = !field && ctx->pstarInRows && ctx->rowsCurrent;
-  if (!field && ctx->pstarInRows && !rows) return fail(ctx, PBF_ERR_STATE, "slab pack: no current pStar");
+  const bool rows = !field && ctx->st.pstar_in_live_rows();
+  if (!field && ctx->st.pstarInRows && !rows) return fail(ctx, PBF_ERR_STATE, "slab pack: no current pStar");
   const vec4<N> *src = field ? static_cast<const vec4<N> *>(field)
-                             : rows ? ctx->rowPstar[ctx->rcur].as<const vec4<N>>() : ctx->pstar[ctx->pcur].as<const vec4<N>>();
+                             : rows ? ctx->rowPstar[ctx->st.rcur].as<const vec4<N>>() : ctx->pstar[ctx->st.pcur].as<const vec4<N>>();
   if (m)
     hipLaunchKernelGGL((k_pack_field<N>), grid_for(m), dim3(BLOCK), 0, ctx->stream, ctx->sentL, ctx->sentR,
                        ctx->ghostSrcL.as<const uint32_t>(), ctx->ghostSrcR.as<const uint32_t>(),
@@ -2118,12 +2030,12 @@ template <typename N> int slab_unpack(pbf_ctx *ctx, const void *rL, const void *
   StepConsts<N> c;
   if (!ctx->haveParams) return fail(ctx, PBF_ERR_STATE, "pbf_slab_unpack before any stage");
   if (int rc = make_consts<N>(ctx, &ctx->lastParams, c)) return rc;
-  const bool rows = !field && ctx->pstarInRows && ctx->rowsCurrent;
+  const bool rows = !field && ctx->st.pstar_in_live_rows();
   if (m)
     hipLaunchKernelGGL((k_unpack_field<N>), grid_for(m), dim3(BLOCK), 0, ctx->stream, c, ctx->ghostAt, ctx->gotL, ctx->gotR,
                        static_cast<const vec4<N> *>(rL), static_cast<const vec4<N> *>(rR),
                        ctx->slotOf.as<const uint32_t>(),
-                       field ? static_cast<vec4<N> *>(field) : rows ? ctx->rowPstar[ctx->rcur].as<vec4<N>>() : ctx->pstar[ctx->pcur].as<vec4<N>>(),
+                       field ? static_cast<vec4<N> *>(field) : rows ? ctx->rowPstar[ctx->st.rcur].as<vec4<N>>() : ctx->pstar[ctx->st.pcur].as<vec4<N>>(),
                        field ? nullptr : rows ? ctx->rowQpos.as<uint2>() : ctx->qpos.as<uint2>(),
                        rows ? ctx->rowSlotOf.as<const uint32_t>() : nullptr);
   LAUNCH_CHECK(ctx);
@@ -2134,18 +2046,12 @@ template <typename N> int slab_finish(pbf_ctx *ctx, bool knownOwned = false) {
   // drop the copies: the MIGRATE select with no neighbours keeps exactly the non-ghost particles
   pbf_slab_cut none{0, 0xFFFFFFFFu, 0, 0};
   uint32_t t[3];
-  const bool wasSorted = ctx->sorted;
   // (pbf_slab_step knows the count — every non-copy is owned — and skips the synchronising read-back)
   if (int rc = run_select<N, SEL_MIGRATE>(ctx, &none, nullptr, nullptr, 0, t, !knownOwned)) return rc;
   if (knownOwned) t[0] = ctx->n ? ctx->nOwned : 0;
-  if (ctx->n) {
-    ctx->cur = 1 - ctx->cur;
-    ctx->pcur = ctx->cur;
-  }
+  ctx->st.compacted(/*flipped=*/ctx->n != 0);
   ctx->n = t[0];
   ctx->nOwned = t[0];
-  ctx->sorted = false;
-  (void)wasSorted;
   ctx->hasObstacles = ctx->realObstacles;
   ctx->slabActive = false;
   ctx->sentL = ctx->sentR = ctx->gotL = ctx->gotR = 0;
@@ -2195,7 +2101,7 @@ int pbf_slab_configure(pbf_ctx *ctx, const pbf_slab_cut *cut, uint32_t left_xlo,
   ctx->shiftL = int32_t(origin(left_xlo, left_xlo > 0)) - int32_t(ctx->xoff);
   ctx->shiftR = int32_t(origin(right_xlo, true)) - int32_t(ctx->xoff);
   ctx->slabConfigured = true;
-  ctx->sorted = false;
+  ctx->st.compacted(/*flipped=*/false);  // (the keys' frame changed)
   return PBF_OK;
 }
 size_t pbf_slab_record_bytes(const pbf_ctx *ctx, int kind) {
@@ -2229,12 +2135,12 @@ int pbf_slab_add_ghosts(pbf_ctx *ctx, const void *recv_left, uint32_t n_left, co
 }
 int pbf_slab_pack(pbf_ctx *ctx, void *send_left, void *send_right) {
   if (int rc = slab_check(ctx)) return rc;
-  if (!ctx->sorted) return fail(ctx, PBF_ERR_STATE, "pbf_slab_pack needs pbf_stage_sort first");
+  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_slab_pack needs pbf_stage_sort first");
   return DISPATCH(ctx, slab_pack, ctx, send_left, send_right);
 }
 int pbf_slab_unpack(pbf_ctx *ctx, const void *recv_left, const void *recv_right) {
   if (int rc = slab_check(ctx)) return rc;
-  if (!ctx->sorted) return fail(ctx, PBF_ERR_STATE, "pbf_slab_unpack needs pbf_stage_sort first");
+  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_slab_unpack needs pbf_stage_sort first");
   return DISPATCH(ctx, slab_unpack, ctx, recv_left, recv_right);
 }
 int pbf_slab_finish(pbf_ctx *ctx) {
@@ -2253,8 +2159,8 @@ int pbf_slab_column_histogram(pbf_ctx *ctx, uint32_t out[1024]) {
   if (ctx->n) {
     const uint32_t blocks = uint32_t(std::min<size_t>((ctx->n + BLOCK - 1) / BLOCK, size_t(ctx->numCUs) * 4));
     hipLaunchKernelGGL(k_column_histogram, dim3(blocks), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
-                       ctx->slabConfigured ? ctx->xoff : 0u, ctx->key[ctx->cur].as<const uint32_t>(),
-                       ctx->type[ctx->cur].as<const uint8_t>(), ctx->colHist.as<uint32_t>());
+                       ctx->slabConfigured ? ctx->xoff : 0u, ctx->key[ctx->st.cur].as<const uint32_t>(),
+                       ctx->type[ctx->st.cur].as<const uint8_t>(), ctx->colHist.as<uint32_t>());
     LAUNCH_CHECK(ctx);
   }
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->colHist.p, 1024 * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2296,8 +2202,8 @@ int exchange(pbf_ctx *ctx, size_t nSL, size_t nSR, size_t nRL, size_t nRR, size_
 template <typename N, bool FAST> int slab_extras_impl(pbf_ctx *ctx, const pbf_params *p) {
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
-  const uint8_t *type = ctx->type[ctx->cur].as<const uint8_t>();
-  const vec4<N> *ps = ctx->pstar[ctx->cur].as<const vec4<N>>();
+  const uint8_t *type = ctx->type[ctx->st.cur].as<const uint8_t>();
+  const vec4<N> *ps = ctx->pstar[ctx->st.cur].as<const vec4<N>>();
   const size_t fb = sizeof(vec4<N>);
   auto refresh = [&](void *field) -> int {
     if (int rc = slab_pack<N>(ctx, ctx->wireSend[0].p, ctx->wireSend[1].p, field)) return rc;
@@ -2305,7 +2211,7 @@ template <typename N, bool FAST> int slab_extras_impl(pbf_ctx *ctx, const pbf_pa
     return slab_unpack<N>(ctx, ctx->wireRecv[0].p, ctx->wireRecv[1].p, field);
   };
   auto vel = [&](int k) { return ctx->vel4[k].as<vec4<N>>(); };
-  int s = ctx->cur, o = 1 - s;
+  int s = ctx->st.cur, o = 1 - s;
   if (int rc = refresh(vel(s))) return rc;
   if (p->vorticity) {
     vec4<N> *omega = ctx->pstar[2].as<vec4<N>>();
@@ -2343,11 +2249,8 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
     ~ModeGuard() { c->slabStepMode = false; }
   } guard{ctx};
   ctx->slabStepMode = true;
-  if (ctx->prePredicted) {
-    ctx->prePredicted = false;  // the previous step of this pbf_slab_steps call has predicted already (k_finalise_predict)
-  } else if (int rc = stage_predict<N>(ctx, p)) {
-    return rc;
-  }
+  if (!ctx->st.take_prediction())  // (else the previous step of this pbf_slab_steps call has predicted already)
+    if (int rc = stage_predict<N>(ctx, p)) return rc;
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   const uint32_t nPrev = uint32_t(ctx->n), oldCopies = ctx->ghostsPending ? ctx->gotL + ctx->gotR : 0u;
@@ -2357,7 +2260,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
   uint8_t *mL = ctx->wireSend[0].as<uint8_t>(), *mR = ctx->wireSend[1].as<uint8_t>();
   uint8_t *gL = ctx->wireGhost[0].as<uint8_t>(), *gR = ctx->wireGhost[1].as<uint8_t>();
   uint8_t *rL = ctx->wireRecv[0].as<uint8_t>(), *rR = ctx->wireRecv[1].as<uint8_t>();
-  const int a = ctx->cur;
+  const int a = ctx->st.cur;
   const uint32_t nb = std::max(1u, (nPrev + SEL_TILE - 1) / SEL_TILE);
   if (int rc = ensure(ctx, ctx->selCounts, size_t(4) * nb * 4)) return rc;
   if (int rc = ensure(ctx, ctx->selTotals, 16)) return rc;
@@ -2371,7 +2274,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
   hipLaunchKernelGGL(k_slab_scan, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, counts, tot, reinterpret_cast<uint32_t *>(mL),
                      reinterpret_cast<uint32_t *>(mR), reinterpret_cast<uint32_t *>(gL), reinterpret_cast<uint32_t *>(gR),
                      reinterpret_cast<uint32_t *>(rL), reinterpret_cast<uint32_t *>(rR));
-  hipLaunchKernelGGL((k_slab_emit<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nPrev, sc, arrays<N>(ctx, a, ctx->pcur), nb, counts,
+  hipLaunchKernelGGL((k_slab_emit<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, nPrev, sc, arrays<N>(ctx, a, ctx->st.pcur), nb, counts,
                      reinterpret_cast<MigrantRec<N> *>(mL + WIRE_HDR), reinterpret_cast<MigrantRec<N> *>(mR + WIRE_HDR),
                      reinterpret_cast<GhostRec<N> *>(gL + WIRE_HDR), reinterpret_cast<GhostRec<N> *>(gR + WIRE_HDR), ctx->wireCap,
                      ctx->ghostSrcL.as<uint32_t>(), ctx->ghostSrcR.as<uint32_t>());
@@ -2416,9 +2319,9 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
     hipLaunchKernelGGL((k_append_migrants_h<N>), grid_for(arrived), dim3(BLOCK), 0, ctx->stream, nPrev,
                        reinterpret_cast<const MigrantRec<N> *>(rL + WIRE_HDR), got[0],
                        reinterpret_cast<const MigrantRec<N> *>(rR + WIRE_HDR), got[1], ctx->shiftL, ctx->shiftR,
-                       arrays<N>(ctx, a, ctx->pcur), c.tableN, ctx->count.as<uint32_t>());
+                       arrays<N>(ctx, a, ctx->st.pcur), c.tableN, ctx->count.as<uint32_t>());
     hipLaunchKernelGGL((k_slab_arrival_ghosts<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, nPrev, arrived, sc,
-                       arrays<N>(ctx, a, ctx->pcur), tot, reinterpret_cast<GhostRec<N> *>(gL + WIRE_HDR),
+                       arrays<N>(ctx, a, ctx->st.pcur), tot, reinterpret_cast<GhostRec<N> *>(gL + WIRE_HDR),
                        reinterpret_cast<GhostRec<N> *>(gR + WIRE_HDR), reinterpret_cast<uint32_t *>(gL),
                        reinterpret_cast<uint32_t *>(gR), ctx->wireCap, ctx->ghostSrcL.as<uint32_t>(), ctx->ghostSrcR.as<uint32_t>());
     LAUNCH_CHECK(ctx);
@@ -2433,7 +2336,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
     hipLaunchKernelGGL((k_append_ghosts_h<N>), grid_for(copies), dim3(BLOCK), 0, ctx->stream, ctx->ghostAt,
                        reinterpret_cast<const GhostRec<N> *>(rL + WIRE_HDR), got[0],
                        reinterpret_cast<const GhostRec<N> *>(rR + WIRE_HDR), got[1], ctx->shiftL, ctx->shiftR,
-                       arrays<N>(ctx, a, ctx->pcur), c.tableN, ctx->count.as<uint32_t>());
+                       arrays<N>(ctx, a, ctx->st.pcur), c.tableN, ctx->count.as<uint32_t>());
     LAUNCH_CHECK(ctx);
     ctx->hasObstacles = true;  // "special" particles exist: the kernels must look at type[]
   }
@@ -2442,7 +2345,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
   ctx->sortLive = ctx->n - oldCopies - leavers;                   // what the sort keeps
   ctx->nOwned = uint32_t(ctx->sortLive - copies);
   ctx->slabActive = true;
-  ctx->counted = true, ctx->countedTableN = c.tableN;
+  ctx->st.histogram_current(c.tableN);
   if (int rc = stage_sort<N>(ctx, p)) return rc;
   if (int rc = stage_diffuse<N>(ctx, p, /*overlap=*/p->iteration > 0)) return rc;  // beside the iterations, like pbf_step
   // ---- K x { lambda, delta-p }, each followed by the owners refreshing their copies' {pStar, lambda} ------
@@ -2600,7 +2503,8 @@ int pbf_slab_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   for (uint32_t i = 0; i < count; ++i) {
     ctx->fuseNextPredict = fusable && i + 1 < count;
     if (int rc = DISPATCH(ctx, slab_step_impl, ctx, p)) {
-      ctx->fuseNextPredict = ctx->prePredicted = false;
+      ctx->fuseNextPredict = false;
+      (void)ctx->st.take_prediction();
       return rc;
     }
   }
@@ -2658,7 +2562,7 @@ template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const 
     m.sample[0] = m.planes + (hasRight ? 1u : 0u);
     // the owners' diffused colours -> their copies on the neighbours (one more field round; the copies' pStar is current)
     const size_t fb = sizeof(vec4<N>);
-    vec4<N> *col = ctx->col4[ctx->cur].as<vec4<N>>();
+    vec4<N> *col = ctx->col4[ctx->st.cur].as<vec4<N>>();
     if (int rc = slab_pack<N>(ctx, ctx->wireSend[0].p, ctx->wireSend[1].p, col)) return rc;
     if (int rc = exchange(ctx, ctx->sentL * fb, ctx->sentR * fb, ctx->gotL * fb, ctx->gotR * fb)) return rc;
     if (int rc = slab_unpack<N>(ctx, ctx->wireRecv[0].p, ctx->wireRecv[1].p, col)) return rc;
@@ -2668,7 +2572,7 @@ template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const 
   const uint64_t latticeN = uint64_t(m.sample[0]) * planeN;
   if (latticeN >= (uint64_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "surface lattice too large (resolution x extent)");
   m.tableN = c.tableN, m.hasObstacles = c.hasObstacles;
-  const int s = ctx->cur;
+  const int s = ctx->st.cur;
   if (int rc = ensure(ctx, ctx->latticePN, (latticeN + 1) * sizeof(vec4<N>))) return rc;
   if (int rc = ensure(ctx, ctx->latticeC, (latticeN + 1) * sizeof(vec4<N>))) return rc;
   *nTriangles = 0;
@@ -2683,7 +2587,7 @@ template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const 
                        ctx->mcNear.as<uint32_t>());
     const uint64_t nodeBlocks = uint64_t((m.planes + 3) / 4) * ((m.sample[1] + 3) / 4) * ((m.sample[2] + 3) / 4);
     hipLaunchKernelGGL((k_mc_field<N>), grid_for(nodeBlocks * 64), dim3(BLOCK), 0, ctx->stream, m, ctx->table.as<const uint32_t>(),
-                       ctx->pos4[s].as<const vec4<N>>(), ctx->pstar[ctx->pcur].as<const vec4<N>>(), ctx->col4[s].as<const vec4<N>>(),
+                       ctx->pos4[s].as<const vec4<N>>(), ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->col4[s].as<const vec4<N>>(),
                        ctx->type[s].as<const uint8_t>(), ctx->mcNear.as<const uint32_t>(), ctx->latticePN.as<vec4<N>>(),
                        ctx->latticeC.as<vec4<N>>());
     LAUNCH_CHECK(ctx);

@@ -148,6 +148,36 @@ def test_rigid_rotation_vorticity_sign_and_confinement(pkg, fp64):
     assert np.abs(got[steep] - dv[steep]).max() <= (1e-8 if fp64 else 5e-3) * np.abs(dv).max()
 
 
+def test_omega_is_refused_after_a_new_upload(pkg):
+    """The vorticity of the last extras pass describes the particle set it ran on: an upload replaces the set, and
+    reading omega then is PBF_ERR_STATE (-4) until a step with p.vorticity has run again — not the old set's field."""
+    sc = scene("cloud")
+    p = pkg.default_params(2, 1000.0)
+    p.vorticity = 1
+    s = pkg.Solver(h=0.1).upload(**sc).step(p)
+    assert s.omega().shape == (len(sc["id"]), 3)
+    s.upload(**sc)
+    with pytest.raises(pkg.PbfError, match=r"\(-4\)"):
+        s.omega()
+    assert np.isfinite(s.step(p).omega()).all()
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_upload_of_a_larger_set_after_a_step_equals_a_fresh_solver(pkg, fp64):
+    """upload n1, step, upload n2 = 8 n1 (every particle buffer grows), step: nothing derived from the first set — row
+    arrays, lists, quantised copies, sized for n1 — may take part.  Bit-equal to a solver that only ever saw the second."""
+    small, _ = pkg.scene_dambreak(1024, fp64)
+    big, side = pkg.scene_dambreak(8 * len(small["id"]), fp64)
+    assert len(big["id"]) >= 8 * len(small["id"])
+    p = pkg.default_params(4, side)
+    s = pkg.Solver(h=0.1, fp64=fp64).upload(**small).step(p)
+    got = s.upload(**big).step(p).download()
+    want = pkg.Solver(h=0.1, fp64=fp64).upload(**big).step(p).download()
+    assert len(got["id"]) == len(big["id"])
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+
+
 @pytest.mark.parametrize("fp64", [False, True])
 def test_xsph_conserves_momentum_and_smooths(pkg, fp64):
     """XSPH (eq. 17) is a symmetric-weight average of velocity differences: with equal masses it leaves sum m v

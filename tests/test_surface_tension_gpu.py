@@ -227,6 +227,19 @@ def test_graph_replay_with_toggled_coefficients(pkg, fp64):
     assert enabled and replays > 0 and captured > base_captured, (captured, replays, base_captured)
 
 
+def test_surface_state_is_refused_after_a_new_upload(pkg):
+    """The record of the last surface-tension pass describes the particle set it ran on: after an upload reading it is
+    PBF_ERR_STATE (-4) until a step has run the pass again."""
+    sc = scene("cubes1024")
+    p = pkg.default_params(2, 1000.0)
+    s = solver(pkg, sc, False).set_surface_tension(GAMMA, BETA).step(p)
+    assert s.surface_state().shape == (len(sc["id"]), 4)
+    s.upload(**sc)
+    with pytest.raises(pkg.PbfError, match=r"\(-4\)"):
+        s.surface_state()
+    assert np.isfinite(s.step(p).surface_state()).all()
+
+
 @pytest.mark.parametrize("fp64", [True, False])
 def test_deterministic(pkg, fp64):
     sc = scene("obstacles")
