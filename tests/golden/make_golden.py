@@ -192,6 +192,35 @@ def ref_mc():
     print("ref_mc_digest.npz: 4 arrays")
 
 
+def mc_winding_sign(row):
+    """The sign of ((v1 - v0) x (v2 - v0)) . n for the triangle `row` (three edge numbers) of case 1 under an outward
+    radial normal field.  Case 1: corner 0 alone is below the isolevel (outside the fluid, ompsph.hpp:428), the fluid's
+    centre is the opposite corner (1, 1, 1), the crossings are the midpoints of the edges the row names (edge e joins
+    the corners ompsph.hpp:443-454 lerps between) and n = x - centre at each."""
+    corner = np.array([(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)], float)
+    ends = [(0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7)]
+    row = [int(e) for e in row]
+    assert len(row) == 3 and all(0 in ends[e] for e in row), row
+    v = np.array([(corner[ends[e][0]] + corner[ends[e][1]]) / 2 for e in row])
+    n = (v - corner[6]).sum(axis=0)
+    sign = int(np.sign(np.cross(v[1] - v[0], v[2] - v[0]) @ n))
+    assert sign != 0
+    return sign
+
+
+def ref_mc_winding():
+    """One recorded value: the sign mc_winding_sign gives the reference's TriTable row of case 1."""
+    so = os.path.join(O.ORACLE_DIR, "_ref", "libref_mc.so")
+    assert os.path.exists(so), "oracle/_ref/libref_mc.so missing (needs /root/reference)"
+    R = C.CDLL(so)
+    R.ref_mc_tri.restype = C.c_uint32
+    row = [R.ref_mc_tri(1, j) for j in range(4)]
+    assert row[3] == 255, row
+    sign = mc_winding_sign(row[:3])
+    np.savez_compressed(os.path.join(HERE, "ref_mc_winding.npz"), sign=np.array(sign, np.int8))
+    print("ref_mc_winding.npz: sign", sign)
+
+
 def by_id(d):
     o = np.argsort(d["id"], kind="stable")
     return {k: v[o] for k, v in d.items()}
@@ -242,5 +271,6 @@ if __name__ == "__main__":
     O.build()
     ref_grid()
     ref_mc()
+    ref_mc_winding()
     oracle_selfcheck()
     ref_live_values()
