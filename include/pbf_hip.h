@@ -253,8 +253,27 @@ int pbf_download_mesh(pbf_ctx *ctx, void *vs, void *ns, void *cs);
  * freshly allocated vectors: 54 MB at 1 M particles); the pointers stay valid until the next pbf_surface / pbf_destroy.
  * The C++ shim builds Result::mesh's vectors from them (range construction: no zero fill, the three copies in parallel). */
 int pbf_map_mesh(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs);
-/* the lattice of the last pbf_surface: sample[3] nodes per axis, 4 + 4 values of N per node {v, normal} {colour} */
+/* the lattice of the last pbf_surface / pbf_surface_indexed: sample[3] nodes per axis, 4 + 4 values of N per node
+ * {v, normal} {colour} */
 int pbf_read_lattice(pbf_ctx *ctx, uint64_t sample[3], void *pn, void *c);
+/* The same surface as an INDEXED mesh (no reference counterpart): one vertex per crossed lattice edge, triangles as index
+ * triples.  Same preconditions, same field and same triangles in the same order as pbf_surface; de-indexed, it is that
+ * soup, except that every vertex is interpolated from the edge's lower node towards its +axis node — the soup interpolates
+ * cube edges 2, 3, 6 and 7 from the other end, a few units in the last place away.  Node (x, y, z), index
+ * (x * sample[1] + y) * sample[2] + z, owns the edges to its +x, +y and +z neighbours; an edge is crossed iff exactly one end
+ * value is < isolevel; vertices are numbered by ascending owner index, x < y < z within a node.  Two triangles that share an
+ * edge share two indices: the mesh is watertight by construction.  40 V + 12 T bytes in fp32 instead of 120 T.
+ * PBF_ERR_INVALID at 2^29 vertices or more.
+ * vs / ns = 3 values of N per vertex, cs = 4, tris = 3 uint32 per triangle; any pointer of pbf_download_mesh_indexed may be
+ * NULL.  pbf_map_mesh_indexed: page-locked staging owned by the ctx, valid until the next surface call / pbf_destroy.
+ * The two kinds exclude each other: after pbf_surface_indexed there is no soup (pbf_download_mesh / pbf_map_mesh return
+ * PBF_ERR_STATE), after pbf_surface no indexed mesh (the _indexed readers return PBF_ERR_STATE).
+ * Slab mode is not supported: an edge on a cut plane is owned by a node of another rank, so the vertex numbering would
+ * need a scan across ranks — PBF_ERR_STATE on a ctx configured with pbf_slab_configure. */
+int pbf_surface_indexed(pbf_ctx *ctx, const pbf_params *params, const pbf_mc_params *mc, uint64_t *n_vertices,
+                        uint64_t *n_triangles);
+int pbf_download_mesh_indexed(pbf_ctx *ctx, void *vs, void *ns, void *cs, uint32_t *tris);
+int pbf_map_mesh_indexed(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs, const uint32_t **tris);
 
 /* ---- multi-GPU: slab decomposition along x (no reference counterpart: it is single-device) ------
  * One process per GPU.  Every rank uses the GLOBAL grid (same pbf_params bounds), owns the cell columns

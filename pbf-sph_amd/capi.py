@@ -151,6 +151,10 @@ _SIGS = {
     "pbf_download_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_map_mesh": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pbf_read_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbf_surface_indexed": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pbf_download_mesh_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbf_map_mesh_indexed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p)]),
     "pbf_reserve": (C.c_int, [C.c_void_p, C.c_size_t]),
     "pbf_slab_configure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "pbf_slab_record_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
@@ -420,6 +424,23 @@ class Solver:
         pn, cc = np.empty((nn, 4), self.dtype), np.empty((nn, 4), self.dtype)
         self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), _vp(pn), _vp(cc)), "pbf_read_lattice")
         return dict(vs=vs, ns=ns, cs=cs, sample=smp, pn=pn, c=cc)
+
+    def surface_indexed(self, p, mc=None):
+        """The same surface as an indexed mesh: one vertex per crossed lattice edge -> dict(vs (V,3), ns (V,3), cs (V,4),
+        tris (T,3) uint32, sample, pn, c).  vs[tris] is surface()'s soup (include/pbf_hip.h)."""
+        mc = mc or McParams()
+        nv, nt = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.pbf_surface_indexed(self.ctx, C.byref(p), C.byref(mc), C.byref(nv), C.byref(nt)), "pbf_surface_indexed")
+        v, t = nv.value, nt.value
+        vs, ns, cs = np.empty((v, 3), self.dtype), np.empty((v, 3), self.dtype), np.empty((v, 4), self.dtype)
+        tris = np.empty((t, 3), np.uint32)
+        self._chk(self.L.pbf_download_mesh_indexed(self.ctx, _vp(vs), _vp(ns), _vp(cs), _vp(tris)), "pbf_download_mesh_indexed")
+        smp = np.zeros(3, np.uint64)
+        self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), None, None), "pbf_read_lattice")
+        nn = int(smp.prod())
+        pn, cc = np.empty((nn, 4), self.dtype), np.empty((nn, 4), self.dtype)
+        self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), _vp(pn), _vp(cc)), "pbf_read_lattice")
+        return dict(vs=vs, ns=ns, cs=cs, tris=tris, sample=smp, pn=pn, c=cc)
 
     def extent(self):
         e = np.zeros(3, np.uint64)

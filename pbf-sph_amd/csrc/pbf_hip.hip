@@ -123,6 +123,11 @@ struct pbf_ctx {
   bool meshStaged = false;
   uint64_t mcSample[3] = {0, 0, 0};
   uint64_t mcTriangles = 0;
+  // pbf_surface_indexed: per node the count of crossed owned edges, then (first vertex << 3) | mask; its scan; the index triples
+  DevBuf mcEdgeWord, mcEdgeOffsets, mcEdgeSums, meshT;
+  enum MeshKind { MESH_NONE, MESH_SOUP, MESH_INDEXED };
+  MeshKind meshKind = MESH_NONE;  // what the last surface call left in meshV / meshN / meshC (3 per triangle, or 1 per crossed edge)
+  uint64_t mcVertices = 0;
   DevBuf qpos;               // 8-byte quantised pStar for the list build (k_build_lists_q)
   DevBuf nbrList, nbrCount;  // neighbour lists handed from the lambda launch to the delta launch: NBR_ROWS slots per particle
   // option "row_major": the iterations' working set also laid out cell-row-major (csrc/pbf_kernels.hpp RowArrays)
@@ -1344,7 +1349,7 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->id[0],   &ctx->id[1],   &ctx->type[0], &ctx->type[1], &ctx->key[0],   &ctx->key[1],
                    &ctx->pstar[0], &ctx->pstar[1], &ctx->pstar[2], &ctx->count, &ctx->table,   &ctx->blockSums,
                    &ctx->permTmp, &ctx->wells,   &ctx->staging, &ctx->bricks, &ctx->brickCtl, &ctx->bigCells,
-                   &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->meshV, &ctx->meshN,
+                   &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->mcEdgeWord, &ctx->mcEdgeOffsets, &ctx->mcEdgeSums, &ctx->meshT, &ctx->meshV, &ctx->meshN,
                    &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB,
                    &ctx->sceneSources, &ctx->sceneDrains, &ctx->drainCounts, &ctx->queryPoints, &ctx->queryCounts,
                    &ctx->queryIds};
@@ -2520,7 +2525,11 @@ uint64_t pbf_slab_host_syncs(const pbf_ctx *ctx) { return ctx ? ctx->slabHostSyn
 // ================================================================================================
 namespace {
 
-template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uint64_t *nTriangles) {
+// `nVertices` non-NULL: the indexed mesh (pbf_surface_indexed) — same field, count and scan, then one vertex per crossed
+// lattice edge and index triples instead of k_mc_emit's three private vertices per triangle
+template <typename N>
+int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uint64_t *nTriangles, uint64_t *nVertices) {
+  const bool indexed = nVertices != nullptr;
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   // Slab mode (after pbf_slab_step; the copies of the neighbours' boundary columns are still in the arrays): every rank
@@ -2571,6 +2580,8 @@ template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const 
   const uint64_t planeN = uint64_t(m.sample[1]) * m.sample[2];
   const uint64_t latticeN = uint64_t(m.sample[0]) * planeN;
   if (latticeN >= (uint64_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "surface lattice too large (resolution x extent)");
+  // (the 32-bit scan of up to three vertices per node must not wrap before the 2^29 test below sees its total)
+  if (indexed && 3 * latticeN >= (uint64_t(1) << 32)) return fail(ctx, PBF_ERR_INVALID, "surface lattice too large for an indexed mesh");
   m.tableN = c.tableN, m.hasObstacles = c.hasObstacles;
   const int s = ctx->st.cur;
   if (int rc = ensure(ctx, ctx->latticePN, (latticeN + 1) * sizeof(vec4<N>))) return rc;
@@ -2578,6 +2589,9 @@ template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const 
   *nTriangles = 0;
   ctx->mcTriangles = 0;
   ctx->meshStaged = false;
+  ctx->meshKind = indexed ? pbf_ctx::MESH_INDEXED : pbf_ctx::MESH_SOUP;
+  ctx->mcVertices = 0;
+  if (indexed) *nVertices = 0;
   if (m.planes) {
     // which of a cell's 27 slots hold particles (most lattice nodes sit in empty space and skip their gather)
     if (int rc = ensure(ctx, ctx->mcNear, (size_t(c.tableN) + 64) * 4)) return rc;
@@ -2617,9 +2631,42 @@ template <typename N> int surface_impl(pbf_ctx *ctx, const pbf_params *p, const 
                      ctx->latticePN.as<const vec4<N>>(), counts);
   launch_scans(ctx, scan_job(counts, len, sums, offsets), 1);
   LAUNCH_CHECK(ctx);
-  uint32_t total = 0;
+  uint32_t total = 0, totalV = 0;
+  const uint32_t nodes = uint32_t(latticeN);
+  if (indexed) {  // crossed edges per owner node and their scan, ahead of the one read-back both totals share
+    const uint32_t elen = nodes + 1, enb = (elen + SCAN_TILE - 1) / SCAN_TILE;
+    if (int rc = ensure(ctx, ctx->mcEdgeWord, (size_t(elen) + SCAN_TILE) * 4)) return rc;
+    if (int rc = ensure(ctx, ctx->mcEdgeOffsets, (size_t(elen) + SCAN_TILE) * 4)) return rc;
+    if (int rc = ensure(ctx, ctx->mcEdgeSums, (size_t(enb) + 1) * 4)) return rc;
+    uint32_t *ew = ctx->mcEdgeWord.as<uint32_t>(), *eo = ctx->mcEdgeOffsets.as<uint32_t>();
+    HIPCHK(ctx, hipMemsetAsync(ew + nodes, 0, 4, ctx->stream));  // closing sentinel: eo[nodes] = total
+    hipLaunchKernelGGL((k_mc_edge_mark<N>), grid_for(nodes), dim3(BLOCK), 0, ctx->stream, m, nodes,
+                       ctx->latticePN.as<const vec4<N>>(), ew);
+    launch_scans(ctx, scan_job(ew, elen, ctx->mcEdgeSums.as<uint32_t>(), eo), 1);
+    LAUNCH_CHECK(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(&totalV, eo + nodes, 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
   HIPCHK(ctx, hipMemcpyAsync(&total, offsets + marchVolume, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the mesh buffers are sized from the count
+  if (indexed) {
+    if (totalV >= (1u << 29)) return fail(ctx, PBF_ERR_INVALID, "indexed mesh: 2^29 vertices or more");
+    ctx->mcTriangles = total, ctx->mcVertices = totalV;
+    *nTriangles = total, *nVertices = totalV;
+    if (total == 0) return PBF_OK;  // (no triangle <=> no crossed edge: every lattice edge belongs to a cube)
+    if (int rc = ensure(ctx, ctx->meshV, size_t(totalV) * 3 * sizeof(N))) return rc;
+    if (int rc = ensure(ctx, ctx->meshN, size_t(totalV) * 3 * sizeof(N))) return rc;
+    if (int rc = ensure(ctx, ctx->meshC, size_t(totalV) * 4 * sizeof(N))) return rc;
+    if (int rc = ensure(ctx, ctx->meshT, size_t(total) * 3 * 4)) return rc;
+    hipLaunchKernelGGL((k_mc_emit_vertices<N>), grid_for(nodes), dim3(BLOCK), 0, ctx->stream, m, nodes,
+                       ctx->latticePN.as<const vec4<N>>(), ctx->latticeC.as<const vec4<N>>(),
+                       ctx->mcEdgeOffsets.as<const uint32_t>(), ctx->mcEdgeWord.as<uint32_t>(), ctx->meshV.as<N>(),
+                       ctx->meshN.as<N>(), ctx->meshC.as<N>());
+    hipLaunchKernelGGL((k_mc_emit_indices<N>), grid_for(marchVolume), dim3(BLOCK), 0, ctx->stream, m, marchVolume,
+                       ctx->latticePN.as<const vec4<N>>(), offsets, ctx->mcEdgeWord.as<const uint32_t>(),
+                       ctx->meshT.as<uint32_t>());
+    LAUNCH_CHECK(ctx);
+    return PBF_OK;
+  }
   ctx->mcTriangles = total;
   *nTriangles = total;
   if (total == 0) return PBF_OK;
@@ -2642,11 +2689,69 @@ int pbf_surface(pbf_ctx *ctx, const pbf_params *params, const pbf_mc_params *mc,
 
   if (!mc || !n_triangles) return fail(ctx, PBF_ERR_INVALID, "NULL argument");
   if (!(mc->resolution > 0)) return fail(ctx, PBF_ERR_INVALID, "resolution must be > 0");
-  return DISPATCH(ctx, surface_impl, ctx, params, mc, n_triangles);
+  return DISPATCH(ctx, surface_impl, ctx, params, mc, n_triangles, static_cast<uint64_t *>(nullptr));
+}
+
+int pbf_surface_indexed(pbf_ctx *ctx, const pbf_params *params, const pbf_mc_params *mc, uint64_t *n_vertices,
+                        uint64_t *n_triangles) {
+  // an edge on a cut plane has its owner on another rank: the vertex numbering would need a scan across ranks
+  if (ctx && ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, "pbf_surface_indexed is not supported in slab mode");
+  if (int rc = check(ctx, params, true)) return rc;
+
+  if (!mc || !n_vertices || !n_triangles) return fail(ctx, PBF_ERR_INVALID, "NULL argument");
+  if (!(mc->resolution > 0)) return fail(ctx, PBF_ERR_INVALID, "resolution must be > 0");
+  return DISPATCH(ctx, surface_impl, ctx, params, mc, n_triangles, n_vertices);
+}
+
+int pbf_download_mesh_indexed(pbf_ctx *ctx, void *vs, void *ns, void *cs, uint32_t *tris) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (ctx->meshKind == pbf_ctx::MESH_SOUP)
+    return fail(ctx, PBF_ERR_STATE, "the last surface is a triangle soup (pbf_surface): pbf_download_mesh reads it");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t nv = ctx->mcVertices, nt = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
+  if (nt == 0) return PBF_OK;
+  if (vs) HIPCHK(ctx, hipMemcpyAsync(vs, ctx->meshV.p, nv * 3 * e, hipMemcpyDeviceToHost, ctx->stream));
+  if (ns) HIPCHK(ctx, hipMemcpyAsync(ns, ctx->meshN.p, nv * 3 * e, hipMemcpyDeviceToHost, ctx->stream));
+  if (cs) HIPCHK(ctx, hipMemcpyAsync(cs, ctx->meshC.p, nv * 4 * e, hipMemcpyDeviceToHost, ctx->stream));
+  if (tris) HIPCHK(ctx, hipMemcpyAsync(tris, ctx->meshT.p, nt * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
+}
+
+int pbf_map_mesh_indexed(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs, const uint32_t **tris) {
+  if (!ctx || !vs || !ns || !cs || !tris) return PBF_ERR_INVALID;
+  *vs = *ns = *cs = nullptr, *tris = nullptr;
+  if (ctx->meshKind == pbf_ctx::MESH_SOUP)
+    return fail(ctx, PBF_ERR_STATE, "the last surface is a triangle soup (pbf_surface): pbf_map_mesh reads it");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t nv = ctx->mcVertices, nt = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
+  if (nt == 0) return PBF_OK;
+  const size_t bv = nv * 3 * e, bc = nv * 4 * e, bt = nt * 3 * 4, total = 2 * bv + bc + bt;
+  if (ctx->meshHostCap < total) {
+    if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
+    ctx->meshHost = nullptr, ctx->meshHostCap = 0;
+    const size_t want = total + total / 4 + 4096;
+    HIPCHK(ctx, hipHostMalloc(&ctx->meshHost, want, hipHostMallocDefault));
+    ctx->meshHostCap = want;
+    ctx->meshStaged = false;
+  }
+  char *h = static_cast<char *>(ctx->meshHost);
+  if (!ctx->meshStaged) {
+    HIPCHK(ctx, hipMemcpyAsync(h, ctx->meshV.p, bv, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h + bv, ctx->meshN.p, bv, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h + 2 * bv, ctx->meshC.p, bc, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h + 2 * bv + bc, ctx->meshT.p, bt, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->meshStaged = true;
+  }
+  *vs = h, *ns = h + bv, *cs = h + 2 * bv, *tris = reinterpret_cast<const uint32_t *>(h + 2 * bv + bc);
+  return PBF_OK;
 }
 
 int pbf_download_mesh(pbf_ctx *ctx, void *vs, void *ns, void *cs) {
   if (!ctx) return PBF_ERR_INVALID;
+  if (ctx->meshKind == pbf_ctx::MESH_INDEXED)
+    return fail(ctx, PBF_ERR_STATE, "the last surface is indexed (pbf_surface_indexed): pbf_download_mesh_indexed reads it");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
   if (n == 0) return PBF_OK;
@@ -2659,6 +2764,8 @@ int pbf_download_mesh(pbf_ctx *ctx, void *vs, void *ns, void *cs) {
 
 int pbf_map_mesh(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs) {
   if (!ctx || !vs || !ns || !cs) return PBF_ERR_INVALID;
+  if (ctx->meshKind == pbf_ctx::MESH_INDEXED)
+    return fail(ctx, PBF_ERR_STATE, "the last surface is indexed (pbf_surface_indexed): pbf_map_mesh_indexed reads it");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
   *vs = *ns = *cs = nullptr;

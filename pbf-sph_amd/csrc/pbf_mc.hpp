@@ -233,4 +233,91 @@ __global__ __launch_bounds__(BLOCK) void k_mc_emit(McConsts<N> m, uint32_t march
   }
 }
 
+// ---- indexed mesh (pbf_surface_indexed): one vertex per crossed lattice edge, triangles as index triples ----------------
+// A node owns the lattice edges to its +x, +y and +z neighbours; an edge is crossed iff exactly one of its end values is
+// < isolevel (mc_case's predicate), and its vertex is interpolated from the owner towards the +axis node with k_mc_emit's
+// expressions.  Vertices are numbered by ascending owner index, x < y < z inside a node: the scan of k_mc_edge_mark's counts.
+// Cube edge e -> (corner that owns it, axis): edges 2, 3, 6 and 7 run against their axis, so their owner is lerpAll's `t`.
+template <typename N>
+__device__ inline uint32_t mc_owned_crossings(const McConsts<N> &m, const vec4<N> *__restrict__ latticePN, uint32_t idx,
+                                              uint32_t &x, uint32_t &y, uint32_t &z) {
+  const uint32_t sy = m.sample[1], sz = m.sample[2], plane = sy * sz;
+  x = idx / plane, y = (idx / sz) % sy, z = idx % sz;
+  const bool below = latticePN[idx].x < m.isolevel;
+  uint32_t mask = 0;
+  if (x + 1u < m.sample[0] && (latticePN[idx + plane].x < m.isolevel) != below) mask |= 1u;
+  if (y + 1u < sy && (latticePN[idx + sz].x < m.isolevel) != below) mask |= 2u;
+  if (z + 1u < sz && (latticePN[idx + 1u].x < m.isolevel) != below) mask |= 4u;
+  return mask;
+}
+
+// one lane per node, z fastest (the own value and the +z value are neighbouring lanes' loads; +y and +x are the same rows
+// one row / one plane on): the number of crossed owned edges
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_mc_edge_mark(McConsts<N> m, uint32_t latticeN,
+                                                        const vec4<N> *__restrict__ latticePN,
+                                                        uint32_t *__restrict__ edgeWord) {
+  const uint32_t idx = blockIdx.x * BLOCK + threadIdx.x;
+  if (idx >= latticeN) return;
+  uint32_t x, y, z;
+  edgeWord[idx] = uint32_t(__builtin_popcount(mc_owned_crossings<N>(m, latticePN, idx, x, y, z)));
+}
+
+// one lane per node; a node that owns crossed edges replaces its count by (first vertex index << 3) | mask — an edge's vertex
+// is then (word >> 3) + popcount(word & ((1 << axis) - 1)) — and writes its one to three vertices
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_mc_emit_vertices(McConsts<N> m, uint32_t latticeN,
+                                                            const vec4<N> *__restrict__ latticePN,
+                                                            const vec4<N> *__restrict__ latticeC,
+                                                            const uint32_t *__restrict__ edgeOffsets,
+                                                            uint32_t *__restrict__ edgeWord, N *__restrict__ outV,
+                                                            N *__restrict__ outN, N *__restrict__ outC) {
+  const uint32_t idx = blockIdx.x * BLOCK + threadIdx.x;
+  if (idx >= latticeN) return;
+  if (edgeWord[idx] == 0u) return;
+  uint32_t c[3];
+  const uint32_t mask = mc_owned_crossings<N>(m, latticePN, idx, c[0], c[1], c[2]);
+  uint32_t w = edgeOffsets[idx];
+  edgeWord[idx] = (w << 3) | mask;
+  const uint32_t stride[3] = {m.sample[1] * m.sample[2], m.sample[2], 1u};
+  const vec4<N> pf = latticePN[idx], cf = latticeC[idx];
+  for (int ax = 0; ax < 3; ++ax) {
+    if (!(mask >> ax & 1u)) continue;
+    const vec4<N> pt = latticePN[idx + stride[ax]], ct = latticeC[idx + stride[ax]];
+    const N wgt = (m.isolevel - pf.x) / (pt.x - pf.x);                 // utils::scale, owner -> +axis node
+    auto mix = [&](N a, N b) { return a * (N(1) - wgt) + b * wgt; };   // glm::mix
+    auto coord = [&](uint32_t cc, int k) { return (m.minExtent[k] + (N(cc) * m.step)) * m.scale; };
+    outV[3 * w + 0] = mix(coord(c[0] + m.nodeX0, 0), coord(c[0] + m.nodeX0 + (ax == 0 ? 1u : 0u), 0));
+    outV[3 * w + 1] = mix(coord(c[1], 1), coord(c[1] + (ax == 1 ? 1u : 0u), 1));
+    outV[3 * w + 2] = mix(coord(c[2], 2), coord(c[2] + (ax == 2 ? 1u : 0u), 2));
+    outN[3 * w + 0] = mix(pf.y, pt.y), outN[3 * w + 1] = mix(pf.z, pt.z), outN[3 * w + 2] = mix(pf.w, pt.w);
+    outC[4 * w + 0] = mix(cf.x, ct.x), outC[4 * w + 1] = mix(cf.y, ct.y), outC[4 * w + 2] = mix(cf.z, ct.z),
+                 outC[4 * w + 3] = mix(cf.w, ct.w);
+    ++w;
+  }
+}
+
+// one lane per cube with triangles: every case-table entry (a cube edge) -> its owner node's word -> the vertex index
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_mc_emit_indices(McConsts<N> m, uint32_t marchVolume,
+                                                           const vec4<N> *__restrict__ latticePN,
+                                                           const uint32_t *__restrict__ offsets,
+                                                           const uint32_t *__restrict__ edgeWord,
+                                                           uint32_t *__restrict__ outT) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= marchVolume) return;
+  if (offsets[i + 1] == offsets[i]) return;
+  uint32_t px, py, pz, node[8];
+  N values[8];
+  mc_cube_origin(i, m.sample, px, py, pz);
+  const uint32_t ci = mc_case<N>(m, latticePN, px, py, pz, values, node);
+  const int OWNER[12] = {0, 1, 3, 0, 4, 5, 7, 4, 0, 1, 2, 3}, AXIS[12] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 2, 2, 2};
+  uint32_t w = offsets[i] * 3u;
+  for (int k = 0; kMcTriTable[ci][k] != 255; ++k, ++w) {
+    const int e = kMcTriTable[ci][k];
+    const uint32_t word = edgeWord[node[OWNER[e]]];
+    outT[w] = (word >> 3) + uint32_t(__builtin_popcount(word & ((1u << AXIS[e]) - 1u)));
+  }
+}
+
 }  // namespace pbf

@@ -35,6 +35,7 @@ struct Args {
   bool allDevices = false;                // --all-devices: EVERY device matching -d becomes one x-slab (RCCL halo)
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
+  bool indexedMesh = false;               // --indexed-mesh: the frames' surface as an indexed mesh (one vertex per lattice edge)
 
   struct SourceArg {
     std::array<double, 7> v;  // x, y, z, vx, vy, vz, rate
@@ -78,6 +79,9 @@ struct Args {
           "      --slabs=[K]                       K slabs on the first matching device (in-process exchange; tests)\n"
           "      --surface-tension=[g[,b]]         Opt-in surface tension (cohesion g) and adhesion to obstacles (b) after\n"
           "                                        Akinci et al. 2013; not in the reference. Single device only\n"
+          "      --indexed-mesh                    Extract the surface as an indexed mesh (one vertex per crossed lattice\n"
+          "                                        edge, watertight by index); mesh.obj becomes an indexed OBJ.\n"
+          "                                        Single device only\n"
           "      --source=[x,y,z,vx,vy,vz,rate[,tag]]  An inlet (repeatable): a floor x ceil sheet of sqrt(rate) particles\n"
           "                                        per frame at the world point, with that velocity. With --resident\n"
           "                                        emitted on the GPU, otherwise by advance(). Single device only\n"
@@ -128,6 +132,7 @@ struct Args {
         else if (a == "--fast-math") fastMath = true;
         else if (a == "--json") json = true;
         else if (a == "--all-devices") allDevices = true;
+        else if (a == "--indexed-mesh") indexedMesh = true;
         else if (value(i, a, "", "--slabs", v)) slabs = std::stoull(v);
         else if (value(i, a, "", "--surface-tension", v)) {
           const size_t comma = v.find(',');

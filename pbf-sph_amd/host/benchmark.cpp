@@ -14,6 +14,8 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <filesystem>
+#include <fstream>
 #include <iomanip>
 #include <numeric>
 
@@ -109,6 +111,10 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cerr << "--surface-tension is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
   }
+  if (args.indexedMesh && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--indexed-mesh is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
   // + inlets and outlets (sph::Scene::sources / drains): with --resident they go to the device (hip_impl::Solver::step),
   // without it into the Scene advance() gets
   sph::Scene<T, N, sph::vec> scene;
@@ -127,6 +133,8 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   }
   sph::hip_impl::Solver<T, N> solver(N(0.1), devices, flags);
   if (surfaceTension) solver.surfaceTension(N(args.cohesion), N(args.adhesion));
+  if (args.indexedMesh) solver.indexedMesh(true);
+  sph::hip_impl::IndexedMesh<N, sph::vec> indexed;  // --indexed-mesh --resident: the last frame's mesh
   // the resident arrays grow by what the inlets emit: room for every frame of the run
   if (args.resident && emittedPerFrame) solver.reserve(particles.size() + (args.warmup + args.iterations) * emittedPerFrame);
   sph::Result<T, N, sph::vec> result;
@@ -138,7 +146,8 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   auto one = [&](size_t frame) {
     if (args.resident) {
       solver.step(frameParam(frame), scene);
-      if (param.surface && solver.count()) result.mesh = solver.surface(frameParam(frame));
+      if (param.surface && solver.count() && args.indexedMesh) indexed = solver.surfaceIndexed(frameParam(frame));
+      else if (param.surface && solver.count()) result.mesh = solver.surface(frameParam(frame));
       solver.sync();  // per-frame time like the reference's blocking advance()
     } else {
       result = solver.advance(frameParam(frame), scene, particles);
@@ -183,6 +192,9 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   const double psps = double(particles.size()) * double(frames) / seconds;
   std::cout << std::setprecision(6) << "Particle-steps/s     : " << psps << " (" << (args.resident ? "device-resident" : "advance(): upload+step+download per frame")
             << ", K=" << args.solverIter << ", " << (args.fp64 ? "fp64" : "fp32") << ")\n";
+  const auto &imesh = args.resident ? indexed : solver.lastIndexedMesh();
+  if (args.indexedMesh)
+    std::cout << "Indexed mesh         : " << imesh.vs.size() << " vertices, " << imesh.tris.size() / 3 << " triangles\n";
   if (args.verbose) {
     const char *names[16];
     double ms[16];
@@ -199,6 +211,16 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
               << ",\"seconds\":" << seconds << ",\"particle_steps_per_s\":" << psps << ",\"frame_ms_mean\":" << st.mean
               << "}" << std::endl;
   sph::save(result, particles, output);
+  if (args.indexedMesh && !output.empty()) {  // mesh.obj as an indexed OBJ: V `v`, V `vn`, T `f a//a b//b c//c`
+    std::ofstream obj(std::filesystem::path(output) / "mesh.obj");
+    for (const auto &v : imesh.vs) obj << "v " << v.x << ' ' << v.y << ' ' << v.z << '\n';
+    for (const auto &n : imesh.ns) obj << "vn " << n.x << ' ' << n.y << ' ' << n.z << '\n';
+    for (size_t t = 0; t + 2 < imesh.tris.size(); t += 3) {
+      obj << 'f';
+      for (size_t k = 0; k < 3; ++k) obj << ' ' << imesh.tris[t + k] + 1 << "//" << imesh.tris[t + k] + 1;
+      obj << '\n';
+    }
+  }
   std::cout << "Results flushed." << std::endl;
   return 0;
 }

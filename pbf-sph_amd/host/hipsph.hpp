@@ -178,6 +178,15 @@ inline std::vector<uint32_t> recut(const std::vector<uint32_t> &old, const std::
 // that, so the "copy two headers, add a case" recipe of INTEGRATION.md is compiled, linked and run by the test-suite.
 // What V must offer (glm::vec does): x / y / z[/ w] members, V<3>(a, b, c) from mixed arithmetic types, V<3> + V<3>,
 // V<3> - V<3>, V<3> * N, and a packed layout.
+// The surface as an indexed mesh (pbf_surface_indexed; no reference counterpart, hence declared here and not in sph.hpp):
+// one vertex per crossed lattice edge, triangle t = {tris[3t], tris[3t + 1], tris[3t + 2]}; vs[tris[k]] is vertex k of the
+// ColouredMesh soup.
+template <typename N, template <size_t S, typename C = N> typename V> struct IndexedMesh {
+  std::vector<V<3>> vs{}, ns{};
+  std::vector<V<4>> cs{};
+  std::vector<uint32_t> tris{};
+};
+
 #ifdef PBF_SPH_HAS_VEC
 template <typename T, typename N, template <size_t, typename C = N> typename V = sph::vec>
 #else
@@ -204,6 +213,8 @@ class Solver final : public sph::Solver<T, N, V> {
   uint64_t frame_ = 0;
   unsigned rebalanceEvery_ = 8;
   bool attached_ = false;
+  bool indexedFrames_ = false;       // indexedMesh(true): advance() extracts the indexed mesh instead of Result::mesh
+  IndexedMesh<N, V> lastIndexed_;
   bool multi() const { return slabs_.size() > 1; }
 
   // PBF_SHIM_TIMING=1: mean host time of advance()'s phases, printed by the destructor (diagnostic)
@@ -497,7 +508,17 @@ public:
     clk.lap(1);
     sph::Result<T, N, V> result;
     if (!scene.queries.empty()) result.queries = queryHost(config, scene);
-    if (config.surface) {  // ompsph.hpp:277-477
+    if (config.surface && indexedFrames_) {  // the same order of events as below, with the indexed mesh
+      const auto l = layout();
+      xs.resize(pbf_count(ctx_));
+      check(pbf_download_aos_begin(ctx_, xs.data(), &l), "pbf_download_aos_begin");
+      IndexedCopy copy(*this, config, scene, lastIndexed_);
+      clk.lap(2);
+      check(pbf_download_aos_end(ctx_), "pbf_download_aos_end");
+      clk.lap(3);
+      copy.join();
+      clk.lap(4);
+    } else if (config.surface) {  // ompsph.hpp:277-477
       // the mesh lands in page-locked staging (one DMA); its three vectors are then built on host threads WHILE the
       // particles travel back over PCIe
       // — and the particles set off BEFORE the surface kernels start (pbf_download_aos_begin: their DMA runs on a copy
@@ -551,7 +572,65 @@ public:
     return mesh;
   }
 
+  // The same surface as an indexed mesh: 40 V + 12 T bytes in fp32 instead of 120 T, watertight by index.  Single device (an
+  // edge on a slab's cut plane belongs to a node of another device).
+  IndexedMesh<N, V> surfaceIndexed(const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene = {}) {
+    if (multi()) throw std::runtime_error("the indexed mesh is a single-device feature");
+    IndexedMesh<N, V> mesh;
+    IndexedCopy(*this, config, scene, mesh).join();
+    return mesh;
+  }
+  // indexedMesh(true): advance() runs config.surface through the indexed path; Result::mesh stays empty and the frame's mesh
+  // is lastIndexedMesh() until the next advance().  Off by default: advance() is the reference's.
+  Solver &indexedMesh(bool on) {
+    if (on && multi()) throw std::runtime_error("the indexed mesh is a single-device feature");
+    indexedFrames_ = on;
+    return *this;
+  }
+  const IndexedMesh<N, V> &lastIndexedMesh() const { return lastIndexed_; }
+
 private:
+  // pbf_surface_indexed + the hand-over, shaped like MeshCopy below: one DMA into the page-locked staging, four range
+  // assignments on threads of their own once the mesh is large enough to pay for them
+  struct IndexedCopy {
+    IndexedMesh<N, V> &mesh;
+    const V<3> *v3 = nullptr, *n3 = nullptr;
+    const V<4> *c4 = nullptr;
+    const uint32_t *t3 = nullptr;
+    size_t nv = 0, ni = 0;
+    std::thread th[4];
+    IndexedCopy(Solver &s, const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene, IndexedMesh<N, V> &out)
+        : mesh(out) {
+      const pbf_params p = s.params(config, scene);
+      const pbf_mc_params mc{double(config.surface->resolution), double(config.surface->isolevel),
+                             double(config.surface->particleSize), double(config.surface->particleInfluence)};
+      uint64_t vertices = 0, triangles = 0;
+      s.check(pbf_surface_indexed(s.ctx_, &p, &mc, &vertices, &triangles), "pbf_surface_indexed");
+      const void *pv = nullptr, *pn = nullptr, *pc = nullptr;
+      s.check(pbf_map_mesh_indexed(s.ctx_, &pv, &pn, &pc, &t3), "pbf_map_mesh_indexed");
+      nv = size_t(vertices), ni = size_t(triangles) * 3;
+      v3 = static_cast<const V<3> *>(pv), n3 = static_cast<const V<3> *>(pn), c4 = static_cast<const V<4> *>(pc);
+      if (ni == 0) nv = 0;
+      if (ni >= (size_t(1) << 16)) {
+        th[0] = std::thread([this] { mesh.vs.assign(v3, v3 + nv); });
+        th[1] = std::thread([this] { mesh.ns.assign(n3, n3 + nv); });
+        th[2] = std::thread([this] { mesh.cs.assign(c4, c4 + nv); });
+        th[3] = std::thread([this] { mesh.tris.assign(t3, t3 + ni); });
+      }
+    }
+    void join() {
+      if (th[0].joinable()) {
+        for (auto &t : th) t.join();
+      } else {
+        mesh.vs.assign(v3, v3 + nv), mesh.ns.assign(n3, n3 + nv), mesh.cs.assign(c4, c4 + nv), mesh.tris.assign(t3, t3 + ni);
+      }
+    }
+    ~IndexedCopy() {
+      for (auto &t : th)
+        if (t.joinable()) t.join();
+    }
+  };
+
   // pbf_surface + the mesh hand-over.  ColouredMesh(size) would zero-fill 54 MB (1 M particles) that a pageable
   // device-to-host copy then overwrites at a few GB/s: 11 ms per frame in round 2.  Instead: ONE DMA into the library's
   // page-locked staging (pbf_map_mesh), then the three vectors are range-assigned from it (no fill), each on a thread of its
