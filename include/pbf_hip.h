@@ -213,11 +213,54 @@ enum pbf_buffer {
                          (opt-in extra, absent from the reference), device order; PBF_ERR_STATE when there is none */
   PBF_BUF_SURFACE = 5, /* N[4n]: {n.xyz, rho} of the last surface-tension pass (pbf_set_surface_tension), device order; zero
                           for obstacles; PBF_ERR_STATE when there is none */
-  PBF_BUF_COUNT_ = 6,
+  PBF_BUF_DENSITY = 6, /* N[n]: rho_i of the last density pass (pbf_diagnostics with PBF_DIAG_DENSITY), device order; zero for
+                          obstacles; PBF_ERR_STATE when there is none, or once the arrays have changed since */
+  PBF_BUF_COUNT_ = 7,
 };
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes);
 size_t pbf_table_size(const pbf_ctx *ctx);                /* Morton(extent), sph.hpp:240 */
 int pbf_grid_extent(const pbf_ctx *ctx, uint64_t extent[3], double min_extent[3]); /* ompsph.hpp:132-135 */
+
+/* ---- diagnostics of the resident state (no reference counterpart) ----------------------------------------------
+ * What a caller otherwise downloads every array for: did the run blow up, how fast is the fastest particle (the number a
+ * CFL time step needs), energy and momentum, how far the fluid is from rest density after K iterations, how many
+ * neighbours a particle has (the number h, "list_max" and "nbr_chunks" are tuned by).  Computed on the device and
+ * reduced there in a fixed order without atomics: the same state gives the same bytes, call after call.  Its own call on
+ * the ctx stream, synchronising (one polled read-back of the 216-byte record, no hipStreamSynchronize); never part of a
+ * step or of a captured hipGraph, and a step after it runs exactly as it would have without.
+ *
+ * Stream part (always): over exactly the arrays pbf_download would return now — valid whenever pbf_download is, straight
+ * after pbf_upload included.  `params` may be NULL when what == 0.  A fluid particle with a non-finite component of position
+ * or velocity counts in n_nonfinite and in nothing else; obstacles count in n_obstacle and in nothing else; n_fluid counts
+ * the remaining, finite fluid particles (the three add up to pbf_count).  Over those, every term formed in double from the
+ * stored values widened to double (on fp32 contexts too):
+ *   mass = sum m;  moment = sum m x (x the world position: the centre of mass is moment / mass);  momentum = sum m v;
+ *   kinetic = 1/2 sum m (vx^2 + vy^2 + vz^2);  max_speed = sqrt(max (vx^2 + vy^2 + vz^2));  aabb_min / aabb_max = the
+ *   per-axis extrema of the position.
+ * With no finite fluid particle every floating field is 0.
+ *
+ * Density part (what & PBF_DIAG_DENSITY): the preconditions of pbf_surface — a step has run and its table is still valid,
+ * PBF_ERR_STATE otherwise; so are params whose bounds or scale describe another grid than the last step's (as in
+ * pbf_query_cells).  On the final pStar with the candidates of the predict-time 27 cells, exactly as the extras passes
+ * run: for each fluid particle  rho_i = m_i sum_j W_poly6(r_ij)  over the candidates j with r <= h, i itself and obstacles
+ * included — lambda's own expressions (ompsph.hpp:215-232), i.e. the residual iteration K + 1 would see;
+ * C_i = rho_i / rho0 - 1 (rho0 = 6378);  nbr_i = the candidates j != i with r <= h.  n_density = fluid particles evaluated;
+ * rho_min / rho_max / rho_mean over rho_i;  err_mean = mean |C|, err_max = max |C|, compression_mean = mean max(C, 0);
+ * nbr_max / nbr_mean over nbr_i.  The means are double sums of the per-particle values (computed in N), divided once.
+ * Without the flag the density fields are 0.  PBF_BUF_DENSITY reads rho_i back.
+ *
+ * PBF_ERR_INVALID: out == NULL, unknown bits in `what`, params == NULL with the density flag.  Slab mode is not supported
+ * (global sums need an all-reduce and the ghost copies would have to be left out): PBF_ERR_STATE for both parts.  On every
+ * error *out is untouched. */
+enum { PBF_DIAG_DENSITY = 1u << 0 };
+typedef struct pbf_diag {
+  uint64_t n_fluid, n_obstacle, n_nonfinite;
+  double mass, moment[3], momentum[3], kinetic, max_speed;
+  double aabb_min[3], aabb_max[3];
+  uint64_t n_density, nbr_max;
+  double rho_min, rho_max, rho_mean, err_mean, err_max, compression_mean, nbr_mean;
+} pbf_diag;
+int pbf_diagnostics(pbf_ctx *ctx, const pbf_params *params, uint32_t what, pbf_diag *out);
 
 /* Device self-test of the trimmed exact sqrt / divides the precise pair terms use (csrc/pbf_kernels.hpp sqrt_rsq /
  * div_seeded / div_ranged) against the compiler's full IEEE forms, exhaustively: mismatches[0] sqrt over EVERY fp32 value

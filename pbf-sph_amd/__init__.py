@@ -10,6 +10,9 @@ The directory name has a hyphen (it mirrors the reference repo's name), so impor
 `load_package()` from tests/conftest.py / bench.py, or via importlib by path.
 """
 from .capi import (  # noqa: F401
+    BUF_DENSITY,
+    DIAG_DENSITY,
+    Diag,
     FLAG_FAST_MATH,
     FLAG_NO_LDS,
     FLAG_STAGE_TIMING,

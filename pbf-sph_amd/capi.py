@@ -18,6 +18,8 @@ BUF_KEYS, BUF_TABLE, BUF_PSTAR = 0, 1, 2
 BUF_NBR_COUNT = 3
 BUF_OMEGA = 4
 BUF_SURFACE = 5
+BUF_DENSITY = 6
+DIAG_DENSITY = 1 << 0
 
 
 class PbfError(RuntimeError):
@@ -95,6 +97,23 @@ class Drain(C.Structure):
     _fields_ = [("centre", C.c_double * 3), ("width", C.c_double)]
 
 
+class Diag(C.Structure):
+    """pbf_diag (include/pbf_hip.h): 27 eight-byte words"""
+    _fields_ = [("n_fluid", C.c_uint64), ("n_obstacle", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("mass", C.c_double), ("moment", C.c_double * 3), ("momentum", C.c_double * 3), ("kinetic", C.c_double),
+                ("max_speed", C.c_double), ("aabb_min", C.c_double * 3), ("aabb_max", C.c_double * 3),
+                ("n_density", C.c_uint64), ("nbr_max", C.c_uint64),
+                ("rho_min", C.c_double), ("rho_max", C.c_double), ("rho_mean", C.c_double), ("err_mean", C.c_double),
+                ("err_max", C.c_double), ("compression_mean", C.c_double), ("nbr_mean", C.c_double)]
+
+    def as_dict(self):
+        out = {}
+        for name, t in self._fields_:
+            v = getattr(self, name)
+            out[name] = np.array(v[:], np.float64) if hasattr(v, "__len__") else (int(v) if t is C.c_uint64 else float(v))
+        return out
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -140,6 +159,7 @@ _SIGS = {
     "pbf_set_drains": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pbf_scene_host_syncs": (C.c_uint64, [C.c_void_p]),
     "pbf_query_cells": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pbf_diagnostics": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_uint32, C.POINTER(Diag)]),
     "pbf_read_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "pbf_table_size": (C.c_size_t, [C.c_void_p]),
     "pbf_selftest_math": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -327,6 +347,21 @@ class Solver:
         (zero for obstacles)"""
         a = np.empty((self.n, 4), self.dtype)
         self._chk(self.L.pbf_read_buffer(self.ctx, BUF_SURFACE, _vp(a), a.nbytes), "read surface state")
+        return a
+
+    def diagnostics(self, p=None, density=False, raw=False):
+        """Conserved sums, extrema and — `density`, which needs the params of the last step — the density residual of the
+        resident state, computed and reduced on the device (pbf_diagnostics, include/pbf_hip.h) -> dict of the fields of
+        pbf_diag (3-vectors as float64 arrays); raw: the Diag structure itself."""
+        d = Diag()
+        what = DIAG_DENSITY if density else 0
+        self._chk(self.L.pbf_diagnostics(self.ctx, None if p is None else C.byref(p), what, C.byref(d)), "pbf_diagnostics")
+        return d if raw else d.as_dict()
+
+    def density(self):
+        """(n,): rho_i of the last diagnostics(p, density=True), device order (zero for obstacles)"""
+        a = np.empty(self.n, self.dtype)
+        self._chk(self.L.pbf_read_buffer(self.ctx, BUF_DENSITY, _vp(a), a.nbytes), "read density")
         return a
 
     def reserve(self, capacity):

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <string>
 #include <vector>
@@ -154,6 +155,15 @@ struct pbf_ctx {
   uint32_t sceneSeq = 0;
   uint64_t sceneHostSyncs = 0;
   DevBuf queryPoints, queryCounts, queryIds;  // pbf_query_cells
+  // pbf_diagnostics: the density pass's own outputs (N[cap] rho, uint32[cap] neighbour counts; allocated with the first
+  // density request), one partial record per DIAG_TILE particles, the pinned record the last kernel writes and the host
+  // polls.  diagDensityValid: diagRho holds the pass of the CURRENT sorted set (PBF_BUF_DENSITY) — set by the pass, dropped by
+  // every sort (stage_sort, or a replayed one: restore), and only ever believed while st.sorted holds, which every event
+  // that changes the arrays clears.  An observer's record, not derived state of the step: it is no part of DerivedState.
+  DevBuf diagRho, diagNbr, diagPartials;
+  DiagRecord *hostDiag = nullptr;
+  uint32_t diagSeq = 0;
+  bool diagDensityValid = false;
   // advance() path: the caller's std::vector<Particle> buffer, page-locked in place (hipHostRegister) so the per-frame
   // 56-byte-per-particle upload and download are plain DMA instead of the runtime's pageable staging
   void *regPtr = nullptr;
@@ -599,6 +609,7 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   ctx->n = nLive;
   ctx->gatherSeq = 0;  // (fresh tickets)
   ctx->st.sorted_now(rows, rowDiffuse);
+  ctx->diagDensityValid = false;  // (a new order: the last density pass describes the old one)
   if (!rowDiffuse) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
   return PBF_OK;
 }
@@ -957,6 +968,18 @@ int ensure_surface(pbf_ctx *ctx) {
   return ensure(ctx, ctx->surfB, bytes);
 }
 
+// pbf_diagnostics' buffers, sized to the particle capacity: allocated by the first call that needs them (`first`) and, once
+// they exist, regrown when an upload grows the capacity
+int ensure_diag(pbf_ctx *ctx, bool first, bool density) {
+  if (first || ctx->diagPartials.p)
+    if (int rc = ensure(ctx, ctx->diagPartials, (ctx->cap / DIAG_TILE + 2) * sizeof(DiagPartial))) return rc;
+  if ((first && density) || ctx->diagRho.p) {
+    if (int rc = ensure(ctx, ctx->diagRho, ctx->cap * (ctx->fp64 ? sizeof(double) : sizeof(float)))) return rc;
+    if (int rc = ensure(ctx, ctx->diagNbr, ctx->cap * 4)) return rc;
+  }
+  return PBF_OK;
+}
+
 // Surface tension and adhesion (Akinci et al. 2013), last among the extras: density -> A, normals -> B, velocity update.
 template <typename N, bool FAST> int surface_tension_impl(pbf_ctx *ctx, const StepConsts<N> &c) {
   if (int rc = ensure_surface(ctx)) return rc;
@@ -1149,6 +1172,7 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
   if (int rc = ensure_particles(ctx, n)) return rc;
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
+  if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
   ctx->st.arrays_replaced(0);
   ctx->ghostsPending = false, ctx->slabActive = false;
@@ -1352,7 +1376,7 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->mcEdgeWord, &ctx->mcEdgeOffsets, &ctx->mcEdgeSums, &ctx->meshT, &ctx->meshV, &ctx->meshN,
                    &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB,
                    &ctx->sceneSources, &ctx->sceneDrains, &ctx->drainCounts, &ctx->queryPoints, &ctx->queryCounts,
-                   &ctx->queryIds};
+                   &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
@@ -1364,6 +1388,7 @@ void pbf_destroy(pbf_ctx *ctx) {
   if (ctx->evPacked) (void)hipEventDestroy(ctx->evPacked);
   if (ctx->hostCounts) (void)hipHostFree(ctx->hostCounts);
   if (ctx->hostScene) (void)hipHostFree(ctx->hostScene);
+  if (ctx->hostDiag) (void)hipHostFree(ctx->hostDiag);
   if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
   if (ctx->regPtr) (void)hipHostUnregister(ctx->regPtr);
   if (ctx->ownStream) (void)hipStreamDestroy(ctx->stream);
@@ -1422,6 +1447,7 @@ int pbf_upload_aos(pbf_ctx *ctx, size_t n, const void *particles, const pbf_aos_
   if (int rc = ensure_particles(ctx, n)) return rc;
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
+  if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
   ctx->st.arrays_replaced(0);
   ctx->n = n, ctx->uploaded = n;
@@ -1540,6 +1566,7 @@ StepState snapshot(pbf_ctx *ctx) {
 void restore(pbf_ctx *ctx, const StepState &s) {
   ctx->st = s.st, ctx->hasObstacles = s.hasObstacles;  // (all of the derived state, not only what the key compares)
   ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
+  ctx->diagDensityValid = false;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
@@ -1735,22 +1762,74 @@ template <typename N> int upload_drains(pbf_ctx *ctx, const std::vector<pbf_drai
   HIPCHK(ctx, hipMemcpy(ctx->sceneDrains.p, img.data(), img.size() * sizeof(SceneDrain<N>), hipMemcpyHostToDevice));
   return PBF_OK;
 }
-template <typename N>
-int query_impl(pbf_ctx *ctx, const pbf_params *p, size_t np, const double *points, uint32_t *counts, uint64_t *ids, size_t cap) {
-  // make_consts leaves its grid in the ctx: keep the last step's, and refuse params that describe another one (the table,
-  // the keys and the arrays on the device belong to the step's grid; a larger tableN would index beyond them)
+// The consts of `p` for a call that works on what the last step left: make_consts leaves its grid in the ctx, so the last
+// step's is kept, and params that describe another one are refused (the table, the keys and the arrays on the device belong to
+// the step's grid; a larger tableN would index beyond them).
+template <typename N> int consts_on_last_grid(pbf_ctx *ctx, const pbf_params *p, StepConsts<N> &c, const char *who) {
   const uint32_t tableN = ctx->tableN;
   uint64_t extent[3];
   double minExtent[3];
   std::memcpy(extent, ctx->extent, sizeof(extent)), std::memcpy(minExtent, ctx->minExtent, sizeof(minExtent));
-  StepConsts<N> c;
   const int made = make_consts<N>(ctx, p, c);
   const bool sameGrid = made == PBF_OK && c.tableN == tableN && std::memcmp(extent, ctx->extent, sizeof(extent)) == 0 &&
                         std::memcmp(minExtent, ctx->minExtent, sizeof(minExtent)) == 0;
   ctx->tableN = tableN;
   std::memcpy(ctx->extent, extent, sizeof(extent)), std::memcpy(ctx->minExtent, minExtent, sizeof(minExtent));
   if (made != PBF_OK) return made;
-  if (!sameGrid) return fail(ctx, PBF_ERR_STATE, "pbf_query_cells: bounds / scale differ from the last step's");
+  if (!sameGrid) return fail(ctx, PBF_ERR_STATE, std::string(who) + ": bounds / scale differ from the last step's");
+  return PBF_OK;
+}
+
+// pbf_diagnostics.  The stream part reads the arrays pbf_download would return; the density part runs DensityOp over the final
+// pStar (pstar[cur] after finalise) on the last step's keys and table, through whichever gather kernel the ctx is set to.
+// Neither touches a buffer a step reads, a ticket word or the derived state (materialise_pstar apart, which pbf_surface and
+// PBF_BUF_PSTAR do alike): a step after it makes the launches and takes the graph it would have without.
+static_assert(sizeof(pbf_diag) == 27 * 8 && offsetof(DiagRecord, seq) == sizeof(pbf_diag) &&
+                  offsetof(pbf_diag, mass) == offsetof(DiagRecord, mass) &&
+                  offsetof(pbf_diag, n_density) == offsetof(DiagRecord, n_density) &&
+                  offsetof(pbf_diag, nbr_mean) == offsetof(DiagRecord, nbr_mean),
+              "DiagRecord (pbf_kernels.hpp) is pbf_diag followed by the polled word");
+template <typename N, bool FAST> int density_pass(pbf_ctx *ctx, const StepConsts<N> &c) {
+  const int s = ctx->st.cur;
+  typename DensityOp<N, FAST>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
+                                      ctx->type[s].as<const uint8_t>(), ctx->diagRho.as<N>(), ctx->diagNbr.as<uint32_t>()};
+  return launch_gather<N, DensityOp<N, FAST>>(ctx, c, a);
+}
+template <typename N> int diagnostics_impl(pbf_ctx *ctx, const pbf_params *p, bool density, pbf_diag *out) {
+  StepConsts<N> c;
+  if (density)
+    if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_diagnostics")) return rc;
+  if (int rc = ensure_diag(ctx, /*first=*/true, density)) return rc;
+  if (!ctx->hostDiag) {
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostDiag), sizeof(DiagRecord), hipHostMallocDefault));
+    std::memset(ctx->hostDiag, 0, sizeof(DiagRecord));
+  }
+  const int s = ctx->st.cur;
+  const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
+  if (density && n) {
+    if (int rc = materialise_pstar<N>(ctx)) return rc;
+    if (int rc = ctx->fast ? density_pass<N, true>(ctx, c) : density_pass<N, false>(ctx, c)) return rc;
+    ctx->diagDensityValid = true;
+  }
+  if (nb)
+    hipLaunchKernelGGL((k_diag_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pos4[s].as<const vec4<N>>(),
+                       ctx->vel4[s].as<const vec4<N>>(), ctx->type[s].as<const uint8_t>(),
+                       density ? ctx->diagRho.as<const N>() : static_cast<const N *>(nullptr),
+                       ctx->diagNbr.as<const uint32_t>(), ctx->diagPartials.as<DiagPartial>());
+  const uint32_t seq = ++ctx->diagSeq ? ctx->diagSeq : ++ctx->diagSeq;  // (never 0: the pinned word starts there)
+  hipLaunchKernelGGL(k_diag_final, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->diagPartials.as<const DiagPartial>(),
+                     ctx->hostDiag, seq);
+  LAUNCH_CHECK(ctx);
+  if (int rc = wait_for_word(ctx, &ctx->hostDiag->seq, seq, "diagnostics read-back")) return rc;
+  std::atomic_thread_fence(std::memory_order_acquire);  // (the record is read through a plain pointer, after the polled word)
+  std::memcpy(out, ctx->hostDiag, sizeof(pbf_diag));
+  return PBF_OK;
+}
+
+template <typename N>
+int query_impl(pbf_ctx *ctx, const pbf_params *p, size_t np, const double *points, uint32_t *counts, uint64_t *ids, size_t cap) {
+  StepConsts<N> c;
+  if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_query_cells")) return rc;
   std::vector<N> pts(3 * np);
   for (size_t k = 0; k < 3 * np; ++k) pts[k] = N(points[k]);
   if (int rc = ensure(ctx, ctx->queryPoints, pts.size() * sizeof(N))) return rc;
@@ -1825,6 +1904,22 @@ int pbf_query_cells(pbf_ctx *ctx, const pbf_params *p, size_t n_points, const do
   return DISPATCH(ctx, query_impl, ctx, p, n_points, points, counts, ids, cap_per_point);
 }
 
+int pbf_diagnostics(pbf_ctx *ctx, const pbf_params *p, uint32_t what, pbf_diag *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_diagnostics: out == NULL");
+  if (what & ~uint32_t(PBF_DIAG_DENSITY)) return fail(ctx, PBF_ERR_INVALID, "pbf_diagnostics: unknown bits in `what`");
+  const bool density = (what & PBF_DIAG_DENSITY) != 0;
+  if (density && !p) return fail(ctx, PBF_ERR_INVALID, "pbf_diagnostics: PBF_DIAG_DENSITY needs params");
+  if (density && (!(p->scale > 0) || !(p->dt > 0))) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  // global sums would need an all-reduce, and the copies of the neighbours' boundary columns would have to be left out
+  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
+    return fail(ctx, PBF_ERR_STATE, "pbf_diagnostics is not supported in slab mode");
+  if (density && !ctx->st.sorted)
+    return fail(ctx, PBF_ERR_STATE, "pbf_diagnostics: the density part needs a step first (no valid cell table)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return DISPATCH(ctx, diagnostics_impl, ctx, p, density, out);
+}
+
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
   if (!ctx || !host) return PBF_ERR_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1851,6 +1946,11 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
     case PBF_BUF_SURFACE:
       if (!ctx->st.surfaceValid) return fail(ctx, PBF_ERR_STATE, "no surface-tension pass since the arrays last changed (pbf_set_surface_tension)");
       src = ctx->surfB.p, avail = std::min(ctx->n * v, ctx->surfB.cap);
+      break;
+    case PBF_BUF_DENSITY:
+      if (!ctx->diagDensityValid || !ctx->st.sorted)
+        return fail(ctx, PBF_ERR_STATE, "no density pass since the arrays last changed (pbf_diagnostics with PBF_DIAG_DENSITY)");
+      src = ctx->diagRho.p, avail = std::min(ctx->n * (v / 4), ctx->diagRho.cap);
       break;
     default: return fail(ctx, PBF_ERR_INVALID, "unknown buffer");
   }

@@ -2787,4 +2787,208 @@ __global__ __launch_bounds__(64) void k_query_cells(StepConsts<N> c, const N *__
   if (lane == 0) counts[q] = found;
 }
 
+// ------------------------------------------------------------------------------------------------
+// pbf_diagnostics: what the state is, told on the device.  No reference counterpart.
+//
+// DensityOp: LambdaOp's density sum on its own — rho_i = m_i sum_{j in N(i) u {i}} W_poly6(r), the very expressions
+// and candidate order of LambdaOp::add / add_bf (ompsph.hpp:215-232), so it is the residual one more solver iteration would
+// see — plus the number of candidates j != i with r <= h.  The candidate carries its INDEX, which is what tells a particle
+// meeting itself from a coincident neighbour.  It reads pStar, masses and types and writes two arrays of its own.
+// ------------------------------------------------------------------------------------------------
+template <typename N> struct DensitySrc {
+  vec4<N> p;     // pStar.xyz (.w unused)
+  uint32_t idx;  // the candidate's index in the sorted arrays
+};
+template <typename N> __device__ inline void pin_registers(DensitySrc<N> &b) {  // (the list readers' pipelining, see above)
+  pin_registers(b.p);
+  asm volatile("" : "+v"(b.idx));
+}
+template <typename N, bool FAST> struct DensityOp {
+  using Src = DensitySrc<N>;
+  struct Args {
+    const vec4<N> *pstar, *pos4;  // (mass = pos4[i].w)
+    const uint8_t *type;
+    N *rho;         // N[n], 0 for obstacles
+    uint32_t *nbr;  // uint32[n], 0 for obstacles
+  };
+  static constexpr bool kNeedsCandidateType = false;  // obstacles are candidates, as for lambda
+  static constexpr bool kFilter = true;
+  static constexpr bool kTileable = false;
+  __device__ static Src load(const Args &a, uint32_t b) { return Src{a.pstar[b], b}; }
+  vec4<N> pa;
+  N mass, rho;
+  uint32_t self, nbr;
+  __device__ bool near(const StepConsts<N> &c, const Src &b) const { return maybe_within_h<N>(pa, b.p, c.h2filter); }
+  __device__ bool begin(const StepConsts<N> &c, const Args &a, uint32_t i) {
+    if (c.hasObstacles && a.type[i] != 0) {
+      a.rho[i] = N(0), a.nbr[i] = 0u;
+      return false;
+    }
+    pa = a.pstar[i], mass = a.pos4[i].w;
+    rho = N(0), nbr = 0u, self = i;
+    return true;
+  }
+  __device__ void add(const StepConsts<N> &c, const Src &b) { add_bf(c, b); }
+  // (an excluded pair adds exactly +0, like LambdaOp::add_bf: the sum is the same bits on every gather kernel)
+  __device__ void add_bf(const StepConsts<N> &c, const Src &b, bool valid = true) {
+    const auto g = pair_geom<N, FAST>(pa, b.p, c.h);
+    const bool in = g.inH && valid;
+    const N d = (c.h * c.h) - g.r * g.r;
+    const N w = mass * (c.poly6Factor * (d * d * d));
+    rho += in ? w : N(0);
+    nbr += (in && b.idx != self) ? 1u : 0u;
+  }
+  __device__ void end(const StepConsts<N> &, const Args &a, uint32_t i) { a.rho[i] = rho, a.nbr[i] = nbr; }
+};
+
+// The reduction: two launches of a fixed shape, no atomics — the same state gives the same bits every time.
+//   k_diag_partial  workgroup b owns particles [DIAG_TILE b, DIAG_TILE (b + 1)), lane = particle in rounds of 64 like
+//                   k_drain_count; a lane folds its DIAG_ITEMS particles in double, the wave folds its lanes with an xor
+//                   butterfly (a + b is commutative: every lane ends with the same bits), lane 0 of each wave parks the wave's
+//                   record in LDS, thread 0 folds the waves in wave order and stores ONE record per workgroup;
+//   k_diag_final    one workgroup: rounds of BLOCK records in index order, each round folded the same way and then onto the
+//                   running record; thread 0 derives the pbf_diag and hands it to the host's pinned words, followed — behind
+//                   a system-scope fence — by the sequence number the host polls (the k_drain_scan hand-over).
+// Every term is formed in double from the stored value widened to double (no contraction: -ffp-contract=off).
+constexpr int DIAG_ITEMS = 4;
+constexpr int DIAG_TILE = BLOCK * DIAG_ITEMS;
+struct DiagPartial {
+  // sum: mass, moment.xyz, momentum.xyz, sum m |v|^2, sum rho, sum |C|, sum max(C, 0)
+  // hi:  max |v|^2, aabb_max.xyz, rho max, max |C|          lo: aabb_min.xyz, rho min
+  // cnt: finite fluid, obstacles, non-finite fluid, density particles, sum nbr, max nbr (the last one folds by max)
+  double sum[11], hi[6], lo[4];
+  unsigned long long cnt[6];
+};
+__device__ inline void diag_identity(DiagPartial &p) {
+  for (int k = 0; k < 11; ++k) p.sum[k] = 0.0;
+  for (int k = 0; k < 6; ++k) p.hi[k] = -__builtin_huge_val();
+  for (int k = 0; k < 4; ++k) p.lo[k] = __builtin_huge_val();
+  for (int k = 0; k < 6; ++k) p.cnt[k] = 0ull;
+}
+// a (the earlier record) takes b in
+__device__ inline void diag_fold(DiagPartial &a, const DiagPartial &b) {
+  for (int k = 0; k < 11; ++k) a.sum[k] += b.sum[k];
+  for (int k = 0; k < 6; ++k) a.hi[k] = fmax(a.hi[k], b.hi[k]);
+  for (int k = 0; k < 4; ++k) a.lo[k] = fmin(a.lo[k], b.lo[k]);
+  for (int k = 0; k < 5; ++k) a.cnt[k] += b.cnt[k];
+  a.cnt[5] = a.cnt[5] > b.cnt[5] ? a.cnt[5] : b.cnt[5];
+}
+__device__ inline void diag_wave_fold(DiagPartial &p) {
+#pragma unroll 1
+  for (int m = 1; m < 64; m <<= 1) {
+    DiagPartial o;
+    for (int k = 0; k < 11; ++k) o.sum[k] = __shfl_xor(p.sum[k], m);
+    for (int k = 0; k < 6; ++k) o.hi[k] = __shfl_xor(p.hi[k], m);
+    for (int k = 0; k < 4; ++k) o.lo[k] = __shfl_xor(p.lo[k], m);
+    for (int k = 0; k < 6; ++k) o.cnt[k] = __shfl_xor(p.cnt[k], m);
+    diag_fold(p, o);
+  }
+}
+// the wave records through LDS, folded in wave order by thread 0 (which alone holds the result)
+__device__ inline void diag_block_fold(DiagPartial &p, DiagPartial *waves) {
+  diag_wave_fold(p);
+  if ((threadIdx.x & 63u) == 0) waves[threadIdx.x >> 6] = p;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (uint32_t w = 1; w < BLOCK / 64; ++w) diag_fold(p, waves[w]);
+  __syncthreads();  // (the next round overwrites `waves`)
+}
+
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_diag_partial(uint32_t n, const vec4<N> *__restrict__ pos4,
+                                                        const vec4<N> *__restrict__ vel4, const uint8_t *__restrict__ type,
+                                                        const N *__restrict__ rho, const uint32_t *__restrict__ nbr,
+                                                        DiagPartial *__restrict__ partials) {
+  __shared__ DiagPartial waves[BLOCK / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t waveBase = blockIdx.x * DIAG_TILE + wave * 64u * DIAG_ITEMS;
+  DiagPartial a;
+  diag_identity(a);
+#pragma unroll 1
+  for (int j = 0; j < DIAG_ITEMS; ++j) {
+    const uint32_t i = waveBase + j * 64u + lane;
+    if (i >= n) continue;
+    if (type[i] & TYPE_OBSTACLE) {
+      a.cnt[1] += 1ull;
+      continue;
+    }
+    const vec4<N> p = pos4[i], v = vel4[i];
+    const double x = double(p.x), y = double(p.y), z = double(p.z), m = double(p.w);
+    const double vx = double(v.x), vy = double(v.y), vz = double(v.z);
+    if (isfinite(x) && isfinite(y) && isfinite(z) && isfinite(vx) && isfinite(vy) && isfinite(vz)) {
+      const double v2 = vx * vx + vy * vy + vz * vz;
+      a.cnt[0] += 1ull;
+      a.sum[0] += m;
+      a.sum[1] += m * x, a.sum[2] += m * y, a.sum[3] += m * z;
+      a.sum[4] += m * vx, a.sum[5] += m * vy, a.sum[6] += m * vz;
+      a.sum[7] += m * v2;
+      a.hi[0] = fmax(a.hi[0], v2);
+      a.hi[1] = fmax(a.hi[1], x), a.hi[2] = fmax(a.hi[2], y), a.hi[3] = fmax(a.hi[3], z);
+      a.lo[0] = fmin(a.lo[0], x), a.lo[1] = fmin(a.lo[1], y), a.lo[2] = fmin(a.lo[2], z);
+    } else {
+      a.cnt[2] += 1ull;
+    }
+    if (rho) {  // the density part: every fluid particle the pass evaluated; C in N as LambdaOp::end forms it
+      const N r = rho[i];
+      const N C = r / N(RHO) - N(1);
+      const double rd = double(r), Cd = double(C);
+      const unsigned long long k = nbr[i];
+      a.cnt[3] += 1ull, a.cnt[4] += k;
+      a.cnt[5] = a.cnt[5] > k ? a.cnt[5] : k;
+      a.sum[8] += rd, a.sum[9] += fabs(Cd), a.sum[10] += fmax(Cd, 0.0);
+      a.hi[4] = fmax(a.hi[4], rd), a.hi[5] = fmax(a.hi[5], fabs(Cd));
+      a.lo[3] = fmin(a.lo[3], rd);
+    }
+  }
+  diag_block_fold(a, waves);
+  if (threadIdx.x == 0) partials[blockIdx.x] = a;
+}
+
+// the device's image of pbf_diag (include/pbf_hip.h; pbf_hip.hip asserts that the two agree) + the polled word
+struct DiagRecord {
+  unsigned long long n_fluid, n_obstacle, n_nonfinite;
+  double mass, moment[3], momentum[3], kinetic, max_speed, aabb_min[3], aabb_max[3];
+  unsigned long long n_density, nbr_max;
+  double rho_min, rho_max, rho_mean, err_mean, err_max, compression_mean, nbr_mean;
+  uint32_t seq;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_diag_final(uint32_t nb, const DiagPartial *__restrict__ partials,
+                                                      volatile DiagRecord *__restrict__ host, uint32_t seq) {
+  __shared__ DiagPartial waves[BLOCK / 64];
+  DiagPartial t;
+  diag_identity(t);
+  for (uint32_t base = 0; base < nb; base += BLOCK) {
+    const uint32_t i = base + threadIdx.x;
+    DiagPartial p;
+    if (i < nb) p = partials[i];
+    else diag_identity(p);
+    diag_block_fold(p, waves);
+    diag_fold(t, p);  // (thread 0's is the one that counts)
+  }
+  if (threadIdx.x != 0) return;
+  const bool any = t.cnt[0] != 0ull, dens = t.cnt[3] != 0ull;
+  host->n_fluid = t.cnt[0], host->n_obstacle = t.cnt[1], host->n_nonfinite = t.cnt[2];
+  host->mass = any ? t.sum[0] : 0.0;
+  for (int k = 0; k < 3; ++k) {
+    host->moment[k] = any ? t.sum[1 + k] : 0.0;
+    host->momentum[k] = any ? t.sum[4 + k] : 0.0;
+    host->aabb_min[k] = any ? t.lo[k] : 0.0;
+    host->aabb_max[k] = any ? t.hi[1 + k] : 0.0;
+  }
+  host->kinetic = any ? 0.5 * t.sum[7] : 0.0;
+  host->max_speed = any ? sqrt(t.hi[0]) : 0.0;
+  const double nd = double(t.cnt[3]);
+  host->n_density = t.cnt[3], host->nbr_max = dens ? t.cnt[5] : 0ull;
+  host->rho_min = dens ? t.lo[3] : 0.0, host->rho_max = dens ? t.hi[4] : 0.0;
+  host->rho_mean = dens ? t.sum[8] / nd : 0.0;
+  host->err_mean = dens ? t.sum[9] / nd : 0.0;
+  host->err_max = dens ? t.hi[5] : 0.0;
+  host->compression_mean = dens ? t.sum[10] / nd : 0.0;
+  host->nbr_mean = dens ? double(t.cnt[4]) / nd : 0.0;
+  __threadfence_system();
+  host->seq = seq;
+  __threadfence_system();
+}
+
 }  // namespace pbf

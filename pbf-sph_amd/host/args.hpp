@@ -36,6 +36,7 @@ struct Args {
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
   bool indexedMesh = false;               // --indexed-mesh: the frames' surface as an indexed mesh (one vertex per lattice edge)
+  size_t diagnostics = 0;                 // --diagnostics[=every]: with --resident, a JSON line of pbf_diagnostics every `every` frames
 
   struct SourceArg {
     std::array<double, 7> v;  // x, y, z, vx, vy, vz, rate
@@ -82,6 +83,9 @@ struct Args {
           "      --indexed-mesh                    Extract the surface as an indexed mesh (one vertex per crossed lattice\n"
           "                                        edge, watertight by index); mesh.obj becomes an indexed OBJ.\n"
           "                                        Single device only\n"
+          "      --diagnostics[=every]             With --resident: after every [every]-th timed frame (default 1) one JSON\n"
+          "                                        line {\"frame\":..,\"diag\":{..}} of the device-side diagnostics (sums,\n"
+          "                                        extrema, density residual); outside the timed interval. Single device only\n"
           "      --source=[x,y,z,vx,vy,vz,rate[,tag]]  An inlet (repeatable): a floor x ceil sheet of sqrt(rate) particles\n"
           "                                        per frame at the world point, with that velocity. With --resident\n"
           "                                        emitted on the GPU, otherwise by advance(). Single device only\n"
@@ -133,6 +137,11 @@ struct Args {
         else if (a == "--json") json = true;
         else if (a == "--all-devices") allDevices = true;
         else if (a == "--indexed-mesh") indexedMesh = true;
+        else if (a == "--diagnostics") diagnostics = 1;
+        else if (a.rfind("--diagnostics=", 0) == 0) {
+          diagnostics = std::stoull(a.substr(14));
+          if (diagnostics == 0) throw std::runtime_error("--diagnostics: every must be >= 1");
+        }
         else if (value(i, a, "", "--slabs", v)) slabs = std::stoull(v);
         else if (value(i, a, "", "--surface-tension", v)) {
           const size_t comma = v.find(',');

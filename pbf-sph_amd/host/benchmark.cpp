@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <filesystem>
 #include <fstream>
 #include <iomanip>
@@ -111,6 +112,11 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cerr << "--surface-tension is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
   }
+  if (args.diagnostics && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--diagnostics is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (args.diagnostics && !args.resident) std::cout << "--diagnostics takes effect with --resident: ignored" << std::endl;
   if (args.indexedMesh && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--indexed-mesh is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -161,6 +167,26 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       throw;
     }
   }
+  // --diagnostics: one JSON line per `every` timed frames; its time is kept out of the frame times and of the runtime
+  double diagMillis = 0;
+  auto report = [&](size_t frame) {
+    const auto d0 = hrc::now();
+    const auto d = solver.diagnostics(frameParam(frame), /*density=*/solver.count() != 0);
+    auto num = [](double x) {  // (JSON has no NaN / Infinity)
+      char buf[40];
+      std::snprintf(buf, sizeof buf, "%.17g", x);
+      return std::isfinite(x) ? std::string(buf) : std::string("null");
+    };
+    auto vec3 = [&](const double *v) { return "[" + num(v[0]) + "," + num(v[1]) + "," + num(v[2]) + "]"; };
+    std::cout << "{\"frame\":" << frame << ",\"diag\":{\"n_fluid\":" << d.fluid << ",\"n_obstacle\":" << d.obstacles
+              << ",\"n_nonfinite\":" << d.nonFinite << ",\"mass\":" << num(d.mass) << ",\"moment\":" << vec3(d.moment)
+              << ",\"momentum\":" << vec3(d.momentum) << ",\"kinetic\":" << num(d.kinetic) << ",\"max_speed\":" << num(d.maxSpeed)
+              << ",\"aabb_min\":" << vec3(d.aabbMin) << ",\"aabb_max\":" << vec3(d.aabbMax) << ",\"n_density\":" << d.densityParticles
+              << ",\"nbr_max\":" << d.nbrMax << ",\"rho_min\":" << num(d.rhoMin) << ",\"rho_max\":" << num(d.rhoMax)
+              << ",\"rho_mean\":" << num(d.rhoMean) << ",\"err_mean\":" << num(d.errMean) << ",\"err_max\":" << num(d.errMax)
+              << ",\"compression_mean\":" << num(d.compressionMean) << ",\"nbr_mean\":" << num(d.nbrMean) << "}}" << std::endl;
+    diagMillis += duration_millis(hrc::now() - d0).count();
+  };
   start = hrc::now();
   for (size_t frame = 0; frame < args.iterations; ++frame) {
     const auto f0 = hrc::now();
@@ -171,11 +197,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       throw;
     }
     frameTime.push_back(duration_millis(hrc::now() - f0).count());
+    if (args.resident && args.diagnostics && (frame + 1) % args.diagnostics == 0) report(frame);
   }
   end = hrc::now();
   if (args.resident) solver.download(particles);
 
-  const double seconds = duration_millis(end - start).count() / 1000.0;
+  const double seconds = (duration_millis(end - start).count() - diagMillis) / 1000.0;
   const size_t frames = args.iterations;
   const Stats st = frameTime.empty() ? Stats{0, 0, 0, 0} : summaryStats(frameTime);
   std::cout << "Benchmark completed after " << frames << " frames:\n"

@@ -187,6 +187,15 @@ template <typename N, template <size_t S, typename C = N> typename V> struct Ind
   std::vector<uint32_t> tris{};
 };
 
+// What Solver::diagnostics() returns: pbf_diag (include/pbf_hip.h) as a plain struct; the density fields are 0 unless asked for.
+struct Diagnostics {
+  uint64_t fluid = 0, obstacles = 0, nonFinite = 0;
+  double mass = 0, moment[3] = {0, 0, 0}, momentum[3] = {0, 0, 0}, kinetic = 0, maxSpeed = 0;
+  double aabbMin[3] = {0, 0, 0}, aabbMax[3] = {0, 0, 0};
+  uint64_t densityParticles = 0, nbrMax = 0;
+  double rhoMin = 0, rhoMax = 0, rhoMean = 0, errMean = 0, errMax = 0, compressionMean = 0, nbrMean = 0;
+};
+
 #ifdef PBF_SPH_HAS_VEC
 template <typename T, typename N, template <size_t, typename C = N> typename V = sph::vec>
 #else
@@ -570,6 +579,24 @@ public:
       mesh.cs.insert(mesh.cs.end(), c4, c4 + nv);
     }
     return mesh;
+  }
+
+  // Conserved sums, extrema and — `density` — the density residual of the resident state, computed and reduced on the device
+  // (pbf_diagnostics; the fields are pbf_diag's, include/pbf_hip.h).  The density part needs a step() first and the config
+  // of that step.  Single device: on several the library's own refusal is thrown.
+  Diagnostics diagnostics(const sph::SphParams<T, N, V> &config, bool density = false) {
+    const pbf_params p = params(config, sph::Scene<T, N, V>{});
+    pbf_diag d{};
+    check(pbf_diagnostics(ctx_, &p, density ? uint32_t(PBF_DIAG_DENSITY) : 0u, &d), "pbf_diagnostics");
+    Diagnostics o;
+    o.fluid = d.n_fluid, o.obstacles = d.n_obstacle, o.nonFinite = d.n_nonfinite;
+    o.mass = d.mass, o.kinetic = d.kinetic, o.maxSpeed = d.max_speed;
+    for (int k = 0; k < 3; ++k)
+      o.moment[k] = d.moment[k], o.momentum[k] = d.momentum[k], o.aabbMin[k] = d.aabb_min[k], o.aabbMax[k] = d.aabb_max[k];
+    o.densityParticles = d.n_density, o.nbrMax = d.nbr_max;
+    o.rhoMin = d.rho_min, o.rhoMax = d.rho_max, o.rhoMean = d.rho_mean;
+    o.errMean = d.err_mean, o.errMax = d.err_max, o.compressionMean = d.compression_mean, o.nbrMean = d.nbr_mean;
+    return o;
   }
 
   // The same surface as an indexed mesh: 40 V + 12 T bytes in fp32 instead of 120 T, watertight by index.  Single device (an
