@@ -206,7 +206,7 @@ enum pbf_buffer {
   PBF_BUF_TABLE = 1,  /* uint32[table_size] = the reference's gridTable (sph.hpp:238-250) */
   PBF_BUF_PSTAR = 2,  /* N[4n]: pStar.xyz, lambda */
   PBF_BUF_NBR_COUNT = 3, /* uint32[n]: neighbour list of each particle after the last list build: low 8 bits = length (<= 160),
-                            upper 24 bits = the pool chunk holding its slots 40..63 when the length exceeds 40 (two-tier
+                            upper 24 bits = the 120-slot pool chunk holding its slots 40..159 when the length exceeds 40 (two-tier
                             lists, csrc/pbf_kernels.hpp NbrLists); 0xFFFFFFFF = more than 160 survivors (or the chunk pool ran
                             dry): the particle walks its cells; diagnostic, list gather only */
   PBF_BUF_OMEGA = 4,  /* N[4n]: {omega.xyz, 0}, the vorticity estimate of the last step run with pbf_params.vorticity
@@ -261,6 +261,58 @@ typedef struct pbf_diag {
   double rho_min, rho_max, rho_mean, err_mean, err_max, compression_mean, nbr_mean;
 } pbf_diag;
 int pbf_diagnostics(pbf_ctx *ctx, const pbf_params *params, uint32_t what, pbf_diag *out);
+
+/* ---- sampling the SPH fields at arbitrary points and on a regular lattice (no reference counterpart) -----------
+ * "What is the fluid doing HERE": density, velocity and colour at a point that is not a particle — a gauge or probe at a
+ * fixed position, a density or velocity volume for rendering, slices or a grid code — without downloading the particles.
+ * One kernel, one lane per point, on the keys and table of the last step.  Its own call on the ctx stream, synchronising
+ * (plain copies and one hipStreamSynchronize, like pbf_query_cells); never part of a step or of a captured hipGraph, and
+ * a step after it runs exactly as it would have without.
+ *
+ * The outputs are RAW SUMS, not Shepard-normalised values: sums are what can be bounded, and what adds across slabs.
+ * v(x) = mv / weight and c(x) = mc / weight are the caller's division (the C++ shim and the Python binding offer it, with 0
+ * where weight == 0).
+ *
+ * Preconditions, those of the density part of pbf_diagnostics: a step has run and its table is still valid; params
+ * describe the last step's grid (bounds and scale, as in pbf_query_cells); not slab mode (a point near a cut needs both
+ * ranks' candidates) — PBF_ERR_STATE otherwise.
+ * PBF_ERR_INVALID: points, out or params NULL when n > 0; a non-finite point, origin or spacing; unknown bits in `what`;
+ * mv or mc non-NULL without its flag; n, or the product of dims, >= 2^31; a zero in dims.  On every error the output arrays
+ * are untouched.  n = 0 returns PBF_OK and launches nothing.
+ *
+ * The point: rounded to N (the ctx's float or double), then x_s = point / scale in N (solver frame).  Its cell is
+ * cell_coord((x_s - minExtent) / h) per axis — pbf_query_cells' expressions (truncation towards zero: a quotient in
+ * (-1, 0) is cell 0).  Unlike pbf_query_cells, which keeps the low 10 bits of whatever comes out, a quotient of 2^31 or
+ * more in magnitude is outside without being converted, and the coordinates are tested against the extent (below).  A lattice
+ * point is origin[a] + N(i_a) * spacing[a], origin and spacing rounded to N first, formed in N on the device as one multiply
+ * and one add (not contracted): pbf_sample_lattice returns bit for bit what pbf_sample_points returns on the same points
+ * formed that way by the caller.
+ * The grid test: the point is IN THE GRID iff every cell coordinate lies in [0, extent_a) of pbf_grid_extent and the cell's
+ * code + 1 < pbf_table_size.  Otherwise outside = 1 and every other field of its record is 0.
+ * The candidates: the particles of the 27 cells around that cell, by their PREDICT-TIME keys, evaluated at their FINAL pStar
+ * (the one PBF_BUF_PSTAR reads), with mass, velocity and colour as pbf_download would return them now — the frame the
+ * extras passes and PBF_DIAG_DENSITY use.  It follows that a particle which delta-p carried more than a cell away from its
+ * predict-time cell can be missed although it lies within h of the point, exactly as those passes miss it.
+ * The pair term is the density sum's, with the candidate's own mass:  r = |x_s - p_j| (IEEE sqrt; with
+ * PBF_FLAG_FAST_MATH the pair kernels' v_rsq form),  in = r <= h,  w = m_j * (poly6Factor * (d * d * d)),  d = h * h - r * r.
+ * An excluded candidate's term is SELECTED to +0, never multiplied by 0.  Obstacles count in rho and count[1] only.
+ * Summation: one accumulator set per point, in N, in the walk's order (27 cells x fastest, then y, then z; within a cell
+ * the sorted order).  The record of a point therefore does not depend on which other points are in the call, on their order
+ * or on n. */
+enum { PBF_SAMPLE_VELOCITY = 1u << 0, PBF_SAMPLE_COLOUR = 1u << 1 };
+typedef struct pbf_sample_out {   /* caller-owned host arrays of N (float / double as the ctx); any may be NULL */
+  void *rho;       /* N[n]   sum over ALL candidates j with r <= h of  m_j W_poly6(r)   (solver frame; compare with rho0 = 6378) */
+  void *weight;    /* N[n]   the same sum over FLUID candidates only */
+  void *mv;        /* N[3n]  sum over fluid candidates of (m_j W) v_j   — needs PBF_SAMPLE_VELOCITY */
+  void *mc;        /* N[4n]  sum over fluid candidates of (m_j W) c_j   — needs PBF_SAMPLE_COLOUR */
+  uint32_t *count; /* uint32[2n]  {fluid, obstacle} candidates with r <= h */
+  uint8_t *outside;/* uint8[n]    1 = the point's cell is not a cell of the last step's grid: its record is all zeros */
+} pbf_sample_out;
+int pbf_sample_points(pbf_ctx *ctx, const pbf_params *params, size_t n, const double *points /* 3n, world */, uint32_t what,
+                      const pbf_sample_out *out);
+/* point (i, j, k) of the lattice has index (i * dims[1] + j) * dims[2] + k */
+int pbf_sample_lattice(pbf_ctx *ctx, const pbf_params *params, const double origin[3], const double spacing[3],
+                       const uint64_t dims[3], uint32_t what, const pbf_sample_out *out);
 
 /* Device self-test of the trimmed exact sqrt / divides the precise pair terms use (csrc/pbf_kernels.hpp sqrt_rsq /
  * div_seeded / div_ranged) against the compiler's full IEEE forms, exhaustively: mismatches[0] sqrt over EVERY fp32 value

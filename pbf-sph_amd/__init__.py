@@ -20,6 +20,9 @@ from .capi import (  # noqa: F401
     McParams,
     Params,
     PbfError,
+    SAMPLE_COLOUR,
+    SAMPLE_VELOCITY,
+    SampleOut,
     SlabCut,
     Solver,
     apply_motion,

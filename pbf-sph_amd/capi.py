@@ -20,6 +20,7 @@ BUF_OMEGA = 4
 BUF_SURFACE = 5
 BUF_DENSITY = 6
 DIAG_DENSITY = 1 << 0
+SAMPLE_VELOCITY, SAMPLE_COLOUR = 1 << 0, 1 << 1
 
 
 class PbfError(RuntimeError):
@@ -114,6 +115,12 @@ class Diag(C.Structure):
         return out
 
 
+class SampleOut(C.Structure):
+    """pbf_sample_out (include/pbf_hip.h): six caller-owned host arrays, any may be NULL"""
+    _fields_ = [("rho", C.c_void_p), ("weight", C.c_void_p), ("mv", C.c_void_p), ("mc", C.c_void_p),
+                ("count", C.c_void_p), ("outside", C.c_void_p)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -160,6 +167,9 @@ _SIGS = {
     "pbf_scene_host_syncs": (C.c_uint64, [C.c_void_p]),
     "pbf_query_cells": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pbf_diagnostics": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_uint32, C.POINTER(Diag)]),
+    "pbf_sample_points": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_uint32, C.POINTER(SampleOut)]),
+    "pbf_sample_lattice": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.POINTER(SampleOut)]),
     "pbf_read_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "pbf_table_size": (C.c_size_t, [C.c_void_p]),
     "pbf_selftest_math": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -401,6 +411,45 @@ class Solver:
                   "pbf_query_cells")
         self.last_query_counts = counts
         return [ids[i, :min(int(counts[i]), cap)].copy() for i in range(len(pts))]
+
+    def _sample_arrays(self, n, velocity, colour):
+        a = dict(rho=np.zeros(n, self.dtype), weight=np.zeros(n, self.dtype), count=np.zeros((n, 2), np.uint32),
+                 outside=np.zeros(n, np.uint8))
+        if velocity:
+            a["mv"] = np.zeros((n, 3), self.dtype)
+        if colour:
+            a["mc"] = np.zeros((n, 4), self.dtype)
+        out = SampleOut(_vp(a["rho"]), _vp(a["weight"]), _vp(a.get("mv")), _vp(a.get("mc")), _vp(a["count"]), _vp(a["outside"]))
+        return a, out, (SAMPLE_VELOCITY if velocity else 0) | (SAMPLE_COLOUR if colour else 0)
+
+    @staticmethod
+    def _sample_normalised(a):
+        # the caller's division (include/pbf_hip.h): mv / weight, mc / weight, 0 where weight == 0
+        w = a["weight"][:, None]
+        safe = np.where(w == 0, 1, w)
+        for raw, name in (("mv", "velocity"), ("mc", "colour")):
+            if raw in a:
+                a[name] = np.where(w == 0, 0, a[raw] / safe).astype(a[raw].dtype)
+        return a
+
+    def sample(self, p, points, velocity=False, colour=False):
+        """The SPH sums at world points (pbf_sample_points, include/pbf_hip.h) -> dict of numpy arrays: the raw sums rho,
+        weight, mv (n,3), mc (n,4), count (n,2) {fluid, obstacle}, outside, plus velocity = mv / weight and colour =
+        mc / weight (0 where weight == 0) when asked for."""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        a, out, what = self._sample_arrays(len(pts), velocity, colour)
+        self._chk(self.L.pbf_sample_points(self.ctx, C.byref(p), len(pts), _vp(pts), what, C.byref(out)), "pbf_sample_points")
+        return self._sample_normalised(a)
+
+    def sample_lattice(self, p, origin, spacing, dims, velocity=False, colour=False):
+        """The same sums on the lattice origin + (i, j, k) * spacing, i < dims[0] ... (pbf_sample_lattice); point (i, j, k)
+        has index (i * dims[1] + j) * dims[2] + k."""
+        o, sp = np.ascontiguousarray(origin, np.float64).reshape(3), np.ascontiguousarray(spacing, np.float64).reshape(3)
+        d = np.ascontiguousarray(dims, np.uint64).reshape(3)
+        n = int(d[0]) * int(d[1]) * int(d[2])
+        a, out, what = self._sample_arrays(n if n < 2 ** 31 else 0, velocity, colour)
+        self._chk(self.L.pbf_sample_lattice(self.ctx, C.byref(p), _vp(o), _vp(sp), _vp(d), what, C.byref(out)), "pbf_sample_lattice")
+        return self._sample_normalised(a)
 
     def sync(self):
         self._chk(self.L.pbf_sync(self.ctx), "pbf_sync")

@@ -155,6 +155,9 @@ struct pbf_ctx {
   uint32_t sceneSeq = 0;
   uint64_t sceneHostSyncs = 0;
   DevBuf queryPoints, queryCounts, queryIds;  // pbf_query_cells
+  // pbf_sample_points / pbf_sample_lattice: the uploaded points in N, and one allocation holding the call's SoA outputs
+  // {rho, weight, mv, mc, count, outside}.  Scratch of an observer: no step reads either.
+  DevBuf samplePoints, sampleOut;
   // pbf_diagnostics: the density pass's own outputs (N[cap] rho, uint32[cap] neighbour counts; allocated with the first
   // density request), one partial record per DIAG_TILE particles, the pinned record the last kernel writes and the host
   // polls.  diagDensityValid: diagRho holds the pass of the CURRENT sorted set (PBF_BUF_DENSITY) — set by the pass, dropped by
@@ -1376,7 +1379,7 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->mcEdgeWord, &ctx->mcEdgeOffsets, &ctx->mcEdgeSums, &ctx->meshT, &ctx->meshV, &ctx->meshN,
                    &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB,
                    &ctx->sceneSources, &ctx->sceneDrains, &ctx->drainCounts, &ctx->queryPoints, &ctx->queryCounts,
-                   &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials};
+                   &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials, &ctx->samplePoints, &ctx->sampleOut};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
@@ -1851,6 +1854,101 @@ int query_impl(pbf_ctx *ctx, const pbf_params *p, size_t np, const double *point
       std::memcpy(ids + q * cap, rows.data() + q * cap, std::min<size_t>(counts[q], cap) * 8);
   return PBF_OK;
 }
+
+// pbf_sample_points / pbf_sample_lattice: one k_sample launch over the final pStar on the last step's keys and table.  Like
+// pbf_diagnostics it touches nothing a step reads (materialise_pstar apart) and is never captured.  `points` == nullptr: the
+// lattice source.  The answers travel with plain async copies straight into the caller's arrays, only those it asked for.
+struct SampleLatticeDesc {
+  double origin[3], spacing[3];
+  uint64_t dims[3];
+};
+template <typename N, bool FAST, typename Source>
+int launch_sample(pbf_ctx *ctx, const StepConsts<N> &c, const Source &src, uint64_t threads, uint32_t what,
+                  const SampleOut<N> &out) {
+  const int s = ctx->st.cur;
+  const dim3 grid(unsigned((threads + BLOCK - 1) / BLOCK));
+  const SampleExtent ext{{uint32_t(ctx->extent[0]), uint32_t(ctx->extent[1]), uint32_t(ctx->extent[2])}};
+#define PBF_SAMPLE_LAUNCH(W)                                                                                              \
+  hipLaunchKernelGGL((k_sample<N, FAST, W, Source>), grid, dim3(BLOCK), 0, ctx->stream, c, src, ext,                      \
+                     ctx->table.as<const uint32_t>(), ctx->pstar[ctx->st.pcur].as<const vec4<N>>(),                       \
+                     ctx->pos4[s].as<const vec4<N>>(), ctx->vel4[s].as<const vec4<N>>(), ctx->col4[s].as<const vec4<N>>(), \
+                     ctx->type[s].as<const uint8_t>(), out)
+  switch (what) {
+    case 0: PBF_SAMPLE_LAUNCH(0u); break;
+    case SAMPLE_VELOCITY: PBF_SAMPLE_LAUNCH(SAMPLE_VELOCITY); break;
+    case SAMPLE_COLOUR: PBF_SAMPLE_LAUNCH(SAMPLE_COLOUR); break;
+    default: PBF_SAMPLE_LAUNCH(SAMPLE_VELOCITY | SAMPLE_COLOUR); break;
+  }
+#undef PBF_SAMPLE_LAUNCH
+  LAUNCH_CHECK(ctx);
+  return PBF_OK;
+}
+template <typename N>
+int sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, const SampleLatticeDesc *lat, uint32_t what,
+                const pbf_sample_out *o, const char *who) {
+  StepConsts<N> c;
+  if (int rc = consts_on_last_grid<N>(ctx, p, c, who)) return rc;
+  // the outputs' places in the one allocation, each 256-byte aligned
+  size_t at = 0;
+  auto place = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  const size_t oRho = place(n * sizeof(N)), oWeight = place(n * sizeof(N)), oMv = place(3 * n * sizeof(N)),
+               oMc = place(4 * n * sizeof(N)), oCount = place(2 * n * 4), oOutside = place(n);
+  if (int rc = ensure(ctx, ctx->sampleOut, at)) return rc;
+  std::vector<N> pts;
+  if (points) {
+    pts.resize(3 * n);
+    for (size_t k = 0; k < 3 * n; ++k) pts[k] = N(points[k]);
+    if (int rc = ensure(ctx, ctx->samplePoints, pts.size() * sizeof(N))) return rc;
+  }
+  if (int rc = join_diffuse(ctx)) return rc;
+  if (int rc = materialise_pstar<N>(ctx)) return rc;
+  char *base = ctx->sampleOut.as<char>();
+  const SampleOut<N> out{reinterpret_cast<N *>(base + oRho),        reinterpret_cast<N *>(base + oWeight),
+                         reinterpret_cast<N *>(base + oMv),         reinterpret_cast<N *>(base + oMc),
+                         reinterpret_cast<uint32_t *>(base + oCount), reinterpret_cast<uint8_t *>(base + oOutside)};
+  int rc;
+  if (points) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->samplePoints.p, pts.data(), pts.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
+    const SamplePointSource<N> src{ctx->samplePoints.as<const N>(), uint32_t(n)};
+    rc = ctx->fast ? launch_sample<N, true>(ctx, c, src, n, what, out) : launch_sample<N, false>(ctx, c, src, n, what, out);
+  } else {
+    SampleLatticeSource<N> src;
+    for (int a = 0; a < 3; ++a) src.origin[a] = N(lat->origin[a]), src.spacing[a] = N(lat->spacing[a]), src.dims[a] = uint32_t(lat->dims[a]);
+    src.by = (src.dims[1] + 3u) / 4u, src.bz = (src.dims[2] + 3u) / 4u;
+    const uint64_t waves = uint64_t((src.dims[0] + 3u) / 4u) * src.by * src.bz;  // (at most 2^29: dims' product is below 2^31)
+    rc = ctx->fast ? launch_sample<N, true>(ctx, c, src, waves * 64u, what, out)
+                   : launch_sample<N, false>(ctx, c, src, waves * 64u, what, out);
+  }
+  if (rc != PBF_OK) return rc;
+  auto back = [&](void *host, size_t off, size_t bytes) {
+    return host ? hipMemcpyAsync(host, base + off, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  };
+  HIPCHK(ctx, back(o->rho, oRho, n * sizeof(N)));
+  HIPCHK(ctx, back(o->weight, oWeight, n * sizeof(N)));
+  HIPCHK(ctx, back(o->mv, oMv, 3 * n * sizeof(N)));
+  HIPCHK(ctx, back(o->mc, oMc, 4 * n * sizeof(N)));
+  HIPCHK(ctx, back(o->count, oCount, 2 * n * 4));
+  HIPCHK(ctx, back(o->outside, oOutside, n));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pts is a temporary; the caller reads the answers)
+  return PBF_OK;
+}
+// what both entry points refuse, in the header's order: arguments first (PBF_ERR_INVALID), then the state (PBF_ERR_STATE)
+int sample_check(pbf_ctx *ctx, const pbf_params *p, uint32_t what, const pbf_sample_out *o, const char *who) {
+  const std::string w(who);
+  if (!p || !o) return fail(ctx, PBF_ERR_INVALID, w + ": NULL argument");
+  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  if (o->mv && !(what & PBF_SAMPLE_VELOCITY)) return fail(ctx, PBF_ERR_INVALID, w + ": mv needs PBF_SAMPLE_VELOCITY");
+  if (o->mc && !(what & PBF_SAMPLE_COLOUR)) return fail(ctx, PBF_ERR_INVALID, w + ": mc needs PBF_SAMPLE_COLOUR");
+  // a point near a cut needs both ranks' candidates
+  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
+    return fail(ctx, PBF_ERR_STATE, w + " is not supported in slab mode");
+  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, w + " needs a step first (no valid cell table)");
+  return PBF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1918,6 +2016,39 @@ int pbf_diagnostics(pbf_ctx *ctx, const pbf_params *p, uint32_t what, pbf_diag *
     return fail(ctx, PBF_ERR_STATE, "pbf_diagnostics: the density part needs a step first (no valid cell table)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return DISPATCH(ctx, diagnostics_impl, ctx, p, density, out);
+}
+
+int pbf_sample_points(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, uint32_t what, const pbf_sample_out *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (what & ~uint32_t(PBF_SAMPLE_VELOCITY | PBF_SAMPLE_COLOUR)) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_points: unknown bits in `what`");
+  if (n >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_points: 2^31 points or more");
+  if (n == 0) return PBF_OK;
+  if (!points) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_points: NULL argument");
+  for (size_t k = 0; k < 3 * n; ++k)
+    if (!std::isfinite(points[k])) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_points: points must be finite");
+  if (int rc = sample_check(ctx, p, what, out, "pbf_sample_points")) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return DISPATCH(ctx, sample_impl, ctx, p, n, points, nullptr, what, out, "pbf_sample_points");
+}
+
+int pbf_sample_lattice(pbf_ctx *ctx, const pbf_params *p, const double origin[3], const double spacing[3], const uint64_t dims[3],
+                       uint32_t what, const pbf_sample_out *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (what & ~uint32_t(PBF_SAMPLE_VELOCITY | PBF_SAMPLE_COLOUR)) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_lattice: unknown bits in `what`");
+  if (!origin || !spacing || !dims) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_lattice: NULL argument");
+  SampleLatticeDesc lat;
+  uint64_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(origin[a]) || !std::isfinite(spacing[a]))
+      return fail(ctx, PBF_ERR_INVALID, "pbf_sample_lattice: origin and spacing must be finite");
+    if (dims[a] == 0) return fail(ctx, PBF_ERR_INVALID, "pbf_sample_lattice: a zero in dims");
+    if (dims[a] >= (uint64_t(1) << 31) || (n *= dims[a]) >= (uint64_t(1) << 31))
+      return fail(ctx, PBF_ERR_INVALID, "pbf_sample_lattice: 2^31 points or more");
+    lat.origin[a] = origin[a], lat.spacing[a] = spacing[a], lat.dims[a] = dims[a];
+  }
+  if (int rc = sample_check(ctx, p, what, out, "pbf_sample_lattice")) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return DISPATCH(ctx, sample_impl, ctx, p, size_t(n), nullptr, &lat, what, out, "pbf_sample_lattice");
 }
 
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {

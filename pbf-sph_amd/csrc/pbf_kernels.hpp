@@ -2788,6 +2788,113 @@ __global__ __launch_bounds__(64) void k_query_cells(StepConsts<N> c, const N *__
 }
 
 // ------------------------------------------------------------------------------------------------
+// pbf_sample_points / pbf_sample_lattice: the SPH sums at a point that is no particle.  No reference counterpart.
+//
+// k_sample: one lane per point.  The point's cell with k_query_cells' expressions, the 27-cell walk of for_each_candidate
+// from that cell's code, DensityOp's pair term with the CANDIDATE's mass; one accumulator set per lane, in N, in walk order
+// — a point's record depends on nothing but the point and the state.  `Source` says which point a lane owns (and nothing
+// else: the two sources run the same body, so the same point gives the same bits through either).  WHAT is compile time:
+// a variant loads per candidate only what its sums need — {pStar} for the filter, then {mass, type} of the survivors,
+// vel4 / col4 of the survivors under their flags.  Outputs are SoA, indexed by the point's index.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t SAMPLE_VELOCITY = 1u << 0, SAMPLE_COLOUR = 1u << 1;  // = PBF_SAMPLE_* (include/pbf_hip.h)
+template <typename N> struct SampleOut {
+  N *rho, *weight, *mv, *mc;  // N[n], N[n], N[3n], N[4n]
+  uint32_t *count;            // uint32[2n]
+  uint8_t *outside;           // uint8[n]
+};
+// lane t owns point t of the uploaded array (3 N per point, world): consecutive lanes load and store consecutive elements
+template <typename N> struct SamplePointSource {
+  const N *pts;
+  uint32_t n;
+  __device__ bool point(uint32_t &q, N &x, N &y, N &z) const {
+    q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= n) return false;
+    const size_t at = 3 * size_t(q);  // (3 q passes 2^32 from q = 1.43e9 on)
+    x = pts[at], y = pts[at + 1], z = pts[at + 2];
+    return true;
+  }
+};
+// A wave owns a 4 x 4 x 4 block of lattice points (blocks in k-fastest order, lanes k-fastest inside one): its lanes share
+// their home cells and most of their candidates' cache lines, where 64 consecutive k would string a wave along a line
+// (a gather costs by the lines it touches: tools/gather_rate.hip).  The point is origin + N(i) * spacing per axis, one
+// multiply and one add (-ffp-contract=off keeps them apart).  Which lane owns a point never enters its sums.
+template <typename N> struct SampleLatticeSource {
+  N origin[3], spacing[3];
+  uint32_t dims[3];
+  uint32_t by, bz;  // blocks along j and k: (dims + 3) / 4
+  __device__ bool point(uint32_t &q, N &x, N &y, N &z) const {
+    const uint64_t t = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint64_t w = t >> 6;
+    const uint32_t lane = uint32_t(t) & 63u;
+    const uint64_t bi = w / (uint64_t(by) * bz);
+    const uint32_t rest = uint32_t(w - bi * (uint64_t(by) * bz));
+    const uint64_t i = 4u * bi + (lane >> 4);
+    const uint32_t j = 4u * (rest / bz) + ((lane >> 2) & 3u), k = 4u * (rest % bz) + (lane & 3u);
+    if (i >= dims[0] || j >= dims[1] || k >= dims[2]) return false;
+    q = (uint32_t(i) * dims[1] + j) * dims[2] + k;  // (the product of dims is below 2^31)
+    x = origin[0] + N(uint32_t(i)) * spacing[0], y = origin[1] + N(j) * spacing[1], z = origin[2] + N(k) * spacing[2];
+    return true;
+  }
+};
+struct SampleExtent {
+  uint32_t e[3];  // pbf_grid_extent of the last step
+};
+
+template <typename N, bool FAST, uint32_t WHAT, typename Source>
+__global__ __launch_bounds__(BLOCK) void k_sample(StepConsts<N> c, Source src, SampleExtent ext,
+                                                  const uint32_t *__restrict__ table,
+                                                  const vec4<N> *__restrict__ pstar, const vec4<N> *__restrict__ pos4,
+                                                  const vec4<N> *__restrict__ vel4, const vec4<N> *__restrict__ col4,
+                                                  const uint8_t *__restrict__ type, SampleOut<N> out) {
+  uint32_t q;
+  N px, py, pz;
+  if (!src.point(q, px, py, pz)) return;
+  const vec4<N> xs = make_vec4<N>(px / c.scale, py / c.scale, pz / c.scale, N(0));
+  // (k_query_cells' expressions; a quotient no int64 holds is outside whatever the conversion would make of it)
+  auto cell = [](N v) { return fabs(v) < N(2147483648.0) ? cell_coord(v) : int64_t(-1); };
+  const int64_t cx = cell((xs.x - c.minExtent[0]) / c.h), cy = cell((xs.y - c.minExtent[1]) / c.h),
+                cz = cell((xs.z - c.minExtent[2]) / c.h);
+  bool inside = cx >= 0 && cx < int64_t(ext.e[0]) && cy >= 0 && cy < int64_t(ext.e[1]) && cz >= 0 && cz < int64_t(ext.e[2]);
+  const uint32_t code = inside ? morton_encode(uint32_t(cx), uint32_t(cy), uint32_t(cz)) : 0u;
+  inside = inside && uint64_t(code) + 1u < uint64_t(c.tableN);
+  N rho = N(0), weight = N(0);
+  N mvx = N(0), mvy = N(0), mvz = N(0);
+  N mcx = N(0), mcy = N(0), mcz = N(0), mcw = N(0);
+  uint32_t nFluid = 0, nObstacle = 0;
+  if (inside)
+    for_each_candidate(code, table, c.tableN, [&](uint32_t b) {
+      const vec4<N> pb = pstar[b];
+      if (!maybe_within_h<N>(xs, pb, c.h2filter)) return;  // (contributes exactly +0 to every sum, counts nothing)
+      const N m = pos4[b].w;
+      const bool fluid = type[b] == 0;
+      const auto g = pair_geom<N, FAST>(xs, pb, c.h);
+      const bool in = g.inH, inFluid = g.inH && fluid;
+      const N d = (c.h * c.h) - g.r * g.r;
+      const N w = m * (c.poly6Factor * (d * d * d));
+      rho += in ? w : N(0);
+      weight += inFluid ? w : N(0);
+      nFluid += inFluid ? 1u : 0u, nObstacle += (in && !fluid) ? 1u : 0u;
+      if constexpr ((WHAT & SAMPLE_VELOCITY) != 0) {
+        const vec4<N> v = vel4[b];
+        mvx += inFluid ? w * v.x : N(0), mvy += inFluid ? w * v.y : N(0), mvz += inFluid ? w * v.z : N(0);
+      }
+      if constexpr ((WHAT & SAMPLE_COLOUR) != 0) {
+        const vec4<N> col = col4[b];
+        mcx += inFluid ? w * col.x : N(0), mcy += inFluid ? w * col.y : N(0);
+        mcz += inFluid ? w * col.z : N(0), mcw += inFluid ? w * col.w : N(0);
+      }
+    });
+  const size_t at = q;  // (the strided indices in 64 bits: q goes up to 2^31 - 1, 4 q would wrap from 2^30 on)
+  out.rho[at] = rho, out.weight[at] = weight;
+  out.count[2 * at] = nFluid, out.count[2 * at + 1] = nObstacle;
+  out.outside[at] = inside ? uint8_t(0) : uint8_t(1);
+  if constexpr ((WHAT & SAMPLE_VELOCITY) != 0) out.mv[3 * at] = mvx, out.mv[3 * at + 1] = mvy, out.mv[3 * at + 2] = mvz;
+  if constexpr ((WHAT & SAMPLE_COLOUR) != 0)
+    out.mc[4 * at] = mcx, out.mc[4 * at + 1] = mcy, out.mc[4 * at + 2] = mcz, out.mc[4 * at + 3] = mcw;
+}
+
+// ------------------------------------------------------------------------------------------------
 // pbf_diagnostics: what the state is, told on the device.  No reference counterpart.
 //
 // DensityOp: LambdaOp's density sum on its own — rho_i = m_i sum_{j in N(i) u {i}} W_poly6(r), the very expressions

@@ -38,6 +38,9 @@ struct Args {
   bool indexedMesh = false;               // --indexed-mesh: the frames' surface as an indexed mesh (one vertex per lattice edge)
   size_t diagnostics = 0;                 // --diagnostics[=every]: with --resident, a JSON line of pbf_diagnostics every `every` frames
 
+  std::vector<std::array<double, 3>> probes;  // --probe=x,y,z (repeatable): with --resident, the SPH sums at that world point
+  size_t probeEvery = 0;                  // --probe-every=k: a report every k timed frames (0 = once, after the last one)
+
   struct SourceArg {
     std::array<double, 7> v;  // x, y, z, vx, vy, vz, rate
     unsigned long long tag;
@@ -86,6 +89,11 @@ struct Args {
           "      --diagnostics[=every]             With --resident: after every [every]-th timed frame (default 1) one JSON\n"
           "                                        line {\"frame\":..,\"diag\":{..}} of the device-side diagnostics (sums,\n"
           "                                        extrema, density residual); outside the timed interval. Single device only\n"
+          "      --probe=[x,y,z]                   With --resident (repeatable): density, velocity and colour sampled at the\n"
+          "                                        world point on the device; one JSON line {\"frame\":..,\"probes\":[..]} per\n"
+          "                                        report, outside the timed interval. Single device only\n"
+          "      --probe-every=[k]                 Report the probes after every k-th timed frame.\n"
+          "                                        Default: once, after the last timed frame\n"
           "      --source=[x,y,z,vx,vy,vz,rate[,tag]]  An inlet (repeatable): a floor x ceil sheet of sqrt(rate) particles\n"
           "                                        per frame at the world point, with that velocity. With --resident\n"
           "                                        emitted on the GPU, otherwise by advance(). Single device only\n"
@@ -143,6 +151,15 @@ struct Args {
           if (diagnostics == 0) throw std::runtime_error("--diagnostics: every must be >= 1");
         }
         else if (value(i, a, "", "--slabs", v)) slabs = std::stoull(v);
+        else if (value(i, a, "", "--probe-every", v)) {
+          probeEvery = std::stoull(v);
+          if (probeEvery == 0) throw std::runtime_error("--probe-every: k must be >= 1");
+        }
+        else if (value(i, a, "", "--probe", v)) {
+          const auto f = numbers(v);
+          if (f.size() != 3) throw std::runtime_error("--probe: expected x,y,z");
+          probes.push_back({f[0], f[1], f[2]});
+        }
         else if (value(i, a, "", "--surface-tension", v)) {
           const size_t comma = v.find(',');
           cohesion = std::stod(v.substr(0, comma));

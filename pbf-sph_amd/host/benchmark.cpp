@@ -117,6 +117,11 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   if (args.diagnostics && !args.resident) std::cout << "--diagnostics takes effect with --resident: ignored" << std::endl;
+  if (!args.probes.empty() && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--probe is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (!args.probes.empty() && !args.resident) std::cout << "--probe takes effect with --resident: ignored" << std::endl;
   if (args.indexedMesh && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--indexed-mesh is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -187,6 +192,30 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
               << ",\"compression_mean\":" << num(d.compressionMean) << ",\"nbr_mean\":" << num(d.nbrMean) << "}}" << std::endl;
     diagMillis += duration_millis(hrc::now() - d0).count();
   };
+  // --probe: one JSON line per report with the sums at every probe; its time is kept out like the diagnostics'
+  auto probe = [&](size_t frame) {
+    const auto d0 = hrc::now();
+    std::vector<sph::vec<3, N>> pts;
+    for (const auto &q : args.probes) pts.emplace_back(q[0], q[1], q[2]);
+    const auto s = solver.sample(frameParam(frame), pts, PBF_SAMPLE_VELOCITY | PBF_SAMPLE_COLOUR);
+    auto num = [](double x) {
+      char buf[40];
+      std::snprintf(buf, sizeof buf, "%.17g", x);
+      return std::isfinite(x) ? std::string(buf) : std::string("null");
+    };
+    std::cout << "{\"frame\":" << frame << ",\"probes\":[";
+    for (size_t i = 0; i < pts.size(); ++i) {
+      const auto &q = args.probes[i];
+      std::cout << (i ? "," : "") << "{\"at\":[" << num(q[0]) << "," << num(q[1]) << "," << num(q[2]) << "],\"rho\":" << num(s.rho[i])
+                << ",\"weight\":" << num(s.weight[i]) << ",\"velocity\":[" << num(s.velocity[3 * i]) << "," << num(s.velocity[3 * i + 1])
+                << "," << num(s.velocity[3 * i + 2]) << "],\"colour\":[" << num(s.colour[4 * i]) << "," << num(s.colour[4 * i + 1]) << ","
+                << num(s.colour[4 * i + 2]) << "," << num(s.colour[4 * i + 3]) << "],\"count\":[" << s.count[2 * i] << ","
+                << s.count[2 * i + 1] << "],\"outside\":" << int(s.outside[i]) << "}";
+    }
+    std::cout << "]}" << std::endl;
+    diagMillis += duration_millis(hrc::now() - d0).count();
+  };
+  const bool probing = args.resident && !args.probes.empty();
   start = hrc::now();
   for (size_t frame = 0; frame < args.iterations; ++frame) {
     const auto f0 = hrc::now();
@@ -198,6 +227,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     }
     frameTime.push_back(duration_millis(hrc::now() - f0).count());
     if (args.resident && args.diagnostics && (frame + 1) % args.diagnostics == 0) report(frame);
+    if (probing && (args.probeEvery ? (frame + 1) % args.probeEvery == 0 : frame + 1 == args.iterations)) probe(frame);
   }
   end = hrc::now();
   if (args.resident) solver.download(particles);

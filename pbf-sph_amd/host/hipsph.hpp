@@ -23,6 +23,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -187,6 +188,15 @@ template <typename N, template <size_t S, typename C = N> typename V> struct Ind
   std::vector<uint32_t> tris{};
 };
 
+// What Solver::sample() / sampleLattice() return: the raw sums of pbf_sample_out (include/pbf_hip.h), one entry per point —
+// mv 3 and mc 4 values per point, filled when asked for, count {fluid, obstacle} per point — plus the caller's division:
+// velocity = mv / weight and colour = mc / weight, 0 where weight == 0.
+template <typename N> struct Samples {
+  std::vector<N> rho{}, weight{}, mv{}, mc{}, velocity{}, colour{};
+  std::vector<uint32_t> count{};
+  std::vector<uint8_t> outside{};
+};
+
 // What Solver::diagnostics() returns: pbf_diag (include/pbf_hip.h) as a plain struct; the density fields are 0 unless asked for.
 struct Diagnostics {
   uint64_t fluid = 0, obstacles = 0, nonFinite = 0;
@@ -287,6 +297,25 @@ class Solver final : public sph::Solver<T, N, V> {
     p.n_wells = int32_t(scene.wells.size());
     p.wells = wells_.empty() ? nullptr : wells_.data();
     return p;
+  }
+
+  // Solver::sample / sampleLattice: the output arrays sized for n points and handed to the C ABI; then the stated division
+  static pbf_sample_out sampleArrays(Samples<N> &o, size_t n, uint32_t what) {
+    o.rho.assign(n, N(0)), o.weight.assign(n, N(0)), o.count.assign(2 * n, 0u), o.outside.assign(n, uint8_t(0));
+    if (what & PBF_SAMPLE_VELOCITY) o.mv.assign(3 * n, N(0));
+    if (what & PBF_SAMPLE_COLOUR) o.mc.assign(4 * n, N(0));
+    return {o.rho.data(), o.weight.data(), o.mv.empty() ? nullptr : o.mv.data(), o.mc.empty() ? nullptr : o.mc.data(),
+            o.count.data(), o.outside.data()};
+  }
+  static void normalise(Samples<N> &o, uint32_t what) {
+    const size_t n = o.weight.size();
+    if (what & PBF_SAMPLE_VELOCITY) o.velocity.assign(3 * n, N(0));
+    if (what & PBF_SAMPLE_COLOUR) o.colour.assign(4 * n, N(0));
+    for (size_t i = 0; i < n; ++i) {
+      if (o.weight[i] == N(0)) continue;
+      for (size_t a = 0; a < 3 && !o.velocity.empty(); ++a) o.velocity[3 * i + a] = o.mv[3 * i + a] / o.weight[i];
+      for (size_t a = 0; a < 4 && !o.colour.empty(); ++a) o.colour[4 * i + a] = o.mc[4 * i + a] / o.weight[i];
+    }
   }
 
 public:
@@ -596,6 +625,32 @@ public:
     o.densityParticles = d.n_density, o.nbrMax = d.nbr_max;
     o.rhoMin = d.rho_min, o.rhoMax = d.rho_max, o.rhoMean = d.rho_mean;
     o.errMean = d.err_mean, o.errMax = d.err_max, o.compressionMean = d.compression_mean, o.nbrMean = d.nbr_mean;
+    return o;
+  }
+
+  // The SPH sums at world points / on the lattice origin + (i, j, k) * spacing (pbf_sample_points / pbf_sample_lattice,
+  // include/pbf_hip.h): `what` = PBF_SAMPLE_VELOCITY | PBF_SAMPLE_COLOUR.  Needs a step() first and the config of that step.
+  // No numerics here beyond the stated division.  Single device: on several the library's own refusal is thrown.
+  Samples<N> sample(const sph::SphParams<T, N, V> &config, const std::vector<V<3>> &points, uint32_t what = 0) {
+    std::vector<double> pts(3 * points.size());
+    for (size_t i = 0; i < points.size(); ++i) pts[3 * i] = points[i].x, pts[3 * i + 1] = points[i].y, pts[3 * i + 2] = points[i].z;
+    const pbf_params p = params(config, sph::Scene<T, N, V>{});
+    Samples<N> o;
+    const pbf_sample_out out = sampleArrays(o, points.size(), what);
+    check(pbf_sample_points(ctx_, &p, points.size(), pts.data(), what, &out), "pbf_sample_points");
+    normalise(o, what);
+    return o;
+  }
+  Samples<N> sampleLattice(const sph::SphParams<T, N, V> &config, const V<3> &origin, const V<3> &spacing,
+                           const std::array<uint64_t, 3> &dims, uint32_t what = 0) {
+    const double o3[3] = {double(origin.x), double(origin.y), double(origin.z)};
+    const double s3[3] = {double(spacing.x), double(spacing.y), double(spacing.z)};
+    const uint64_t n = dims[0] * dims[1] * dims[2];
+    const pbf_params p = params(config, sph::Scene<T, N, V>{});
+    Samples<N> o;
+    const pbf_sample_out out = sampleArrays(o, n < (uint64_t(1) << 31) ? size_t(n) : 0, what);
+    check(pbf_sample_lattice(ctx_, &p, o3, s3, dims.data(), what, &out), "pbf_sample_lattice");
+    normalise(o, what);
     return o;
   }
 
