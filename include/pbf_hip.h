@@ -215,7 +215,12 @@ enum pbf_buffer {
                           for obstacles; PBF_ERR_STATE when there is none */
   PBF_BUF_DENSITY = 6, /* N[n]: rho_i of the last density pass (pbf_diagnostics with PBF_DIAG_DENSITY), device order; zero for
                           obstacles; PBF_ERR_STATE when there is none, or once the arrays have changed since */
-  PBF_BUF_COUNT_ = 7,
+  PBF_BUF_COUNT_ = 7, /* the values ABOVE it, not a bound for `which`: PBF_BUF_WHITEWATER below is 7 as well */
+};
+/* read through pbf_read_buffer like the values above (enum pbf_buffer itself is closed: its PBF_BUF_COUNT_ stays 7) */
+enum {
+  PBF_BUF_WHITEWATER = 7, /* N[4n]: {I_ta, I_wc, E_k, n_d} of the last pbf_whitewater_step, device order; zero for obstacles;
+                             PBF_ERR_STATE when there is none, or once the arrays have changed since */
 };
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes);
 size_t pbf_table_size(const pbf_ctx *ctx);                /* Morton(extent), sph.hpp:240 */
@@ -313,6 +318,76 @@ int pbf_sample_points(pbf_ctx *ctx, const pbf_params *params, size_t n, const do
 /* point (i, j, k) of the lattice has index (i * dims[1] + j) * dims[2] + k */
 int pbf_sample_lattice(pbf_ctx *ctx, const pbf_params *params, const double origin[3], const double spacing[3],
                        const uint64_t dims[3], uint32_t what, const pbf_sample_out *out);
+
+/* ---- whitewater: spray, foam and air bubbles on the resident state (no reference counterpart) ----------------------
+ * Diffuse particles after Ihmsen, Akinci, Akinci & Teschner 2012, "Unified spray, foam and air bubbles for particle-based
+ * fluids" (The Visual Computer 28): a pool owned by the ctx, advected and refilled by pbf_whitewater_step from the state the
+ * last pbf_step left.  Its own call on the ctx stream, synchronising (one polled read-back of the 56-byte record, no
+ * hipStreamSynchronize); never part of a step or of a captured hipGraph, and a step after it runs exactly as it would have
+ * without.  The same resident state, configuration, pool and frame give the same bytes under every setting of pbf_set_option.
+ *
+ * One step, everything in N, selects and never multiplies by 0 (csrc/pbf_whitewater.hpp restates every expression in its
+ * order; DESIGN.md has the reasoning):
+ *  1 advect   each diffuse particle, with nF = count[0], v_f = mv / weight of pbf_sample_points at its position (nF = 0 and
+ *             v_f = 0 outside the grid or where weight == 0), g = params->constant_force:
+ *               spray   nF <  spray_below:  v = g dt + v
+ *               bubble  nF >= bubble_from:  v = (v + (dt * -k_b) g) + k_d (v_f - v)
+ *               foam    otherwise:          v = v_f;  life = life - dt
+ *             then x += dt v in the relation the fluid's stored position and velocity have (positions in world units,
+ *             velocities in world / scale per time: x = (v dt + x / scale) * scale), x clamped to min_bound / max_bound.  It
+ *             dies when life <= 0, when a component is not finite, or when nF == 0 and the clamp moved it (it left the fluid
+ *             and hit a wall: a deviation from the paper).
+ *  2 normals  the surface-tension pass's density and normal (pbf_set_surface_tension's n_i), into fields of its own:
+ *             PBF_BUF_SURFACE and a later surface-tension pass do not notice.
+ *  3 potentials of each fluid particle i over the fluid candidates j != i of its 27 predict-time cells with 0 < r <= h, on
+ *             the final pStar (solver frame) and the stored velocities, W = 1 - r / h, x_ij = x_i - x_j, v_ij = v_i - v_j:
+ *               I_ta  = sum |v_ij| (1 - vhat_ij . xhat_ij) W                         (a term is 0 when |v_ij| == 0)
+ *               kappa = sum over j with xhat_ji . nhat_i < 0 of (1 - nhat_i . nhat_j) W     (0 when n_i or n_j is zero)
+ *               I_wc  = kappa if vhat_i . nhat_i >= 0.6, else 0;      E_k = m_i |v_i|^2 / 2
+ *             Phi(I, tau) = (min(I, tau[1]) - min(I, tau[0])) / (tau[1] - tau[0]);
+ *             n_d = Phi_k (k_ta Phi_ta + k_wc Phi_wc) dt (0 when v_i == 0);  count_i = min(floor(n_d + u(i, 0)), 1024);
+ *             the counts are scanned in 32 bits: their sum over one step must stay below 2^32 (always so below 4 M particles).
+ *  4 emit     child k of parent i goes to slot survivors + (sum of count_j over j < i in device order) + k; children past
+ *             the capacity are dropped and counted.  With vhat = v_i / |v_i|, e1, e2 orthonormal to it, r_V = h scale / 2:
+ *               r = r_V sqrt(u1), theta = 2 pi u2, hh = u3 dt |v_i|
+ *               x_d = x_i + r cos(theta) e1 + r sin(theta) e2 + hh vhat;   v_d = r cos(theta) e1 + r sin(theta) e2 + v_i
+ *               life = lifetime[0] + Phi_k (lifetime[1] - lifetime[0]);    parent_id = id_i
+ *             Its kind until its first advection: the class of the parent's count of fluid candidates within h, itself included.
+ *  5 compact  the survivors of 1 keep their order, the children follow in slot order.
+ * u for parent id, frame (whitewater steps since pbf_whitewater_configure), child k, stream s (0: the count, with k = 0;
+ * 1, 2, 3: u1, u2, u3):  u = (mix(seed ^ mix(id) ^ mix(frame * 2^32 + k * 4 + s)) >> 40) * 2^-24,  mix = splitmix64:
+ * x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31.
+ *
+ * pbf_whitewater_configure copies the configuration, resets the frame counter and keeps the pool when the capacity is
+ * unchanged (capacity 0 frees it and turns the feature off).  PBF_ERR_INVALID, the ctx unchanged: config == NULL; k_ta or
+ * k_wc negative or not finite; a tau pair with max <= min, lifetime with max < min, or either not finite; k_b not finite;
+ * k_d outside [0, 1]; spray_below > bubble_from; capacity >= 2^31.
+ * pbf_whitewater_upload replaces the pool's content (restart, tests): vel == NULL = at rest, life == NULL = lifetime[1];
+ * kind = spray, parent_id = 2^64 - 1.  PBF_ERR_STATE without a pool; PBF_ERR_INVALID for n > capacity or pos == NULL with n > 0.
+ * pbf_whitewater_step: the preconditions of pbf_sample_points — a step has run, its table is valid, params describe that
+ * grid — and a configured pool, PBF_ERR_STATE otherwise; also in slab mode (a diffuse particle near a cut needs both ranks'
+ * candidates and the pool would have to migrate).  PBF_ERR_INVALID: params == NULL, dt or scale <= 0.  On every error nothing
+ * is launched and the pool is untouched.  `out` may be NULL.  kind[] counts the pool after the step. */
+enum { PBF_WW_SPRAY = 0, PBF_WW_FOAM = 1, PBF_WW_BUBBLE = 2 };
+typedef struct pbf_whitewater {
+  uint64_t capacity;           /* diffuse particles the pool holds; 0 = off, frees the pool */
+  uint64_t seed;
+  double k_ta, k_wc;           /* particles per unit time at potential 1: trapped air, wave crest */
+  double tau_ta[2], tau_wc[2], tau_k[2];   /* clamp ranges {min, max}, min < max */
+  double lifetime[2];          /* {min, max}: life = min + Phi_k * (max - min) */
+  double k_b, k_d;             /* bubbles: buoyancy, drag in [0, 1] */
+  uint32_t spray_below, bubble_from; /* fluid candidates within h: < spray_below spray, >= bubble_from bubble, else foam
+                                        (Ihmsen: 6, 20) */
+} pbf_whitewater;
+typedef struct pbf_whitewater_stats {
+  uint64_t alive, emitted, dropped, died, kind[3];
+} pbf_whitewater_stats;
+int pbf_whitewater_configure(pbf_ctx *ctx, const pbf_whitewater *config);
+int pbf_whitewater_upload(pbf_ctx *ctx, size_t n, const void *pos, const void *vel, const void *life);
+int pbf_whitewater_step(pbf_ctx *ctx, const pbf_params *params, pbf_whitewater_stats *out);
+size_t pbf_whitewater_count(const pbf_ctx *ctx);
+/* pos / vel = 3 values of N per diffuse particle, life = 1; any pointer may be NULL */
+int pbf_whitewater_download(pbf_ctx *ctx, void *pos, void *vel, void *life, uint8_t *kind, uint64_t *parent_id);
 
 /* Device self-test of the trimmed exact sqrt / divides the precise pair terms use (csrc/pbf_kernels.hpp sqrt_rsq /
  * div_seeded / div_ranged) against the compiler's full IEEE forms, exhaustively: mismatches[0] sqrt over EVERY fp32 value

@@ -11,6 +11,7 @@ The directory name has a hyphen (it mirrors the reference repo's name), so impor
 """
 from .capi import (  # noqa: F401
     BUF_DENSITY,
+    BUF_WHITEWATER,
     DIAG_DENSITY,
     Diag,
     FLAG_FAST_MATH,
@@ -25,10 +26,16 @@ from .capi import (  # noqa: F401
     SampleOut,
     SlabCut,
     Solver,
+    WW_BUBBLE,
+    WW_FOAM,
+    WW_SPRAY,
+    Whitewater,
+    WhitewaterStats,
     apply_motion,
     build,
     default_params,
     lib,
     scene_cubes,
     scene_dambreak,
+    whitewater_config,
 )

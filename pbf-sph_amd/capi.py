@@ -19,6 +19,8 @@ BUF_NBR_COUNT = 3
 BUF_OMEGA = 4
 BUF_SURFACE = 5
 BUF_DENSITY = 6
+BUF_WHITEWATER = 7
+WW_SPRAY, WW_FOAM, WW_BUBBLE = 0, 1, 2
 DIAG_DENSITY = 1 << 0
 SAMPLE_VELOCITY, SAMPLE_COLOUR = 1 << 0, 1 << 1
 
@@ -121,6 +123,20 @@ class SampleOut(C.Structure):
                 ("count", C.c_void_p), ("outside", C.c_void_p)]
 
 
+class Whitewater(C.Structure):
+    """pbf_whitewater (include/pbf_hip.h)"""
+    _fields_ = [("capacity", C.c_uint64), ("seed", C.c_uint64), ("k_ta", C.c_double), ("k_wc", C.c_double),
+                ("tau_ta", C.c_double * 2), ("tau_wc", C.c_double * 2), ("tau_k", C.c_double * 2),
+                ("lifetime", C.c_double * 2), ("k_b", C.c_double), ("k_d", C.c_double),
+                ("spray_below", C.c_uint32), ("bubble_from", C.c_uint32)]
+
+
+class WhitewaterStats(C.Structure):
+    """pbf_whitewater_stats (include/pbf_hip.h): 7 eight-byte words"""
+    _fields_ = [("alive", C.c_uint64), ("emitted", C.c_uint64), ("dropped", C.c_uint64), ("died", C.c_uint64),
+                ("kind", C.c_uint64 * 3)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -170,6 +186,11 @@ _SIGS = {
     "pbf_sample_points": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_uint32, C.POINTER(SampleOut)]),
     "pbf_sample_lattice": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                      C.POINTER(SampleOut)]),
+    "pbf_whitewater_configure": (C.c_int, [C.c_void_p, C.POINTER(Whitewater)]),
+    "pbf_whitewater_upload": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbf_whitewater_step": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(WhitewaterStats)]),
+    "pbf_whitewater_count": (C.c_size_t, [C.c_void_p]),
+    "pbf_whitewater_download": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
     "pbf_read_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "pbf_table_size": (C.c_size_t, [C.c_void_p]),
     "pbf_selftest_math": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -277,6 +298,19 @@ def scene_dambreak(nominal, fp64=False):
     L.pbf_scene_dambreak(int(fp64), nominal, _vp(o["id"]), _vp(o["type"]), _vp(o["mass"]), _vp(o["pos"]),
                          _vp(o["vel"]), _vp(o["colour"]), C.byref(side))
     return o, side.value
+
+
+def whitewater_config(capacity, tau_ta, tau_wc, tau_k, k_ta=0.0, k_wc=0.0, lifetime=(2.0, 5.0), k_b=2.0, k_d=0.8,
+                      spray_below=6, bubble_from=20, seed=0):
+    """A pbf_whitewater from keywords.  The classification thresholds, buoyancy and drag default to the paper's; the tau
+    ranges depend on the scene and have no default."""
+    w = Whitewater()
+    w.capacity, w.seed, w.k_ta, w.k_wc = int(capacity), int(seed), float(k_ta), float(k_wc)
+    for name, pair in (("tau_ta", tau_ta), ("tau_wc", tau_wc), ("tau_k", tau_k), ("lifetime", lifetime)):
+        lo, hi = pair
+        getattr(w, name)[:] = [float(lo), float(hi)]
+    w.k_b, w.k_d, w.spray_below, w.bubble_from = float(k_b), float(k_d), int(spray_below), int(bubble_from)
+    return w
 
 
 class Solver:
@@ -450,6 +484,50 @@ class Solver:
         a, out, what = self._sample_arrays(n if n < 2 ** 31 else 0, velocity, colour)
         self._chk(self.L.pbf_sample_lattice(self.ctx, C.byref(p), _vp(o), _vp(sp), _vp(d), what, C.byref(out)), "pbf_sample_lattice")
         return self._sample_normalised(a)
+
+    def whitewater_configure(self, **cfg):
+        """Configure the pool of diffuse particles (pbf_whitewater_configure, include/pbf_hip.h).  Keywords = the fields of
+        pbf_whitewater; the tau ranges have no defaults (tools/whitewater_probe.py prints a scene's percentiles to pick
+        them from).  capacity=0 frees the pool."""
+        w = whitewater_config(**cfg)
+        self._chk(self.L.pbf_whitewater_configure(self.ctx, C.byref(w)), "pbf_whitewater_configure")
+        return self
+
+    def whitewater_upload(self, pos, vel=None, life=None):
+        """Replace the pool's content (restart, tests): pos (n,3) world; vel None = at rest; life None = lifetime[1]."""
+        pos = np.ascontiguousarray(pos, self.dtype).reshape(-1, 3)
+        n = len(pos)
+        vel = None if vel is None else np.ascontiguousarray(vel, self.dtype).reshape(n, 3)
+        life = None if life is None else np.ascontiguousarray(life, self.dtype).reshape(n)
+        self._chk(self.L.pbf_whitewater_upload(self.ctx, n, _vp(pos), _vp(vel), _vp(life)), "pbf_whitewater_upload")
+        return self
+
+    def whitewater_step(self, p):
+        """One whitewater step on the state the last step left -> dict(alive, emitted, dropped, died, kind=[spray, foam,
+        bubble])"""
+        st = WhitewaterStats()
+        self._chk(self.L.pbf_whitewater_step(self.ctx, C.byref(p), C.byref(st)), "pbf_whitewater_step")
+        return dict(alive=int(st.alive), emitted=int(st.emitted), dropped=int(st.dropped), died=int(st.died),
+                    kind=[int(k) for k in st.kind])
+
+    @property
+    def whitewater_count(self):
+        return self.L.pbf_whitewater_count(self.ctx)
+
+    def whitewater_download(self):
+        """The pool -> dict(pos (n,3), vel (n,3), life (n,), kind (n,) uint8, parent_id (n,) uint64)"""
+        n = self.whitewater_count
+        o = dict(pos=np.empty((n, 3), self.dtype), vel=np.empty((n, 3), self.dtype), life=np.empty(n, self.dtype),
+                 kind=np.empty(n, np.uint8), parent_id=np.empty(n, np.uint64))
+        self._chk(self.L.pbf_whitewater_download(self.ctx, _vp(o["pos"]), _vp(o["vel"]), _vp(o["life"]), _vp(o["kind"]),
+                                                 _vp(o["parent_id"])), "pbf_whitewater_download")
+        return o
+
+    def whitewater_potentials(self):
+        """(n,4): {I_ta, I_wc, E_k, n_d} of the last whitewater step, device order (zero for obstacles)"""
+        a = np.empty((self.n, 4), self.dtype)
+        self._chk(self.L.pbf_read_buffer(self.ctx, BUF_WHITEWATER, _vp(a), a.nbytes), "read whitewater potentials")
+        return a
 
     def sync(self):
         self._chk(self.L.pbf_sync(self.ctx), "pbf_sync")

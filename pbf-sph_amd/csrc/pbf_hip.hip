@@ -20,6 +20,7 @@
 #include "pbf_slab.hpp"
 #include "pbf_tiles.hpp"
 #include "pbf_mc.hpp"
+#include "pbf_whitewater.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 
@@ -167,6 +168,21 @@ struct pbf_ctx {
   DiagRecord *hostDiag = nullptr;
   uint32_t diagSeq = 0;
   bool diagDensityValid = false;
+  // pbf_whitewater_* (csrc/pbf_whitewater.hpp): the configuration, the pool in two sets (the compaction moves from one into
+  // the other), the scratch of its passes — k_sample's outputs at the pool's particles, the two scans' inputs and results,
+  // the normal pass's two fields (its own: surfA / surfB belong to the surface-tension pass), the potentials (PBF_BUF_WHITEWATER,
+  // while wwPotValid and st.sorted: dropped by every sort like diagDensityValid) — and the pinned record the host polls.
+  // An observer's state like the diagnostics': no step reads any of it.
+  bool wwOn = false;
+  pbf_whitewater ww{};
+  uint64_t wwFrame = 0;
+  size_t wwCount = 0;
+  int wwCur = 0;
+  DevBuf wwPos[2], wwVel[2], wwKind[2], wwParent[2];
+  DevBuf wwSample, wwAlive, wwAliveOff, wwSums, wwFieldA, wwFieldB, wwPot, wwEmit, wwOffset, wwChildKind;
+  WwRecord *hostWw = nullptr;
+  uint32_t wwSeq = 0;
+  bool wwPotValid = false;
   // advance() path: the caller's std::vector<Particle> buffer, page-locked in place (hipHostRegister) so the per-frame
   // 56-byte-per-particle upload and download are plain DMA instead of the runtime's pageable staging
   void *regPtr = nullptr;
@@ -613,6 +629,7 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   ctx->gatherSeq = 0;  // (fresh tickets)
   ctx->st.sorted_now(rows, rowDiffuse);
   ctx->diagDensityValid = false;  // (a new order: the last density pass describes the old one)
+  ctx->wwPotValid = false;
   if (!rowDiffuse) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
   return PBF_OK;
 }
@@ -983,6 +1000,19 @@ int ensure_diag(pbf_ctx *ctx, bool first, bool density) {
   return PBF_OK;
 }
 
+// pbf_whitewater_step's per-fluid-particle buffers, sized to the particle capacity: allocated when the pool is configured and
+// when an upload grows the capacity (the step itself only allocates when neither has seen the capacity yet)
+int ensure_whitewater_fields(pbf_ctx *ctx) {
+  const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4), n = ctx->cap;
+  if (!n) return PBF_OK;
+  if (int rc = ensure(ctx, ctx->wwFieldA, n * v)) return rc;
+  if (int rc = ensure(ctx, ctx->wwFieldB, n * v)) return rc;
+  if (int rc = ensure(ctx, ctx->wwPot, n * v)) return rc;
+  if (int rc = ensure(ctx, ctx->wwEmit, (n + SCAN_TILE) * 4)) return rc;  // (k_scan_block_sums reads whole uint4 pairs)
+  if (int rc = ensure(ctx, ctx->wwOffset, (n + SCAN_TILE) * 4)) return rc;
+  return ensure(ctx, ctx->wwChildKind, n);
+}
+
 // Surface tension and adhesion (Akinci et al. 2013), last among the extras: density -> A, normals -> B, velocity update.
 template <typename N, bool FAST> int surface_tension_impl(pbf_ctx *ctx, const StepConsts<N> &c) {
   if (int rc = ensure_surface(ctx)) return rc;
@@ -1176,6 +1206,8 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
+  if (ctx->wwOn)
+    if (int rc = ensure_whitewater_fields(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
   ctx->st.arrays_replaced(0);
   ctx->ghostsPending = false, ctx->slabActive = false;
@@ -1379,7 +1411,10 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->mcEdgeWord, &ctx->mcEdgeOffsets, &ctx->mcEdgeSums, &ctx->meshT, &ctx->meshV, &ctx->meshN,
                    &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB,
                    &ctx->sceneSources, &ctx->sceneDrains, &ctx->drainCounts, &ctx->queryPoints, &ctx->queryCounts,
-                   &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials, &ctx->samplePoints, &ctx->sampleOut};
+                   &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials, &ctx->samplePoints, &ctx->sampleOut,
+                   &ctx->wwPos[0], &ctx->wwPos[1], &ctx->wwVel[0], &ctx->wwVel[1], &ctx->wwKind[0], &ctx->wwKind[1],
+                   &ctx->wwParent[0], &ctx->wwParent[1], &ctx->wwSample, &ctx->wwAlive, &ctx->wwAliveOff, &ctx->wwSums,
+                   &ctx->wwFieldA, &ctx->wwFieldB, &ctx->wwPot, &ctx->wwEmit, &ctx->wwOffset, &ctx->wwChildKind};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
@@ -1392,6 +1427,7 @@ void pbf_destroy(pbf_ctx *ctx) {
   if (ctx->hostCounts) (void)hipHostFree(ctx->hostCounts);
   if (ctx->hostScene) (void)hipHostFree(ctx->hostScene);
   if (ctx->hostDiag) (void)hipHostFree(ctx->hostDiag);
+  if (ctx->hostWw) (void)hipHostFree(ctx->hostWw);
   if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
   if (ctx->regPtr) (void)hipHostUnregister(ctx->regPtr);
   if (ctx->ownStream) (void)hipStreamDestroy(ctx->stream);
@@ -1570,6 +1606,7 @@ void restore(pbf_ctx *ctx, const StepState &s) {
   ctx->st = s.st, ctx->hasObstacles = s.hasObstacles;  // (all of the derived state, not only what the key compares)
   ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
   ctx->diagDensityValid = false;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
+  ctx->wwPotValid = false;
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
@@ -1949,6 +1986,198 @@ int sample_check(pbf_ctx *ctx, const pbf_params *p, uint32_t what, const pbf_sam
   if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, w + " needs a step first (no valid cell table)");
   return PBF_OK;
 }
+
+// pbf_whitewater_*: see csrc/pbf_whitewater.hpp for the passes.  Like pbf_diagnostics it reads what the last step left and
+// writes only buffers of its own (materialise_pstar apart): no ticket word, no derived state, no stage timer — a step after
+// it makes the launches and takes the graph it would have without.
+static_assert(sizeof(pbf_whitewater_stats) == 7 * 8 && offsetof(WwRecord, seq) == sizeof(pbf_whitewater_stats) &&
+                  offsetof(pbf_whitewater_stats, kind) == offsetof(WwRecord, kind),
+              "WwRecord (pbf_whitewater.hpp) is pbf_whitewater_stats followed by the polled word");
+template <typename N> WwPool<N> ww_pool(pbf_ctx *ctx, int set) {
+  return WwPool<N>{ctx->wwPos[set].as<vec4<N>>(), ctx->wwVel[set].as<vec4<N>>(), ctx->wwKind[set].as<uint8_t>(),
+                   ctx->wwParent[set].as<uint64_t>()};
+}
+template <typename N> WwConsts<N> ww_consts(const pbf_ctx *ctx) {
+  const pbf_whitewater &g = ctx->ww;
+  WwConsts<N> w;
+  w.kTa = N(g.k_ta), w.kWc = N(g.k_wc), w.kB = N(g.k_b), w.kD = N(g.k_d);
+  for (int k = 0; k < 2; ++k)
+    w.tauTa[k] = N(g.tau_ta[k]), w.tauWc[k] = N(g.tau_wc[k]), w.tauK[k] = N(g.tau_k[k]), w.life[k] = N(g.lifetime[k]);
+  w.sprayBelow = g.spray_below, w.bubbleFrom = g.bubble_from;
+  w.seed = g.seed, w.frame = ctx->wwFrame;
+  return w;
+}
+// the pool's own buffers, sized to its capacity (pbf_whitewater_configure); k_sample's SoA outputs in one allocation
+struct WwSampleLayout {
+  size_t rho, weight, mv, count, outside, bytes;
+};
+WwSampleLayout ww_sample_layout(size_t cap, size_t esz) {
+  WwSampleLayout l{};
+  size_t at = 0;
+  auto place = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  l.rho = place(cap * esz), l.weight = place(cap * esz), l.mv = place(3 * cap * esz), l.count = place(2 * cap * 4);
+  l.outside = place(cap), l.bytes = at;
+  return l;
+}
+int release(pbf_ctx *ctx, DevBuf &b) {
+  if (b.p) HIPCHK(ctx, hipFree(b.p));
+  b.p = nullptr, b.cap = 0;
+  return PBF_OK;
+}
+int ww_resize_pool(pbf_ctx *ctx, size_t cap) {
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  DevBuf *pool[] = {&ctx->wwPos[0], &ctx->wwPos[1], &ctx->wwVel[0], &ctx->wwVel[1], &ctx->wwKind[0], &ctx->wwKind[1],
+                    &ctx->wwParent[0], &ctx->wwParent[1], &ctx->wwSample, &ctx->wwAlive, &ctx->wwAliveOff, &ctx->wwSums};
+  for (DevBuf *b : pool)
+    if (int rc = release(ctx, *b)) return rc;
+  ctx->wwCount = 0, ctx->wwCur = 0;
+  if (!cap) return PBF_OK;
+  const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4), esz = v / 4;
+  for (int s = 0; s < 2; ++s) {
+    if (int rc = ensure(ctx, ctx->wwPos[s], cap * v)) return rc;
+    if (int rc = ensure(ctx, ctx->wwVel[s], cap * v)) return rc;
+    if (int rc = ensure(ctx, ctx->wwKind[s], cap)) return rc;
+    if (int rc = ensure(ctx, ctx->wwParent[s], cap * 8)) return rc;
+  }
+  if (int rc = ensure(ctx, ctx->wwSample, ww_sample_layout(cap, esz).bytes)) return rc;
+  if (int rc = ensure(ctx, ctx->wwAlive, (cap + SCAN_TILE) * 4)) return rc;
+  return ensure(ctx, ctx->wwAliveOff, (cap + SCAN_TILE) * 4);
+}
+
+template <typename N, bool FAST> int whitewater_passes(pbf_ctx *ctx, const StepConsts<N> &c, uint32_t seq) {
+  const int s = ctx->st.cur, ws = ctx->wwCur, wd = 1 - ws;
+  const uint32_t n = uint32_t(ctx->n), m = uint32_t(ctx->wwCount), cap = uint32_t(ctx->ww.capacity);
+  const WwConsts<N> w = ww_consts<N>(ctx);
+  const WwPool<N> src = ww_pool<N>(ctx, ws), dst = ww_pool<N>(ctx, wd);
+  uint32_t *alive = ctx->wwAlive.as<uint32_t>(), *aliveOff = ctx->wwAliveOff.as<uint32_t>();
+  uint32_t *emit = ctx->wwEmit.as<uint32_t>(), *offset = ctx->wwOffset.as<uint32_t>();
+  if (m) {  // 1: advect what is in the pool on the state the last step left
+    const WwSampleLayout l = ww_sample_layout(cap, sizeof(N));
+    char *base = ctx->wwSample.as<char>();
+    const SampleOut<N> out{reinterpret_cast<N *>(base + l.rho), reinterpret_cast<N *>(base + l.weight),
+                           reinterpret_cast<N *>(base + l.mv),  nullptr,
+                           reinterpret_cast<uint32_t *>(base + l.count), reinterpret_cast<uint8_t *>(base + l.outside)};
+    const WwPoolSource<N> from{src.pos4, m};
+    if (int rc = launch_sample<N, FAST>(ctx, c, from, m, SAMPLE_VELOCITY, out)) return rc;
+    hipLaunchKernelGGL((k_ww_advect<N>), grid_for(m), dim3(BLOCK), 0, ctx->stream, c, w, m, src, out.weight, out.mv, out.count,
+                       alive);
+    LAUNCH_CHECK(ctx);
+  }
+  if (n) {  // 2, 3: normals into the whitewater state's own fields, then the potentials and the child counts
+    SurfArgs<N> a{};
+    a.pstar = ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), a.pos4 = ctx->pos4[s].as<const vec4<N>>();
+    a.type = ctx->type[s].as<const uint8_t>();
+    a.fieldOut = ctx->wwFieldA.as<vec4<N>>();
+    if (int rc = launch_gather<N, SurfaceDensityOp<N, FAST>>(ctx, c, a)) return rc;
+    a.fieldIn = ctx->wwFieldA.as<const vec4<N>>(), a.fieldOut = ctx->wwFieldB.as<vec4<N>>();
+    if (int rc = launch_gather<N, SurfaceNormalOp<N, FAST>>(ctx, c, a)) return rc;
+    typename WhitewaterOp<N, FAST>::Args wa{a.pstar, a.pos4, ctx->vel4[s].as<const vec4<N>>(), ctx->wwFieldB.as<const vec4<N>>(),
+                                            a.type, ctx->id[s].as<const uint64_t>(), ctx->wwPot.as<vec4<N>>(), emit,
+                                            ctx->wwChildKind.as<uint8_t>(), w};
+    if (int rc = launch_gather<N, WhitewaterOp<N, FAST>>(ctx, c, wa)) return rc;
+  }
+  // 4, 5: both exclusive scans in one set of launches — the child counts in device order, the survivor flags in pool order
+  ScanJobs jobs{};
+  int njobs = 0;
+  uint32_t *sums = ctx->wwSums.as<uint32_t>();
+  auto add_job = [&](const uint32_t *count, uint32_t len, uint32_t *table) {
+    jobs.count[njobs] = count, jobs.table[njobs] = table, jobs.len[njobs] = len, jobs.sums[njobs] = sums;
+    jobs.nb[njobs] = (len + SCAN_TILE - 1) / SCAN_TILE;
+    sums += jobs.nb[njobs];
+    ++njobs;
+  };
+  if (n) add_job(emit, n, offset);
+  if (m) add_job(alive, m, aliveOff);
+  if (njobs) launch_scans(ctx, jobs, njobs);
+  if (m) hipLaunchKernelGGL((k_ww_move<N>), grid_for(m), dim3(BLOCK), 0, ctx->stream, m, src, alive, aliveOff, dst);
+  if (n)
+    hipLaunchKernelGGL((k_ww_emit<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, c, w, ctx->pos4[s].as<const vec4<N>>(),
+                       ctx->vel4[s].as<const vec4<N>>(), ctx->id[s].as<const uint64_t>(), ctx->wwPot.as<const vec4<N>>(), emit,
+                       offset, ctx->wwChildKind.as<const uint8_t>(), m, alive, aliveOff, cap, dst);
+  hipLaunchKernelGGL(k_ww_final, dim3(1), dim3(BLOCK), 0, ctx->stream, n, emit, offset, m, alive, aliveOff, cap, dst.kind,
+                     ctx->hostWw, seq);
+  LAUNCH_CHECK(ctx);
+  return PBF_OK;
+}
+template <typename N> int whitewater_step_impl(pbf_ctx *ctx, const pbf_params *p, pbf_whitewater_stats *out) {
+  StepConsts<N> c;
+  if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_whitewater_step")) return rc;
+  if (int rc = ensure_whitewater_fields(ctx)) return rc;
+  const size_t nbSums = (ctx->cap + SCAN_TILE - 1) / SCAN_TILE + (size_t(ctx->ww.capacity) + SCAN_TILE - 1) / SCAN_TILE + 2;
+  if (int rc = ensure(ctx, ctx->wwSums, nbSums * 4)) return rc;
+  if (!ctx->hostWw) {
+    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostWw), sizeof(WwRecord), hipHostMallocDefault));
+    std::memset(ctx->hostWw, 0, sizeof(WwRecord));
+  }
+  if (int rc = join_diffuse(ctx)) return rc;
+  if (int rc = materialise_pstar<N>(ctx)) return rc;
+  const uint32_t seq = ++ctx->wwSeq ? ctx->wwSeq : ++ctx->wwSeq;  // (never 0: the pinned word starts there)
+  if (int rc = ctx->fast ? whitewater_passes<N, true>(ctx, c, seq) : whitewater_passes<N, false>(ctx, c, seq)) return rc;
+  if (int rc = wait_for_word(ctx, &ctx->hostWw->seq, seq, "whitewater read-back")) return rc;
+  std::atomic_thread_fence(std::memory_order_acquire);
+  pbf_whitewater_stats st;
+  std::memcpy(&st, ctx->hostWw, sizeof(st));
+  ctx->wwCount = size_t(st.alive), ctx->wwCur = 1 - ctx->wwCur, ctx->wwFrame++;
+  ctx->wwPotValid = ctx->n != 0;
+  if (out) *out = st;
+  return PBF_OK;
+}
+template <typename N> int whitewater_upload_impl(pbf_ctx *ctx, size_t n, const N *pos, const N *vel, const N *life) {
+  std::vector<vec4<N>> P(n), V(n);
+  for (size_t i = 0; i < n; ++i) {
+    P[i] = make_vec4<N>(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], life ? life[i] : N(ctx->ww.lifetime[1]));
+    V[i] = vel ? make_vec4<N>(vel[3 * i], vel[3 * i + 1], vel[3 * i + 2], N(0)) : make_vec4<N>(N(0), N(0), N(0), N(0));
+  }
+  const int s = ctx->wwCur;
+  if (n) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wwPos[s].p, P.data(), n * sizeof(vec4<N>), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->wwVel[s].p, V.data(), n * sizeof(vec4<N>), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->wwKind[s].p, 0, n, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->wwParent[s].p, 0xFF, n * 8, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // P, V are temporaries
+  }
+  ctx->wwCount = n;
+  return PBF_OK;
+}
+template <typename N> int whitewater_download_impl(pbf_ctx *ctx, N *pos, N *vel, N *life, uint8_t *kind, uint64_t *parent) {
+  const size_t n = ctx->wwCount;
+  if (!n) return PBF_OK;
+  const int s = ctx->wwCur;
+  std::vector<vec4<N>> tmp(n);
+  if (pos || life) {
+    HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->wwPos[s].p, n * sizeof(vec4<N>), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) {
+      if (pos) pos[3 * i] = tmp[i].x, pos[3 * i + 1] = tmp[i].y, pos[3 * i + 2] = tmp[i].z;
+      if (life) life[i] = tmp[i].w;
+    }
+  }
+  if (vel) {
+    HIPCHK(ctx, hipMemcpyAsync(tmp.data(), ctx->wwVel[s].p, n * sizeof(vec4<N>), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) vel[3 * i] = tmp[i].x, vel[3 * i + 1] = tmp[i].y, vel[3 * i + 2] = tmp[i].z;
+  }
+  if (kind) HIPCHK(ctx, hipMemcpyAsync(kind, ctx->wwKind[s].p, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (parent) HIPCHK(ctx, hipMemcpyAsync(parent, ctx->wwParent[s].p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
+}
+// what pbf_whitewater_configure refuses (the message, or NULL when the configuration is fine)
+const char *whitewater_config_error(const pbf_whitewater *g) {
+  auto pair = [](const double t[2]) { return std::isfinite(t[0]) && std::isfinite(t[1]) && t[1] > t[0]; };
+  if (!std::isfinite(g->k_ta) || !std::isfinite(g->k_wc) || g->k_ta < 0 || g->k_wc < 0) return "k_ta and k_wc must be finite and >= 0";
+  if (!pair(g->tau_ta) || !pair(g->tau_wc) || !pair(g->tau_k)) return "a tau range needs finite min < max";
+  if (!std::isfinite(g->lifetime[0]) || !std::isfinite(g->lifetime[1]) || g->lifetime[1] < g->lifetime[0]) return "lifetime needs finite min <= max";
+  if (!std::isfinite(g->k_b)) return "k_b must be finite";
+  if (!(g->k_d >= 0 && g->k_d <= 1)) return "k_d must lie in [0, 1]";
+  if (g->spray_below > g->bubble_from) return "spray_below must not exceed bubble_from";
+  if (g->capacity >= (uint64_t(1) << 31)) return "capacity must be < 2^31";
+  return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -2051,6 +2280,57 @@ int pbf_sample_lattice(pbf_ctx *ctx, const pbf_params *p, const double origin[3]
   return DISPATCH(ctx, sample_impl, ctx, p, size_t(n), nullptr, &lat, what, out, "pbf_sample_lattice");
 }
 
+int pbf_whitewater_configure(pbf_ctx *ctx, const pbf_whitewater *config) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!config) return fail(ctx, PBF_ERR_INVALID, "pbf_whitewater_configure: config == NULL");
+  if (const char *why = whitewater_config_error(config)) return fail(ctx, PBF_ERR_INVALID, std::string("pbf_whitewater_configure: ") + why);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!ctx->wwOn || config->capacity != ctx->ww.capacity) {  // (an unchanged capacity keeps the pool and what is in it)
+    ctx->wwOn = false, ctx->ww.capacity = 0;
+    if (int rc = ww_resize_pool(ctx, size_t(config->capacity))) return rc;
+  }
+  ctx->ww = *config, ctx->wwFrame = 0;
+  ctx->wwOn = config->capacity != 0;
+  if (!ctx->wwOn) {
+    ctx->wwPotValid = false;
+    return PBF_OK;
+  }
+  return ensure_whitewater_fields(ctx);
+}
+
+int pbf_whitewater_upload(pbf_ctx *ctx, size_t n, const void *pos, const void *vel, const void *life) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!ctx->wwOn) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_upload: no pool (pbf_whitewater_configure)");
+  if (n > ctx->ww.capacity) return fail(ctx, PBF_ERR_INVALID, "pbf_whitewater_upload: n exceeds the pool's capacity");
+  if (n && !pos) return fail(ctx, PBF_ERR_INVALID, "pbf_whitewater_upload: n > 0 but pos == NULL");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->fp64) return whitewater_upload_impl<double>(ctx, n, (const double *)pos, (const double *)vel, (const double *)life);
+  return whitewater_upload_impl<float>(ctx, n, (const float *)pos, (const float *)vel, (const float *)life);
+}
+
+int pbf_whitewater_step(pbf_ctx *ctx, const pbf_params *p, pbf_whitewater_stats *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!p) return fail(ctx, PBF_ERR_INVALID, "pbf_whitewater_step: params == NULL");
+  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  // a diffuse particle near a cut needs both ranks' candidates, and the pool would have to migrate with the fluid
+  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
+    return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_step is not supported in slab mode");
+  if (!ctx->wwOn) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_step: not configured (pbf_whitewater_configure)");
+  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_step needs a step first (no valid cell table)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return DISPATCH(ctx, whitewater_step_impl, ctx, p, out);
+}
+
+size_t pbf_whitewater_count(const pbf_ctx *ctx) { return ctx && ctx->wwOn ? ctx->wwCount : 0; }
+
+int pbf_whitewater_download(pbf_ctx *ctx, void *pos, void *vel, void *life, uint8_t *kind, uint64_t *parent_id) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!ctx->wwOn) return PBF_OK;  // (no pool: nothing to copy)
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->fp64) return whitewater_download_impl<double>(ctx, (double *)pos, (double *)vel, (double *)life, kind, parent_id);
+  return whitewater_download_impl<float>(ctx, (float *)pos, (float *)vel, (float *)life, kind, parent_id);
+}
+
 int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
   if (!ctx || !host) return PBF_ERR_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2077,6 +2357,11 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
     case PBF_BUF_SURFACE:
       if (!ctx->st.surfaceValid) return fail(ctx, PBF_ERR_STATE, "no surface-tension pass since the arrays last changed (pbf_set_surface_tension)");
       src = ctx->surfB.p, avail = std::min(ctx->n * v, ctx->surfB.cap);
+      break;
+    case PBF_BUF_WHITEWATER:
+      if (!ctx->wwPotValid || !ctx->st.sorted)
+        return fail(ctx, PBF_ERR_STATE, "no whitewater step since the arrays last changed (pbf_whitewater_step)");
+      src = ctx->wwPot.p, avail = std::min(ctx->n * v, ctx->wwPot.cap);
       break;
     case PBF_BUF_DENSITY:
       if (!ctx->diagDensityValid || !ctx->st.sorted)

@@ -35,6 +35,8 @@ struct Args {
   bool allDevices = false;                // --all-devices: EVERY device matching -d becomes one x-slab (RCCL halo)
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
+  double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
+  size_t wwCapacity = 0;                  // 0 = off
   bool indexedMesh = false;               // --indexed-mesh: the frames' surface as an indexed mesh (one vertex per lattice edge)
   size_t diagnostics = 0;                 // --diagnostics[=every]: with --resident, a JSON line of pbf_diagnostics every `every` frames
 
@@ -83,6 +85,11 @@ struct Args {
           "      --slabs=[K]                       K slabs on the first matching device (in-process exchange; tests)\n"
           "      --surface-tension=[g[,b]]         Opt-in surface tension (cohesion g) and adhesion to obstacles (b) after\n"
           "                                        Akinci et al. 2013; not in the reference. Single device only\n"
+          "      --whitewater=[k_ta,k_wc[,capacity]]  With --resident: spray, foam and air bubbles after Ihmsen et al. 2012,\n"
+          "                                        one whitewater step after every frame at these rates; the tau ranges are\n"
+          "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
+          "                                        `capacity` particles (default 262144); whitewater.ply beside cloud.ply.\n"
+          "                                        Single device only\n"
           "      --indexed-mesh                    Extract the surface as an indexed mesh (one vertex per crossed lattice\n"
           "                                        edge, watertight by index); mesh.obj becomes an indexed OBJ.\n"
           "                                        Single device only\n"
@@ -159,6 +166,13 @@ struct Args {
           const auto f = numbers(v);
           if (f.size() != 3) throw std::runtime_error("--probe: expected x,y,z");
           probes.push_back({f[0], f[1], f[2]});
+        }
+        else if (value(i, a, "", "--whitewater", v)) {
+          const auto f = numbers(v);
+          if (f.size() < 2 || f.size() > 3) throw std::runtime_error("--whitewater: expected k_ta,k_wc[,capacity]");
+          wwTa = f[0], wwWc = f[1];
+          wwCapacity = f.size() == 3 ? size_t(f[2]) : size_t(262144);
+          if (!(wwTa >= 0 && wwWc >= 0) || wwCapacity == 0) throw std::runtime_error("--whitewater: rates must be >= 0, capacity >= 1");
         }
         else if (value(i, a, "", "--surface-tension", v)) {
           const size_t comma = v.find(',');

@@ -122,6 +122,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   if (!args.probes.empty() && !args.resident) std::cout << "--probe takes effect with --resident: ignored" << std::endl;
+  const bool whitewater = args.wwCapacity != 0;
+  if (whitewater && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--whitewater is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (whitewater && !args.resident) std::cout << "--whitewater takes effect with --resident: ignored" << std::endl;
   if (args.indexedMesh && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--indexed-mesh is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -154,9 +160,28 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   std::vector<double> frameTime;
   hrc::time_point start, end;
   if (args.resident) solver.upload(particles, &param);
+  // --whitewater --resident: the first frame probes the potentials with rates 0 and takes the tau ranges from their
+  // quantiles; every frame after its fluid step runs one whitewater step
+  pbf_whitewater ww{};
+  bool wwConfigured = false;
+  if (whitewater && args.resident) {
+    ww.capacity = args.wwCapacity, ww.seed = 1;
+    ww.tau_ta[1] = ww.tau_wc[1] = ww.tau_k[1] = 1.0;
+    ww.lifetime[0] = 2.0, ww.lifetime[1] = 5.0, ww.k_b = 2.0, ww.k_d = 0.8, ww.spray_below = 6, ww.bubble_from = 20;
+    solver.whitewater(ww);
+  }
   auto one = [&](size_t frame) {
     if (args.resident) {
       solver.step(frameParam(frame), scene);
+      if (whitewater && solver.count()) {
+        solver.whitewaterStep(frameParam(frame));
+        if (!wwConfigured) {
+          solver.whitewaterQuantileTaus(ww);
+          ww.k_ta = args.wwTa, ww.k_wc = args.wwWc;
+          solver.whitewater(ww);
+          wwConfigured = true;
+        }
+      }
       if (param.surface && solver.count() && args.indexedMesh) indexed = solver.surfaceIndexed(frameParam(frame));
       else if (param.surface && solver.count()) result.mesh = solver.surface(frameParam(frame));
       solver.sync();  // per-frame time like the reference's blocking advance()
@@ -250,6 +275,13 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   std::cout << std::setprecision(6) << "Particle-steps/s     : " << psps << " (" << (args.resident ? "device-resident" : "advance(): upload+step+download per frame")
             << ", K=" << args.solverIter << ", " << (args.fp64 ? "fp64" : "fp32") << ")\n";
   const auto &imesh = args.resident ? indexed : solver.lastIndexedMesh();
+  sph::hip_impl::WhitewaterParticles<N, sph::vec> diffuse;
+  if (whitewater && args.resident) {
+    const auto &w = solver.whitewaterStats();
+    diffuse = solver.whitewaterParticles();
+    std::cout << "Whitewater           : " << w.alive << " alive (" << w.kind[0] << " spray, " << w.kind[1] << " foam, " << w.kind[2]
+              << " bubble), last frame: " << w.emitted << " emitted, " << w.dropped << " dropped, " << w.died << " died\n";
+  }
   if (args.indexedMesh)
     std::cout << "Indexed mesh         : " << imesh.vs.size() << " vertices, " << imesh.tris.size() / 3 << " triangles\n";
   if (args.verbose) {
@@ -268,6 +300,14 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
               << ",\"seconds\":" << seconds << ",\"particle_steps_per_s\":" << psps << ",\"frame_ms_mean\":" << st.mean
               << "}" << std::endl;
   sph::save(result, particles, output);
+  if (whitewater && args.resident && !output.empty()) {  // whitewater.ply: position + kind (0 spray, 1 foam, 2 bubble)
+    std::ofstream ply(std::filesystem::path(output) / "whitewater.ply");
+    ply << "ply\nformat ascii 1.0\nelement vertex " << diffuse.positions.size()
+        << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar kind\nend_header\n";
+    ply.precision(std::numeric_limits<N>::max_digits10);
+    for (size_t i = 0; i < diffuse.positions.size(); ++i)
+      ply << diffuse.positions[i].x << ' ' << diffuse.positions[i].y << ' ' << diffuse.positions[i].z << ' ' << int(diffuse.kind[i]) << '\n';
+  }
   if (args.indexedMesh && !output.empty()) {  // mesh.obj as an indexed OBJ: V `v`, V `vn`, T `f a//a b//b c//c`
     std::ofstream obj(std::filesystem::path(output) / "mesh.obj");
     for (const auto &v : imesh.vs) obj << "v " << v.x << ' ' << v.y << ' ' << v.z << '\n';

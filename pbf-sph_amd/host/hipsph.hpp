@@ -197,6 +197,15 @@ template <typename N> struct Samples {
   std::vector<uint8_t> outside{};
 };
 
+// What Solver::whitewaterParticles() returns: the pool of diffuse particles (pbf_whitewater_download, include/pbf_hip.h) —
+// positions in world units, velocities as the solver stores them, kind = PBF_WW_SPRAY / _FOAM / _BUBBLE.
+template <typename N, template <size_t, typename C = N> typename V> struct WhitewaterParticles {
+  std::vector<V<3>> positions{}, velocities{};
+  std::vector<N> life{};
+  std::vector<uint8_t> kind{};
+  std::vector<uint64_t> parentId{};
+};
+
 // What Solver::diagnostics() returns: pbf_diag (include/pbf_hip.h) as a plain struct; the density fields are 0 unless asked for.
 struct Diagnostics {
   uint64_t fluid = 0, obstacles = 0, nonFinite = 0;
@@ -234,6 +243,8 @@ class Solver final : public sph::Solver<T, N, V> {
   bool attached_ = false;
   bool indexedFrames_ = false;       // indexedMesh(true): advance() extracts the indexed mesh instead of Result::mesh
   IndexedMesh<N, V> lastIndexed_;
+  bool whitewaterOn_ = false;        // whitewater(config) with capacity > 0: advance() runs a whitewater step after the fluid's
+  pbf_whitewater_stats whitewaterStats_{};
   bool multi() const { return slabs_.size() > 1; }
 
   // PBF_SHIM_TIMING=1: mean host time of advance()'s phases, printed by the destructor (diagnostic)
@@ -542,6 +553,7 @@ public:
     upload(xs);
     clk.lap(0);
     step(config, wellsOnly, 1);
+    if (whitewaterOn_) whitewaterStep(config);  // (reads the state only: before the download sets off)
     if (phase_.on) sync();
     clk.lap(1);
     sph::Result<T, N, V> result;
@@ -652,6 +664,54 @@ public:
     check(pbf_sample_lattice(ctx_, &p, o3, s3, dims.data(), what, &out), "pbf_sample_lattice");
     normalise(o, what);
     return o;
+  }
+
+  // Whitewater — spray, foam and air bubbles after Ihmsen et al. 2012 (pbf_whitewater_*, include/pbf_hip.h; no reference
+  // counterpart): a pool of diffuse particles owned by the solver.  whitewater(config) configures it (capacity 0 frees it);
+  // from then on advance() runs one whitewater step after each fluid step, and the resident path calls whitewaterStep()
+  // after step().  Single device.
+  Solver &whitewater(const pbf_whitewater &config) {
+    if (multi()) throw std::runtime_error("whitewater is a single-device feature");
+    check(pbf_whitewater_configure(ctx_, &config), "pbf_whitewater_configure");
+    whitewaterOn_ = config.capacity != 0;
+    whitewaterStats_ = pbf_whitewater_stats{};
+    return *this;
+  }
+  // one whitewater step on the state the last step() left; `config` is that step's
+  pbf_whitewater_stats whitewaterStep(const sph::SphParams<T, N, V> &config) {
+    const pbf_params p = params(config, sph::Scene<T, N, V>{});
+    check(pbf_whitewater_step(ctx_, &p, &whitewaterStats_), "pbf_whitewater_step");
+    return whitewaterStats_;
+  }
+  const pbf_whitewater_stats &whitewaterStats() const { return whitewaterStats_; }  // the record of the last whitewater step
+  WhitewaterParticles<N, V> whitewaterParticles() {
+    WhitewaterParticles<N, V> o;
+    const size_t n = pbf_whitewater_count(ctx_);
+    o.positions.resize(n), o.velocities.resize(n), o.life.resize(n), o.kind.resize(n), o.parentId.resize(n);
+    check(pbf_whitewater_download(ctx_, o.positions.data(), o.velocities.data(), o.life.data(), o.kind.data(), o.parentId.data()),
+          "pbf_whitewater_download");
+    return o;
+  }
+  // The potentials {I_ta, I_wc, E_k, n_d} of the last whitewater step, 4 values per particle in device order.
+  std::vector<N> whitewaterPotentials() {
+    std::vector<N> pot(4 * pbf_count(ctx_));
+    check(pbf_read_buffer(ctx_, PBF_BUF_WHITEWATER, pot.data(), pot.size() * sizeof(N)), "pbf_read_buffer(whitewater)");
+    return pot;
+  }
+  // tau ranges for a scene nobody has looked at yet: the 10 % and 90 % quantiles of the positive values of the potentials
+  // the last whitewater step left (what tools/whitewater_probe.py prints), written into `config`
+  void whitewaterQuantileTaus(pbf_whitewater &config) {
+    const std::vector<N> pot = whitewaterPotentials();
+    double *tau[3] = {config.tau_ta, config.tau_wc, config.tau_k};
+    for (int c = 0; c < 3; ++c) {
+      std::vector<double> v;
+      for (size_t i = size_t(c); i < pot.size(); i += 4)
+        if (pot[i] > N(0)) v.push_back(double(pot[i]));
+      std::sort(v.begin(), v.end());
+      tau[c][0] = v.empty() ? 0.0 : v[size_t(0.1 * double(v.size() - 1))];
+      tau[c][1] = v.empty() ? 1.0 : v[size_t(0.9 * double(v.size() - 1))];
+      if (!(tau[c][1] > tau[c][0])) tau[c][1] = tau[c][0] + 1.0;
+    }
   }
 
   // The same surface as an indexed mesh: 40 V + 12 T bytes in fp32 instead of 120 T, watertight by index.  Single device (an
