@@ -389,6 +389,56 @@ size_t pbf_whitewater_count(const pbf_ctx *ctx);
 /* pos / vel = 3 values of N per diffuse particle, life = 1; any pointer may be NULL */
 int pbf_whitewater_download(pbf_ctx *ctx, void *pos, void *vel, void *life, uint8_t *kind, uint64_t *parent_id);
 
+/* ---- per-particle anisotropy after Yu & Turk 2013 on the resident state (no reference counterpart) --------------------
+ * Yu & Turk, "Reconstructing surfaces of particle-based fluids using anisotropic kernels" (ACM TOG 32(1)): for each particle
+ * a smoothed centre and an anisotropy matrix G_i from the weighted covariance of its neighbourhood — what a renderer needs
+ * to splat ellipsoids (flat discs on sheets, needles on jets) instead of equal spheres, as Macklin & Mueller draw their
+ * fluid.  One gather (AnisotropyOp, csrc/pbf_anisotropy.hpp) through whichever gather kernel the ctx is set to.  Its own call
+ * on the ctx stream, synchronising (plain async copies of the arrays asked for and one hipStreamSynchronize); never part of a
+ * step or of a captured hipGraph, and a step after it runs exactly as it would have without.  The same resident state and
+ * configuration give the same bytes under every setting of pbf_set_option.
+ *
+ * Frame: that of the extras passes, PBF_DIAG_DENSITY and pbf_sample_points — the final pStar (solver frame: world / scale,
+ * h = pbf_desc.h), the candidates of the 27 predict-time cells in walk order.  Candidates are FLUID particles only.
+ * Everything in N, not contracted.  DEVIATION from the paper: the support radius is h, not 2 h (the cells are h wide and the
+ * walk sees 27 of them).
+ * For a fluid particle i, over the fluid candidates j with r = |p_j - p_i| <= h (pair_geom's r; with PBF_FLAG_FAST_MATH its
+ * v_rsq form), i itself included, d = p_j - p_i; an excluded candidate's terms are SELECTED to +0, never multiplied by 0;
+ * one accumulator set per lane, in walk order:
+ *   q = r / h;   w = 1 - q * q * q
+ *   S += w;   M_a += w * d_a;   Q_ab += (w * d_a) * d_b   for ab = xx yy zz xy xz yz        (ten sums)
+ *   n_i = the candidates j != i (told apart by index, as PBF_DIAG_DENSITY does) with r <= h
+ * then
+ *   mu_a = M_a / S
+ *   centre_a = (p_a + smoothing * mu_a) * scale                  (world units: the one product finalise uses)
+ *   C_ab = (Q_ab / S - mu_a * mu_b) / (h * h)                    (the covariance in units of h^2)
+ *   C = R diag(sigma) R^T, sigma_1 >= sigma_2 >= sigma_3, negative round-off clamped to 0: cyclic Jacobi on the symmetric
+ *       3 x 3, pivots in the order (0,1), (0,2), (1,2), Rutishauser's rotation t = sign(theta) / (|theta| + sqrt(theta^2 + 1)),
+ *       theta = (a_qq - a_pp) / (2 a_pq), t selected to 0 where a_pq == 0, a fixed number of sweeps per precision (4 and 4:
+ *       no data-dependent exit), then a compare-select sorting network
+ *   if n_i > min_neighbours:  st_k = k_s * max(sigma_k, sigma_1 / k_r)          otherwise  st_k = k_n  and  R = I
+ *   G_ab = (((R_a1 * R_b1) * (1 / st_1) + (R_a2 * R_b2) * (1 / st_2)) + (R_a3 * R_b3) * (1 / st_3)) / h
+ *        i.e. G = (1 / h) R diag(1 / st) R^T, in the SOLVER frame: the ellipsoid |G x| <= 1 has semi-axes h st_k
+ *   axes = the three unit eigenvectors as rows, in descending order; the third is negated when their determinant is negative
+ *   radii = st (dimensionless)
+ * k_s: a uniformly filled ball has sigma = 0.15 under this weight (int r^4 (1 - r^3) / (3 int r^2 (1 - r^3)) = (3/40) / (1/2)),
+ * so k_s = 20 / 3 gives st ~ 1 in the bulk.  A particle with n_i > min_neighbours whose candidates all coincide with it
+ * (sigma_1 == 0) gets st = 0 and a G that is not finite.
+ * An obstacle's record: centre = its stored position, every other field 0.
+ *
+ * The arrays come back in device order (the order pbf_download returns now), COMPONENT-MAJOR: value k of particle i is at
+ * [k * n + i], n = pbf_count — centre 3 planes (x y z), G 6 (xx yy zz xy xz yz), axes 9 (row-major: axis 1 x y z, axis 2 ...),
+ * radii 3; neighbours[i] = n_i.  Any pointer may be NULL.
+ * Preconditions, those of pbf_sample_points: a step has run and its table is still valid; params describe the last step's
+ * grid; not slab mode (a particle near a cut needs both ranks' candidates) — PBF_ERR_STATE otherwise.
+ * PBF_ERR_INVALID: config, out or params NULL; dt or scale <= 0; smoothing outside [0, 1]; k_r < 1 or not finite; k_s or k_n
+ * not finite or <= 0.  On every error nothing is launched and the outputs are untouched.  pbf_count == 0 returns PBF_OK
+ * (after the argument and slab checks) and writes nothing. */
+typedef struct pbf_anisotropy { double smoothing, k_r, k_s, k_n; uint32_t min_neighbours; } pbf_anisotropy;
+typedef struct pbf_anisotropy_out { void *centre /*N[3n] world*/, *G /*N[6n]*/, *axes /*N[9n]*/, *radii /*N[3n]*/;
+                                    uint32_t *neighbours /*[n]*/; } pbf_anisotropy_out;   /* any pointer may be NULL */
+int pbf_anisotropy_compute(pbf_ctx *ctx, const pbf_params *params, const pbf_anisotropy *config, const pbf_anisotropy_out *out);
+
 /* Device self-test of the trimmed exact sqrt / divides the precise pair terms use (csrc/pbf_kernels.hpp sqrt_rsq /
  * div_seeded / div_ranged) against the compiler's full IEEE forms, exhaustively: mismatches[0] sqrt over EVERY fp32 value
  * >= 2^-75; mismatches[1] (h - r)^2 / r over every fp32 d2 whose root lies in [1e-8, h], for the context's own h and

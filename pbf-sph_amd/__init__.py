@@ -10,6 +10,8 @@ The directory name has a hyphen (it mirrors the reference repo's name), so impor
 `load_package()` from tests/conftest.py / bench.py, or via importlib by path.
 """
 from .capi import (  # noqa: F401
+    Anisotropy,
+    AnisotropyOut,
     BUF_DENSITY,
     BUF_WHITEWATER,
     DIAG_DENSITY,

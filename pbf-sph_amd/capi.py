@@ -137,6 +137,18 @@ class WhitewaterStats(C.Structure):
                 ("kind", C.c_uint64 * 3)]
 
 
+class Anisotropy(C.Structure):
+    """pbf_anisotropy (include/pbf_hip.h)"""
+    _fields_ = [("smoothing", C.c_double), ("k_r", C.c_double), ("k_s", C.c_double), ("k_n", C.c_double),
+                ("min_neighbours", C.c_uint32)]
+
+
+class AnisotropyOut(C.Structure):
+    """pbf_anisotropy_out (include/pbf_hip.h): five caller-owned host arrays, any may be NULL"""
+    _fields_ = [("centre", C.c_void_p), ("G", C.c_void_p), ("axes", C.c_void_p), ("radii", C.c_void_p),
+                ("neighbours", C.c_void_p)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -186,6 +198,7 @@ _SIGS = {
     "pbf_sample_points": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_uint32, C.POINTER(SampleOut)]),
     "pbf_sample_lattice": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                      C.POINTER(SampleOut)]),
+    "pbf_anisotropy_compute": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(Anisotropy), C.POINTER(AnisotropyOut)]),
     "pbf_whitewater_configure": (C.c_int, [C.c_void_p, C.POINTER(Whitewater)]),
     "pbf_whitewater_upload": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_whitewater_step": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(WhitewaterStats)]),
@@ -484,6 +497,24 @@ class Solver:
         a, out, what = self._sample_arrays(n if n < 2 ** 31 else 0, velocity, colour)
         self._chk(self.L.pbf_sample_lattice(self.ctx, C.byref(p), _vp(o), _vp(sp), _vp(d), what, C.byref(out)), "pbf_sample_lattice")
         return self._sample_normalised(a)
+
+    def anisotropy(self, p, smoothing=0.9, k_r=4.0, k_s=20.0 / 3.0, k_n=0.5, min_neighbours=25, only=None):
+        """Smoothed centres and anisotropy matrices after Yu & Turk 2013 on the state the last step left
+        (pbf_anisotropy_compute, include/pbf_hip.h) -> dict of arrays in device order: centre (n,3) world, G (n,6)
+        {xx yy zz xy xz yz} in the solver frame, axes (n,3,3) unit rows in descending order, radii (n,3), neighbours (n,).
+        The library's arrays are component-major; these are transposed views of them.  only: names to ask for (the other
+        pointers are NULL)."""
+        n = self.n
+        planes = dict(centre=3, G=6, axes=9, radii=3)
+        names = list(planes) + ["neighbours"] if only is None else list(only)
+        raw = {k: np.zeros((planes[k], n), self.dtype) if k in planes else np.zeros(n, np.uint32) for k in names}
+        cfg = Anisotropy(float(smoothing), float(k_r), float(k_s), float(k_n), int(min_neighbours))
+        out = AnisotropyOut(*[_vp(raw.get(k)) for k in ("centre", "G", "axes", "radii", "neighbours")])
+        self._chk(self.L.pbf_anisotropy_compute(self.ctx, C.byref(p), C.byref(cfg), C.byref(out)), "pbf_anisotropy_compute")
+        o = {k: (v.T if k in planes else v) for k, v in raw.items()}
+        if "axes" in o:
+            o["axes"] = o["axes"].reshape(n, 3, 3)
+        return o
 
     def whitewater_configure(self, **cfg):
         """Configure the pool of diffuse particles (pbf_whitewater_configure, include/pbf_hip.h).  Keywords = the fields of

@@ -21,6 +21,7 @@
 #include "pbf_tiles.hpp"
 #include "pbf_mc.hpp"
 #include "pbf_whitewater.hpp"
+#include "pbf_anisotropy.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 
@@ -183,6 +184,10 @@ struct pbf_ctx {
   WwRecord *hostWw = nullptr;
   uint32_t wwSeq = 0;
   bool wwPotValid = false;
+  // pbf_anisotropy_compute (csrc/pbf_anisotropy.hpp): AnisotropyOp's outputs in one allocation sized to the capacity —
+  // {centre 3, G 6, axes 9, radii 3} values of N and one uint32 per particle — made by the first call.  Scratch of an
+  // observer: no step reads or writes it.
+  DevBuf anisoOut;
   // advance() path: the caller's std::vector<Particle> buffer, page-locked in place (hipHostRegister) so the per-frame
   // 56-byte-per-particle upload and download are plain DMA instead of the runtime's pageable staging
   void *regPtr = nullptr;
@@ -1414,7 +1419,8 @@ void pbf_destroy(pbf_ctx *ctx) {
                    &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials, &ctx->samplePoints, &ctx->sampleOut,
                    &ctx->wwPos[0], &ctx->wwPos[1], &ctx->wwVel[0], &ctx->wwVel[1], &ctx->wwKind[0], &ctx->wwKind[1],
                    &ctx->wwParent[0], &ctx->wwParent[1], &ctx->wwSample, &ctx->wwAlive, &ctx->wwAliveOff, &ctx->wwSums,
-                   &ctx->wwFieldA, &ctx->wwFieldB, &ctx->wwPot, &ctx->wwEmit, &ctx->wwOffset, &ctx->wwChildKind};
+                   &ctx->wwFieldA, &ctx->wwFieldB, &ctx->wwPot, &ctx->wwEmit, &ctx->wwOffset, &ctx->wwChildKind,
+                   &ctx->anisoOut};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
@@ -1987,6 +1993,55 @@ int sample_check(pbf_ctx *ctx, const pbf_params *p, uint32_t what, const pbf_sam
   return PBF_OK;
 }
 
+// pbf_anisotropy_compute: one AnisotropyOp launch over the final pStar on the last step's keys and table, through whichever
+// gather kernel the ctx is set to.  Like pbf_sample_points it touches nothing a step reads (materialise_pstar apart), takes no
+// ticket word and is never captured; the arrays asked for travel with plain async copies straight into the caller's memory.
+template <typename N> int anisotropy_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_anisotropy *g, const pbf_anisotropy_out *o) {
+  StepConsts<N> c;
+  if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_anisotropy_compute")) return rc;
+  // the outputs' places in the one allocation (sized to the capacity), each 256-byte aligned; a plane has n elements
+  const size_t cap = ctx->cap, n = ctx->n;
+  size_t at = 0;
+  auto place = [&](size_t bytes) {
+    const size_t here = at;
+    at += (bytes + 255) / 256 * 256;
+    return here;
+  };
+  const size_t oCentre = place(3 * cap * sizeof(N)), oG = place(6 * cap * sizeof(N)), oAxes = place(9 * cap * sizeof(N)),
+               oRadii = place(3 * cap * sizeof(N)), oNbr = place(cap * 4);
+  if (int rc = ensure(ctx, ctx->anisoOut, at)) return rc;
+  if (int rc = join_diffuse(ctx)) return rc;
+  if (int rc = materialise_pstar<N>(ctx)) return rc;
+  char *base = ctx->anisoOut.as<char>();
+  const int s = ctx->st.cur;
+  const AnisoConsts<N> k{N(g->smoothing), N(g->k_r), N(g->k_s), N(g->k_n), g->min_neighbours};
+  int rc;
+  if (ctx->fast) {
+    typename AnisotropyOp<N, true>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
+                                           ctx->type[s].as<const uint8_t>(), reinterpret_cast<N *>(base + oCentre),
+                                           reinterpret_cast<N *>(base + oG), reinterpret_cast<N *>(base + oAxes),
+                                           reinterpret_cast<N *>(base + oRadii), reinterpret_cast<uint32_t *>(base + oNbr), k};
+    rc = launch_gather<N, AnisotropyOp<N, true>>(ctx, c, a);
+  } else {
+    typename AnisotropyOp<N, false>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
+                                            ctx->type[s].as<const uint8_t>(), reinterpret_cast<N *>(base + oCentre),
+                                            reinterpret_cast<N *>(base + oG), reinterpret_cast<N *>(base + oAxes),
+                                            reinterpret_cast<N *>(base + oRadii), reinterpret_cast<uint32_t *>(base + oNbr), k};
+    rc = launch_gather<N, AnisotropyOp<N, false>>(ctx, c, a);
+  }
+  if (rc != PBF_OK) return rc;
+  auto back = [&](void *host, size_t off, size_t bytes) {
+    return host ? hipMemcpyAsync(host, base + off, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  };
+  HIPCHK(ctx, back(o->centre, oCentre, 3 * n * sizeof(N)));
+  HIPCHK(ctx, back(o->G, oG, 6 * n * sizeof(N)));
+  HIPCHK(ctx, back(o->axes, oAxes, 9 * n * sizeof(N)));
+  HIPCHK(ctx, back(o->radii, oRadii, 3 * n * sizeof(N)));
+  HIPCHK(ctx, back(o->neighbours, oNbr, n * 4));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
+}
+
 // pbf_whitewater_*: see csrc/pbf_whitewater.hpp for the passes.  Like pbf_diagnostics it reads what the last step left and
 // writes only buffers of its own (materialise_pstar apart): no ticket word, no derived state, no stage timer — a step after
 // it makes the launches and takes the graph it would have without.
@@ -2278,6 +2333,23 @@ int pbf_sample_lattice(pbf_ctx *ctx, const pbf_params *p, const double origin[3]
   if (int rc = sample_check(ctx, p, what, out, "pbf_sample_lattice")) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return DISPATCH(ctx, sample_impl, ctx, p, size_t(n), nullptr, &lat, what, out, "pbf_sample_lattice");
+}
+
+int pbf_anisotropy_compute(pbf_ctx *ctx, const pbf_params *p, const pbf_anisotropy *g, const pbf_anisotropy_out *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!p || !g || !out) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: NULL argument");
+  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  if (!(g->smoothing >= 0 && g->smoothing <= 1)) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: smoothing must lie in [0, 1]");
+  if (!(g->k_r >= 1) || !std::isfinite(g->k_r)) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: k_r must be finite and >= 1");
+  if (!(g->k_s > 0) || !std::isfinite(g->k_s) || !(g->k_n > 0) || !std::isfinite(g->k_n))
+    return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: k_s and k_n must be finite and > 0");
+  // a particle near a cut needs both ranks' candidates, and the copies of the neighbours' columns would have to be left out
+  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
+    return fail(ctx, PBF_ERR_STATE, "pbf_anisotropy_compute is not supported in slab mode");
+  if (ctx->n == 0) return PBF_OK;
+  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_anisotropy_compute needs a step first (no valid cell table)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return DISPATCH(ctx, anisotropy_impl, ctx, p, g, out);
 }
 
 int pbf_whitewater_configure(pbf_ctx *ctx, const pbf_whitewater *config) {

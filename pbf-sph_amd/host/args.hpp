@@ -37,6 +37,9 @@ struct Args {
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
   double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
   size_t wwCapacity = 0;                  // 0 = off
+  bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
+  double anisoCfg[4] = {0.9, 4.0, 20.0 / 3.0, 0.5};
+  unsigned anisoMinNeighbours = 25;
   bool indexedMesh = false;               // --indexed-mesh: the frames' surface as an indexed mesh (one vertex per lattice edge)
   size_t diagnostics = 0;                 // --diagnostics[=every]: with --resident, a JSON line of pbf_diagnostics every `every` frames
 
@@ -90,6 +93,10 @@ struct Args {
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
           "                                        `capacity` particles (default 262144); whitewater.ply beside cloud.ply.\n"
           "                                        Single device only\n"
+          "      --anisotropy[=s,k_r,k_s,k_n,N]    With --resident: smoothed centres and anisotropy (Yu & Turk 2013) of the final\n"
+          "                                        state, computed on the device; ellipsoids.ply beside cloud.ply (centre, three\n"
+          "                                        radii, three axes and the neighbour count per fluid particle). Defaults:\n"
+          "                                        0.9,4,6.6667,0.5,25. Single device only\n"
           "      --indexed-mesh                    Extract the surface as an indexed mesh (one vertex per crossed lattice\n"
           "                                        edge, watertight by index); mesh.obj becomes an indexed OBJ.\n"
           "                                        Single device only\n"
@@ -152,6 +159,14 @@ struct Args {
         else if (a == "--json") json = true;
         else if (a == "--all-devices") allDevices = true;
         else if (a == "--indexed-mesh") indexedMesh = true;
+        else if (a == "--anisotropy") anisotropy = true;
+        else if (a.rfind("--anisotropy=", 0) == 0) {
+          const auto f = numbers(a.substr(13));
+          if (f.size() != 5 || !(f[4] >= 0)) throw std::runtime_error("--anisotropy: expected smoothing,k_r,k_s,k_n,min_neighbours");
+          anisotropy = true;
+          for (int k = 0; k < 4; ++k) anisoCfg[k] = f[size_t(k)];
+          anisoMinNeighbours = unsigned(f[4]);
+        }
         else if (a == "--diagnostics") diagnostics = 1;
         else if (a.rfind("--diagnostics=", 0) == 0) {
           diagnostics = std::stoull(a.substr(14));

@@ -128,6 +128,11 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   if (whitewater && !args.resident) std::cout << "--whitewater takes effect with --resident: ignored" << std::endl;
+  if (args.anisotropy && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--anisotropy is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (args.anisotropy && !args.resident) std::cout << "--anisotropy takes effect with --resident: ignored" << std::endl;
   if (args.indexedMesh && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--indexed-mesh is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -255,6 +260,13 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     if (probing && (args.probeEvery ? (frame + 1) % args.probeEvery == 0 : frame + 1 == args.iterations)) probe(frame);
   }
   end = hrc::now();
+  // --anisotropy --resident: the final state's ellipsoids, in the order the download below returns
+  sph::hip_impl::Anisotropy<N> ellipsoids;
+  const bool anisotropy = args.anisotropy && args.resident && args.warmup + args.iterations > 0;
+  if (anisotropy) {
+    const pbf_anisotropy cfg{args.anisoCfg[0], args.anisoCfg[1], args.anisoCfg[2], args.anisoCfg[3], args.anisoMinNeighbours};
+    ellipsoids = solver.anisotropy(frameParam(args.iterations ? args.iterations - 1 : args.warmup - 1), scene, cfg);
+  }
   if (args.resident) solver.download(particles);
 
   const double seconds = (duration_millis(end - start).count() - diagMillis) / 1000.0;
@@ -307,6 +319,24 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     ply.precision(std::numeric_limits<N>::max_digits10);
     for (size_t i = 0; i < diffuse.positions.size(); ++i)
       ply << diffuse.positions[i].x << ' ' << diffuse.positions[i].y << ' ' << diffuse.positions[i].z << ' ' << int(diffuse.kind[i]) << '\n';
+  }
+  if (anisotropy && !output.empty()) {  // ellipsoids.ply: one vertex per FLUID particle, semi-axes h * scale * radius_k along axis k
+    const size_t n = ellipsoids.neighbours.size();
+    size_t fluid = 0;
+    for (size_t i = 0; i < n && i < particles.size(); ++i) fluid += particles[i].type == sph::Type::Fluid ? 1 : 0;
+    std::ofstream ply(std::filesystem::path(output) / "ellipsoids.ply");
+    ply << "ply\nformat ascii 1.0\nelement vertex " << fluid << "\nproperty float x\nproperty float y\nproperty float z\n";
+    for (const char *name : {"r1", "r2", "r3", "a1x", "a1y", "a1z", "a2x", "a2y", "a2z", "a3x", "a3y", "a3z"})
+      ply << "property float " << name << "\n";
+    ply << "property uint neighbours\nend_header\n";
+    ply.precision(std::numeric_limits<N>::max_digits10);
+    for (size_t i = 0; i < n && i < particles.size(); ++i) {
+      if (particles[i].type != sph::Type::Fluid) continue;
+      for (size_t k = 0; k < 3; ++k) ply << ellipsoids.centre[k * n + i] << ' ';
+      for (size_t k = 0; k < 3; ++k) ply << ellipsoids.radii[k * n + i] << ' ';
+      for (size_t k = 0; k < 9; ++k) ply << ellipsoids.axes[k * n + i] << ' ';
+      ply << ellipsoids.neighbours[i] << '\n';
+    }
   }
   if (args.indexedMesh && !output.empty()) {  // mesh.obj as an indexed OBJ: V `v`, V `vn`, T `f a//a b//b c//c`
     std::ofstream obj(std::filesystem::path(output) / "mesh.obj");

@@ -197,6 +197,14 @@ template <typename N> struct Samples {
   std::vector<uint8_t> outside{};
 };
 
+// What Solver::anisotropy() returns: the arrays of pbf_anisotropy_out (include/pbf_hip.h) in device order, COMPONENT-MAJOR —
+// value k of particle i at [k * n + i], n = neighbours.size(): centre 3 planes (world), G 6 (xx yy zz xy xz yz, solver frame),
+// axes 9 (three unit rows, descending), radii 3.
+template <typename N> struct Anisotropy {
+  std::vector<N> centre{}, G{}, axes{}, radii{};
+  std::vector<uint32_t> neighbours{};
+};
+
 // What Solver::whitewaterParticles() returns: the pool of diffuse particles (pbf_whitewater_download, include/pbf_hip.h) —
 // positions in world units, velocities as the solver stores them, kind = PBF_WW_SPRAY / _FOAM / _BUBBLE.
 template <typename N, template <size_t, typename C = N> typename V> struct WhitewaterParticles {
@@ -663,6 +671,19 @@ public:
     const pbf_sample_out out = sampleArrays(o, n < (uint64_t(1) << 31) ? size_t(n) : 0, what);
     check(pbf_sample_lattice(ctx_, &p, o3, s3, dims.data(), what, &out), "pbf_sample_lattice");
     normalise(o, what);
+    return o;
+  }
+
+  // Per-particle smoothed centres and anisotropy matrices after Yu & Turk 2013 (pbf_anisotropy_compute, include/pbf_hip.h; no
+  // reference counterpart) on the state the last step() left; `config` and `scene` are that step's.  No numerics here.
+  // Single device: on several the library's own refusal is thrown.
+  Anisotropy<N> anisotropy(const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene, const pbf_anisotropy &cfg) {
+    const pbf_params p = params(config, scene);
+    const size_t n = pbf_count(ctx_);
+    Anisotropy<N> o;
+    o.centre.resize(3 * n), o.G.resize(6 * n), o.axes.resize(9 * n), o.radii.resize(3 * n), o.neighbours.resize(n);
+    const pbf_anisotropy_out out{o.centre.data(), o.G.data(), o.axes.data(), o.radii.data(), o.neighbours.data()};
+    check(pbf_anisotropy_compute(ctx_, &p, &cfg, &out), "pbf_anisotropy_compute");
     return o;
   }
 
