@@ -12,8 +12,10 @@
 #include <cstring>
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "pbf_kernels.hpp"
@@ -31,10 +33,75 @@ namespace {
 
 thread_local std::string g_create_error;
 
+// Device memory with one owner.  Every DevBuf and Pinned of this file is a member of pbf_ctx (or a local of ensure()), so the
+// destructors run inside pbf_destroy's `delete ctx` — after it has made the context's device current and synchronised the
+// stream — or on a grow, after ensure() has synchronised: no free ever races work that still uses the memory, and no member
+// can be forgotten.  snapshot() / restore() permute p / cap among the fifteen role buffers directly; each allocation still has
+// exactly one owner afterwards.
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      (void)reset();
+      p = o.p, cap = o.cap;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { (void)reset(); }
+  hipError_t reset() {  // frees now
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr, cap = 0;
+    return e;
+  }
   template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+// Pinned host memory with one owner: `count` elements of T, allocated by the first ensure(), zero-filled (`zero` = false: the
+// caller overwrites all it reads), freed with the context like a DevBuf.  Nothing is carried across a grow.
+template <typename T> struct Pinned {
+  T *p = nullptr;
+  size_t count = 0;
+  Pinned() = default;
+  Pinned(const Pinned &) = delete;
+  Pinned &operator=(const Pinned &) = delete;
+  ~Pinned() { reset(); }
+  void reset() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr, count = 0;
+  }
+  hipError_t ensure(size_t n, bool zero = true) {
+    if (count >= n) return hipSuccess;
+    reset();
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), n * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
+    if (zero) std::memset(static_cast<void *>(p), 0, n * sizeof(T));
+    count = n;
+    return hipSuccess;
+  }
+};
+
+// A read-back mailbox: one pinned record T whose last member `seq` the host polls.  arm() makes the record and hands out the
+// word for this round (never 0: the pinned word starts there); the last kernel of the round writes the record and then,
+// behind a system-scope fence, that word; receive() (below wait_for_word) spins on it and copies the record out.
+template <typename T> struct Mailbox {
+  Pinned<T> rec;
+  uint32_t seq = 0;
+  hipError_t arm(uint32_t &word) {
+    word = ++seq ? seq : ++seq;
+    return rec.ensure(1);
+  }
+};
+struct SceneRecord {  // k_drain_scan's host[0] and host[1]
+  uint32_t kept, seq;
 };
 
 constexpr uint32_t kTickets = 254;  // (kTickets + 2 words = 1024 bytes: ONE fill kernel per step; 1028 bytes took two)
@@ -116,13 +183,12 @@ struct pbf_ctx {
   uint32_t ghostAt = 0;              // pre-sort index of the first copy received this step (k_unpack_field)
   uint32_t slabSeq = 0;              // sequence number of the next read-back (k_slab_counts -> pinned host word)
   uint64_t slabHostSyncs = 0;        // host read-backs inside pbf_slab_step so far (2 per step: the two assembly rounds)
-  uint32_t *hostCounts = nullptr;  // pinned: read-back of the assembly rounds' counts
+  Pinned<uint32_t> hostCounts;     // read-back of the assembly rounds' counts (16 words)
   size_t reserve = 0;        // pbf_reserve: capacity kept for migrants and ghost copies
   uint32_t nOwned = 0, sentL = 0, sentR = 0, gotL = 0, gotR = 0;
   // marching cubes (pbf_surface)
   DevBuf latticePN, latticeC, mcCounts, mcOffsets, mcSums, meshV, meshN, meshC, mcNear;
-  void *meshHost = nullptr;  // pinned staging of the last mesh (pbf_map_mesh)
-  size_t meshHostCap = 0;
+  Pinned<char> meshHost;  // staging of the last mesh (pbf_map_mesh)
   bool meshStaged = false;
   uint64_t mcSample[3] = {0, 0, 0};
   uint64_t mcTriangles = 0;
@@ -153,8 +219,7 @@ struct pbf_ctx {
   uint32_t emitTotal = 0;  // particles the sources emit per step
   size_t uploaded = 0;     // particles of the last upload: with pbf_reserve the sources' bound is max(reserve, uploaded)
   DevBuf sceneSources, sceneDrains, drainCounts;
-  uint32_t *hostScene = nullptr;
-  uint32_t sceneSeq = 0;
+  Mailbox<SceneRecord> hostScene;
   uint64_t sceneHostSyncs = 0;
   DevBuf queryPoints, queryCounts, queryIds;  // pbf_query_cells
   // pbf_sample_points / pbf_sample_lattice: the uploaded points in N, and one allocation holding the call's SoA outputs
@@ -162,17 +227,19 @@ struct pbf_ctx {
   DevBuf samplePoints, sampleOut;
   // pbf_diagnostics: the density pass's own outputs (N[cap] rho, uint32[cap] neighbour counts; allocated with the first
   // density request), one partial record per DIAG_TILE particles, the pinned record the last kernel writes and the host
-  // polls.  diagDensityValid: diagRho holds the pass of the CURRENT sorted set (PBF_BUF_DENSITY) — set by the pass, dropped by
-  // every sort (stage_sort, or a replayed one: restore), and only ever believed while st.sorted holds, which every event
-  // that changes the arrays clears.  An observer's record, not derived state of the step: it is no part of DerivedState.
+  // polls.  diagRhoAt: the order epoch (below) diagRho's pass was made at (PBF_BUF_DENSITY).
   DevBuf diagRho, diagNbr, diagPartials;
-  DiagRecord *hostDiag = nullptr;
-  uint32_t diagSeq = 0;
-  bool diagDensityValid = false;
+  Mailbox<DiagRecord> hostDiag;
+  uint64_t diagRhoAt = 0;
+  // What an observer leaves behind for a later read describes the sorted set it ran on: it goes stale with every sort
+  // (stage_sort, or a replayed one: restore), which bumps orderEpoch, and is only ever believed while st.sorted holds, which
+  // every event that changes the arrays clears; record_current() asks both.  0 = never made.  An observer-side fact, not
+  // derived state of the step: it is no part of DerivedState.
+  uint64_t orderEpoch = 1;
   // pbf_whitewater_* (csrc/pbf_whitewater.hpp): the configuration, the pool in two sets (the compaction moves from one into
   // the other), the scratch of its passes — k_sample's outputs at the pool's particles, the two scans' inputs and results,
   // the normal pass's two fields (its own: surfA / surfB belong to the surface-tension pass), the potentials (PBF_BUF_WHITEWATER,
-  // while wwPotValid and st.sorted: dropped by every sort like diagDensityValid) — and the pinned record the host polls.
+  // while current like diagRho: wwPotAt) — and the pinned record the host polls.
   // An observer's state like the diagnostics': no step reads any of it.
   bool wwOn = false;
   pbf_whitewater ww{};
@@ -181,9 +248,8 @@ struct pbf_ctx {
   int wwCur = 0;
   DevBuf wwPos[2], wwVel[2], wwKind[2], wwParent[2];
   DevBuf wwSample, wwAlive, wwAliveOff, wwSums, wwFieldA, wwFieldB, wwPot, wwEmit, wwOffset, wwChildKind;
-  WwRecord *hostWw = nullptr;
-  uint32_t wwSeq = 0;
-  bool wwPotValid = false;
+  Mailbox<WwRecord> hostWw;
+  uint64_t wwPotAt = 0;
   // pbf_anisotropy_compute (csrc/pbf_anisotropy.hpp): AnisotropyOp's outputs in one allocation sized to the capacity —
   // {centre 3, G 6, axes 9, radii 3} values of N and one uint32 per particle — made by the first call.  Scratch of an
   // observer: no step reads or writes it.
@@ -270,20 +336,22 @@ int fail(pbf_ctx *ctx, int code, const std::string &msg) {
 
 int ensure(pbf_ctx *ctx, DevBuf &b, size_t bytes, bool zero = false) {
   if (b.cap >= bytes) return PBF_OK;
-  void *np = nullptr;
-  const size_t want = bytes + bytes / 4 + 256;
-  HIPCHK(ctx, hipMalloc(&np, want));
+  DevBuf fresh;
+  fresh.cap = bytes + bytes / 4 + 256;
+  HIPCHK(ctx, hipMalloc(&fresh.p, fresh.cap));
   ctx->allocEpoch++;
-  if (zero) HIPCHK(ctx, hipMemsetAsync(np, 0, want, ctx->stream));
+  if (zero) HIPCHK(ctx, hipMemsetAsync(fresh.p, 0, fresh.cap, ctx->stream));
   if (b.p) {
     // contents are never carried across a grow: callers refill
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipFree(b.p));
+    HIPCHK(ctx, b.reset());
   }
-  b.p = np;
-  b.cap = want;
+  b = std::move(fresh);
   return PBF_OK;
 }
+
+// what an observer left at order epoch `madeAt` (pbf_ctx::orderEpoch) still describes the arrays: pbf_read_buffer may hand it out
+bool record_current(const pbf_ctx *ctx, uint64_t madeAt) { return madeAt == ctx->orderEpoch && ctx->st.sorted; }
 
 template <typename N> size_t vsz() { return sizeof(vec4<N>); }
 
@@ -402,11 +470,9 @@ int ensure_table(pbf_ctx *ctx, uint32_t tableN) {
   const size_t entries = size_t(tableN) + 2;  // buckets 0..tableN (+1 overflow) and the closing total
   if (ctx->tableCap >= entries) return PBF_OK;
   // count must start (and, by the atomicSub in k_scatter_slots, always returns to) all-zero
-  ctx->count.cap = 0;
   if (ctx->count.p) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipFree(ctx->count.p));
-    ctx->count.p = nullptr;
+    HIPCHK(ctx, ctx->count.reset());
   }
   if (int rc = ensure(ctx, ctx->count, (entries + SCAN_TILE) * 4, true)) return rc;
   if (int rc = ensure(ctx, ctx->table, (entries + SCAN_TILE) * 4)) return rc;
@@ -474,6 +540,10 @@ inline dim3 grid_for(size_t n) { return dim3(unsigned(std::max<size_t>(1, (n + B
     }                                                                      \
   } while (0)
 
+// the precision the context was created with, and (DISPATCH_FAST, inside a function templated on N) PBF_FLAG_FAST_MATH
+#define DISPATCH(ctx, fn, ...) ((ctx)->fp64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
+#define DISPATCH_FAST(ctx, fn, ...) ((ctx)->fast ? fn<N, true>(__VA_ARGS__) : fn<N, false>(__VA_ARGS__))
+
 int upload_wells(pbf_ctx *ctx, const pbf_params *p) {
   if (p->n_wells <= 0) return PBF_OK;
   if (!p->wells) return fail(ctx, PBF_ERR_INVALID, "n_wells > 0 but wells == NULL");
@@ -509,6 +579,14 @@ int wait_for_word(pbf_ctx *ctx, const volatile uint32_t *word, uint32_t seq, con
       }
     }
   }
+}
+// the mailbox's round is in: `out` is the front of its record (read through a plain pointer, hence the fence after the polled word)
+template <typename T, typename Out> int receive(pbf_ctx *ctx, const Mailbox<T> &box, const char *what, Out &out) {
+  static_assert(sizeof(Out) <= offsetof(T, seq), "the record ends with the polled word");
+  if (int rc = wait_for_word(ctx, &box.rec.p->seq, box.seq, what)) return rc;
+  std::atomic_thread_fence(std::memory_order_acquire);
+  std::memcpy(&out, box.rec.p, sizeof(Out));
+  return PBF_OK;
 }
 
 // ---- stages ------------------------------------------------------------------------------------
@@ -633,8 +711,7 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   ctx->n = nLive;
   ctx->gatherSeq = 0;  // (fresh tickets)
   ctx->st.sorted_now(rows, rowDiffuse);
-  ctx->diagDensityValid = false;  // (a new order: the last density pass describes the old one)
-  ctx->wwPotValid = false;
+  ctx->orderEpoch++;  // (a new order: what the observers left describes the old one)
   if (!rowDiffuse) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
   return PBF_OK;
 }
@@ -945,7 +1022,7 @@ template <typename N, bool FAST> int lambda_impl(pbf_ctx *ctx, const pbf_params 
   return PBF_OK;
 }
 template <typename N> int stage_lambda(pbf_ctx *ctx, const pbf_params *p, bool fuseDiffuse = false) {
-  return ctx->fast ? lambda_impl<N, true>(ctx, p, fuseDiffuse) : lambda_impl<N, false>(ctx, p, fuseDiffuse);
+  return DISPATCH_FAST(ctx, lambda_impl, ctx, p, fuseDiffuse);
 }
 
 template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
@@ -977,7 +1054,7 @@ template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *
   return rc;
 }
 template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
-  return ctx->fast ? delta_impl<N, true>(ctx, p) : delta_impl<N, false>(ctx, p);
+  return DISPATCH_FAST(ctx, delta_impl, ctx, p);
 }
 
 // Opt-in extras (pbf_params.vorticity / .xsph, pbf_set_surface_tension), absent from the reference: see VorticityOp /
@@ -1066,7 +1143,7 @@ template <typename N> int extras(pbf_ctx *ctx, const pbf_params *p, const StepCo
   if (ctx->slabActive && surface_on(ctx))
     return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_set_surface_tension(ctx, 0, 0) turns it off)");
   if (ctx->slabActive) return PBF_OK;  // slab mode: pbf_slab_step runs them itself, with the ghost refreshes in between
-  return ctx->fast ? extras_impl<N, true>(ctx, p, c) : extras_impl<N, false>(ctx, p, c);
+  return DISPATCH_FAST(ctx, extras_impl, ctx, p, c);
 }
 
 template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
@@ -1143,20 +1220,16 @@ template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
   if (ctx->drains.empty()) return PBF_OK;
   const uint32_t n = uint32_t(ctx->n), nb = (n + DRAIN_TILE - 1) / DRAIN_TILE, nd = uint32_t(ctx->drains.size());
   if (int rc = ensure(ctx, ctx->drainCounts, (ctx->cap / DRAIN_TILE + 2) * 4)) return rc;
-  if (!ctx->hostScene) {
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostScene), 64, hipHostMallocDefault));
-    std::memset(ctx->hostScene, 0, 64);
-  }
+  uint32_t seq, kept;
+  HIPCHK(ctx, ctx->hostScene.arm(seq));
   const SceneDrain<N> *drains = ctx->sceneDrains.as<const SceneDrain<N>>();
   uint32_t *counts = ctx->drainCounts.as<uint32_t>();
-  const uint32_t seq = ++ctx->sceneSeq ? ctx->sceneSeq : ++ctx->sceneSeq;  // (never 0: the pinned word starts there)
   hipLaunchKernelGGL((k_drain_count<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pos4[s].as<const vec4<N>>(),
                      ctx->type[s].as<const uint8_t>(), drains, nd, counts);
-  hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, counts, ctx->hostScene, seq);
+  hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, counts, &ctx->hostScene.rec.p->kept, seq);
   LAUNCH_CHECK(ctx);
-  if (int rc = wait_for_word(ctx, ctx->hostScene + 1, seq, "drain read-back")) return rc;
+  if (int rc = receive(ctx, ctx->hostScene, "drain read-back", kept)) return rc;
   ctx->sceneHostSyncs++;
-  const uint32_t kept = static_cast<volatile uint32_t *>(ctx->hostScene)[0];
   if (kept > n) return fail(ctx, PBF_ERR_HIP, "drain read-back: more survivors than particles");
   if (kept == n) return PBF_OK;
   if (kept) {
@@ -1200,6 +1273,26 @@ int check(pbf_ctx *ctx, const pbf_params *p, bool needSorted) {
   ctx->haveParams = true;
   return PBF_OK;
 }
+
+// What the observers of the last step (entry point `who`) refuse alike.  Each entry point asks for the parts in its own,
+// documented order, between the refusals that are its alone.
+struct Refuse {
+  pbf_ctx *ctx;
+  const char *who;
+  int params(const pbf_params *p) const {
+    if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+    return PBF_OK;
+  }
+  int slab_mode() const {
+    if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
+      return fail(ctx, PBF_ERR_STATE, std::string(who) + " is not supported in slab mode");
+    return PBF_OK;
+  }
+  int no_step(const char *part = "") const {  // the keys and the table it reads are the last sort's
+    if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, std::string(who) + part + " needs a step first (no valid cell table)");
+    return PBF_OK;
+  }
+};
 
 int drop_ghosts(pbf_ctx *ctx);  // (defined with the slab code)
 
@@ -1266,8 +1359,6 @@ int download_impl(pbf_ctx *ctx, uint64_t *id, uint8_t *type, N *mass, N *pos, N 
 }
 
 }  // namespace
-
-#define DISPATCH(ctx, fn, ...) ((ctx)->fp64 ? fn<double>(__VA_ARGS__) : fn<float>(__VA_ARGS__))
 
 extern "C" {
 
@@ -1409,20 +1500,6 @@ void pbf_destroy(pbf_ctx *ctx) {
     (void)hipEventDestroy(ep.b);
   }
   for (auto ev : ctx->freeEvents) (void)hipEventDestroy(ev);
-  DevBuf *all[] = {&ctx->pos4[0], &ctx->pos4[1], &ctx->vel4[0], &ctx->vel4[1], &ctx->col4[0],  &ctx->col4[1],
-                   &ctx->id[0],   &ctx->id[1],   &ctx->type[0], &ctx->type[1], &ctx->key[0],   &ctx->key[1],
-                   &ctx->pstar[0], &ctx->pstar[1], &ctx->pstar[2], &ctx->count, &ctx->table,   &ctx->blockSums,
-                   &ctx->permTmp, &ctx->wells,   &ctx->staging, &ctx->bricks, &ctx->brickCtl, &ctx->bigCells,
-                   &ctx->latticePN, &ctx->latticeC, &ctx->mcCounts, &ctx->mcOffsets, &ctx->mcSums, &ctx->mcNear, &ctx->mcEdgeWord, &ctx->mcEdgeOffsets, &ctx->mcEdgeSums, &ctx->meshT, &ctx->meshV, &ctx->meshN,
-                   &ctx->meshC, &ctx->qpos, &ctx->nbrList, &ctx->nbrCount, &ctx->rowPstar[0], &ctx->rowPstar[1], &ctx->rowMass, &ctx->rowQpos, &ctx->rowXYZ, &ctx->rowType, &ctx->rowSlotOf, &ctx->rowCol, &ctx->rowMortonOf, &ctx->rowSegs, &ctx->linCount, &ctx->linTable, &ctx->linSums, &ctx->slotOf,  &ctx->selCounts, &ctx->selTotals, &ctx->ghostSrcL, &ctx->ghostSrcR, &ctx->colHist, &ctx->wireSend[0], &ctx->wireSend[1], &ctx->wireRecv[0], &ctx->wireRecv[1], &ctx->wireGhost[0], &ctx->wireGhost[1], &ctx->diffSum, &ctx->diffCnt, &ctx->surfA, &ctx->surfB,
-                   &ctx->sceneSources, &ctx->sceneDrains, &ctx->drainCounts, &ctx->queryPoints, &ctx->queryCounts,
-                   &ctx->queryIds, &ctx->diagRho, &ctx->diagNbr, &ctx->diagPartials, &ctx->samplePoints, &ctx->sampleOut,
-                   &ctx->wwPos[0], &ctx->wwPos[1], &ctx->wwVel[0], &ctx->wwVel[1], &ctx->wwKind[0], &ctx->wwKind[1],
-                   &ctx->wwParent[0], &ctx->wwParent[1], &ctx->wwSample, &ctx->wwAlive, &ctx->wwAliveOff, &ctx->wwSums,
-                   &ctx->wwFieldA, &ctx->wwFieldB, &ctx->wwPot, &ctx->wwEmit, &ctx->wwOffset, &ctx->wwChildKind,
-                   &ctx->anisoOut};
-  for (DevBuf *b : all)
-    if (b->p) (void)hipFree(b->p);
   for (auto &g : ctx->graphs)
     if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
   if (ctx->evFork) (void)hipEventDestroy(ctx->evFork);
@@ -1430,13 +1507,10 @@ void pbf_destroy(pbf_ctx *ctx) {
   if (ctx->sideStream) (void)hipStreamDestroy(ctx->sideStream);
   if (ctx->copyStream) (void)hipStreamDestroy(ctx->copyStream);
   if (ctx->evPacked) (void)hipEventDestroy(ctx->evPacked);
-  if (ctx->hostCounts) (void)hipHostFree(ctx->hostCounts);
-  if (ctx->hostScene) (void)hipHostFree(ctx->hostScene);
-  if (ctx->hostDiag) (void)hipHostFree(ctx->hostDiag);
-  if (ctx->hostWw) (void)hipHostFree(ctx->hostWw);
-  if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
   if (ctx->regPtr) (void)hipHostUnregister(ctx->regPtr);
   if (ctx->ownStream) (void)hipStreamDestroy(ctx->stream);
+  // every DevBuf and Pinned frees itself here: this device is current and the stream has drained (the side stream's work was
+  // joined into it by the step that started it, the copy stream's by the download ended above)
   delete ctx;
 }
 
@@ -1611,8 +1685,7 @@ StepState snapshot(pbf_ctx *ctx) {
 void restore(pbf_ctx *ctx, const StepState &s) {
   ctx->st = s.st, ctx->hasObstacles = s.hasObstacles;  // (all of the derived state, not only what the key compares)
   ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
-  ctx->diagDensityValid = false;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
-  ctx->wwPotValid = false;
+  ctx->orderEpoch++;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
@@ -1846,30 +1919,24 @@ template <typename N> int diagnostics_impl(pbf_ctx *ctx, const pbf_params *p, bo
   if (density)
     if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_diagnostics")) return rc;
   if (int rc = ensure_diag(ctx, /*first=*/true, density)) return rc;
-  if (!ctx->hostDiag) {
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostDiag), sizeof(DiagRecord), hipHostMallocDefault));
-    std::memset(ctx->hostDiag, 0, sizeof(DiagRecord));
-  }
+  uint32_t seq;
+  HIPCHK(ctx, ctx->hostDiag.arm(seq));
   const int s = ctx->st.cur;
   const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
   if (density && n) {
     if (int rc = materialise_pstar<N>(ctx)) return rc;
-    if (int rc = ctx->fast ? density_pass<N, true>(ctx, c) : density_pass<N, false>(ctx, c)) return rc;
-    ctx->diagDensityValid = true;
+    if (int rc = DISPATCH_FAST(ctx, density_pass, ctx, c)) return rc;
+    ctx->diagRhoAt = ctx->orderEpoch;
   }
   if (nb)
     hipLaunchKernelGGL((k_diag_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pos4[s].as<const vec4<N>>(),
                        ctx->vel4[s].as<const vec4<N>>(), ctx->type[s].as<const uint8_t>(),
                        density ? ctx->diagRho.as<const N>() : static_cast<const N *>(nullptr),
                        ctx->diagNbr.as<const uint32_t>(), ctx->diagPartials.as<DiagPartial>());
-  const uint32_t seq = ++ctx->diagSeq ? ctx->diagSeq : ++ctx->diagSeq;  // (never 0: the pinned word starts there)
   hipLaunchKernelGGL(k_diag_final, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->diagPartials.as<const DiagPartial>(),
-                     ctx->hostDiag, seq);
+                     ctx->hostDiag.rec.p, seq);
   LAUNCH_CHECK(ctx);
-  if (int rc = wait_for_word(ctx, &ctx->hostDiag->seq, seq, "diagnostics read-back")) return rc;
-  std::atomic_thread_fence(std::memory_order_acquire);  // (the record is read through a plain pointer, after the polled word)
-  std::memcpy(out, ctx->hostDiag, sizeof(pbf_diag));
-  return PBF_OK;
+  return receive(ctx, ctx->hostDiag, "diagnostics read-back", *out);
 }
 
 template <typename N>
@@ -1905,6 +1972,35 @@ struct SampleLatticeDesc {
   double origin[3], spacing[3];
   uint64_t dims[3];
 };
+// An observer's SoA outputs as planes of ONE device allocation, each 256-byte aligned: add() them all, allocate `bytes`, set
+// `base`; then at() is a plane's address and back() copies a plane into the caller's array if it asked for one.
+struct Planes {
+  size_t bytes = 0;
+  char *base = nullptr;
+  size_t add(size_t n) {
+    const size_t here = bytes;
+    bytes += (n + 255) / 256 * 256;
+    return here;
+  }
+  template <typename T> T *at(size_t plane) const { return reinterpret_cast<T *>(base + plane); }
+  hipError_t back(void *host, size_t plane, size_t n, hipStream_t stream) const {
+    return host ? hipMemcpyAsync(host, base + plane, n, hipMemcpyDeviceToHost, stream) : hipSuccess;
+  }
+};
+// k_sample's outputs for up to `n` points of `esz`-byte elements, in SampleOut's order; `colour`: mc among them
+struct SamplePlanes : Planes {
+  size_t rho, weight, mv, mc, count, outside;
+  bool colour;
+  SamplePlanes(size_t n, size_t esz, bool withColour) : colour(withColour) {
+    rho = add(n * esz), weight = add(n * esz), mv = add(3 * n * esz), mc = colour ? add(4 * n * esz) : 0;
+    count = add(2 * n * 4), outside = add(n);
+  }
+  template <typename N> SampleOut<N> in(const DevBuf &b) {
+    base = b.as<char>();
+    return SampleOut<N>{at<N>(rho), at<N>(weight), at<N>(mv), colour ? at<N>(mc) : nullptr, at<uint32_t>(count),
+                        at<uint8_t>(outside)};
+  }
+};
 template <typename N, bool FAST, typename Source>
 int launch_sample(pbf_ctx *ctx, const StepConsts<N> &c, const Source &src, uint64_t threads, uint32_t what,
                   const SampleOut<N> &out) {
@@ -1931,16 +2027,8 @@ int sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *point
                 const pbf_sample_out *o, const char *who) {
   StepConsts<N> c;
   if (int rc = consts_on_last_grid<N>(ctx, p, c, who)) return rc;
-  // the outputs' places in the one allocation, each 256-byte aligned
-  size_t at = 0;
-  auto place = [&](size_t bytes) {
-    const size_t here = at;
-    at += (bytes + 255) / 256 * 256;
-    return here;
-  };
-  const size_t oRho = place(n * sizeof(N)), oWeight = place(n * sizeof(N)), oMv = place(3 * n * sizeof(N)),
-               oMc = place(4 * n * sizeof(N)), oCount = place(2 * n * 4), oOutside = place(n);
-  if (int rc = ensure(ctx, ctx->sampleOut, at)) return rc;
+  SamplePlanes l(n, sizeof(N), /*withColour=*/true);
+  if (int rc = ensure(ctx, ctx->sampleOut, l.bytes)) return rc;
   std::vector<N> pts;
   if (points) {
     pts.resize(3 * n);
@@ -1949,33 +2037,26 @@ int sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *point
   }
   if (int rc = join_diffuse(ctx)) return rc;
   if (int rc = materialise_pstar<N>(ctx)) return rc;
-  char *base = ctx->sampleOut.as<char>();
-  const SampleOut<N> out{reinterpret_cast<N *>(base + oRho),        reinterpret_cast<N *>(base + oWeight),
-                         reinterpret_cast<N *>(base + oMv),         reinterpret_cast<N *>(base + oMc),
-                         reinterpret_cast<uint32_t *>(base + oCount), reinterpret_cast<uint8_t *>(base + oOutside)};
+  const SampleOut<N> out = l.in<N>(ctx->sampleOut);
   int rc;
   if (points) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->samplePoints.p, pts.data(), pts.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
     const SamplePointSource<N> src{ctx->samplePoints.as<const N>(), uint32_t(n)};
-    rc = ctx->fast ? launch_sample<N, true>(ctx, c, src, n, what, out) : launch_sample<N, false>(ctx, c, src, n, what, out);
+    rc = DISPATCH_FAST(ctx, launch_sample, ctx, c, src, n, what, out);
   } else {
     SampleLatticeSource<N> src;
     for (int a = 0; a < 3; ++a) src.origin[a] = N(lat->origin[a]), src.spacing[a] = N(lat->spacing[a]), src.dims[a] = uint32_t(lat->dims[a]);
     src.by = (src.dims[1] + 3u) / 4u, src.bz = (src.dims[2] + 3u) / 4u;
     const uint64_t waves = uint64_t((src.dims[0] + 3u) / 4u) * src.by * src.bz;  // (at most 2^29: dims' product is below 2^31)
-    rc = ctx->fast ? launch_sample<N, true>(ctx, c, src, waves * 64u, what, out)
-                   : launch_sample<N, false>(ctx, c, src, waves * 64u, what, out);
+    rc = DISPATCH_FAST(ctx, launch_sample, ctx, c, src, waves * 64u, what, out);
   }
   if (rc != PBF_OK) return rc;
-  auto back = [&](void *host, size_t off, size_t bytes) {
-    return host ? hipMemcpyAsync(host, base + off, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  };
-  HIPCHK(ctx, back(o->rho, oRho, n * sizeof(N)));
-  HIPCHK(ctx, back(o->weight, oWeight, n * sizeof(N)));
-  HIPCHK(ctx, back(o->mv, oMv, 3 * n * sizeof(N)));
-  HIPCHK(ctx, back(o->mc, oMc, 4 * n * sizeof(N)));
-  HIPCHK(ctx, back(o->count, oCount, 2 * n * 4));
-  HIPCHK(ctx, back(o->outside, oOutside, n));
+  HIPCHK(ctx, l.back(o->rho, l.rho, n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->weight, l.weight, n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->mv, l.mv, 3 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->mc, l.mc, 4 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->count, l.count, 2 * n * 4, ctx->stream));
+  HIPCHK(ctx, l.back(o->outside, l.outside, n, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pts is a temporary; the caller reads the answers)
   return PBF_OK;
 }
@@ -1983,63 +2064,46 @@ int sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *point
 int sample_check(pbf_ctx *ctx, const pbf_params *p, uint32_t what, const pbf_sample_out *o, const char *who) {
   const std::string w(who);
   if (!p || !o) return fail(ctx, PBF_ERR_INVALID, w + ": NULL argument");
-  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  const Refuse refuse{ctx, who};
+  if (int rc = refuse.params(p)) return rc;
   if (o->mv && !(what & PBF_SAMPLE_VELOCITY)) return fail(ctx, PBF_ERR_INVALID, w + ": mv needs PBF_SAMPLE_VELOCITY");
   if (o->mc && !(what & PBF_SAMPLE_COLOUR)) return fail(ctx, PBF_ERR_INVALID, w + ": mc needs PBF_SAMPLE_COLOUR");
-  // a point near a cut needs both ranks' candidates
-  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
-    return fail(ctx, PBF_ERR_STATE, w + " is not supported in slab mode");
-  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, w + " needs a step first (no valid cell table)");
-  return PBF_OK;
+  if (int rc = refuse.slab_mode()) return rc;  // (a point near a cut needs both ranks' candidates)
+  return refuse.no_step();
 }
 
 // pbf_anisotropy_compute: one AnisotropyOp launch over the final pStar on the last step's keys and table, through whichever
 // gather kernel the ctx is set to.  Like pbf_sample_points it touches nothing a step reads (materialise_pstar apart), takes no
 // ticket word and is never captured; the arrays asked for travel with plain async copies straight into the caller's memory.
+template <typename N, bool FAST>
+int anisotropy_pass(pbf_ctx *ctx, const StepConsts<N> &c, const pbf_anisotropy *g, const pbf_anisotropy_out *o) {
+  // the outputs' planes are sized to the capacity; a plane has n elements
+  const size_t cap = ctx->cap, n = ctx->n;
+  Planes l;
+  const size_t centre = l.add(3 * cap * sizeof(N)), G = l.add(6 * cap * sizeof(N)), axes = l.add(9 * cap * sizeof(N)),
+               radii = l.add(3 * cap * sizeof(N)), nbr = l.add(cap * 4);
+  if (int rc = ensure(ctx, ctx->anisoOut, l.bytes)) return rc;
+  if (int rc = join_diffuse(ctx)) return rc;
+  if (int rc = materialise_pstar<N>(ctx)) return rc;
+  l.base = ctx->anisoOut.as<char>();
+  const int s = ctx->st.cur;
+  const AnisoConsts<N> k{N(g->smoothing), N(g->k_r), N(g->k_s), N(g->k_n), g->min_neighbours};
+  typename AnisotropyOp<N, FAST>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
+                                         ctx->type[s].as<const uint8_t>(), l.at<N>(centre), l.at<N>(G), l.at<N>(axes),
+                                         l.at<N>(radii), l.at<uint32_t>(nbr), k};
+  if (int rc = launch_gather<N, AnisotropyOp<N, FAST>>(ctx, c, a)) return rc;
+  HIPCHK(ctx, l.back(o->centre, centre, 3 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->G, G, 6 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->axes, axes, 9 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->radii, radii, 3 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->neighbours, nbr, n * 4, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
+}
 template <typename N> int anisotropy_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_anisotropy *g, const pbf_anisotropy_out *o) {
   StepConsts<N> c;
   if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_anisotropy_compute")) return rc;
-  // the outputs' places in the one allocation (sized to the capacity), each 256-byte aligned; a plane has n elements
-  const size_t cap = ctx->cap, n = ctx->n;
-  size_t at = 0;
-  auto place = [&](size_t bytes) {
-    const size_t here = at;
-    at += (bytes + 255) / 256 * 256;
-    return here;
-  };
-  const size_t oCentre = place(3 * cap * sizeof(N)), oG = place(6 * cap * sizeof(N)), oAxes = place(9 * cap * sizeof(N)),
-               oRadii = place(3 * cap * sizeof(N)), oNbr = place(cap * 4);
-  if (int rc = ensure(ctx, ctx->anisoOut, at)) return rc;
-  if (int rc = join_diffuse(ctx)) return rc;
-  if (int rc = materialise_pstar<N>(ctx)) return rc;
-  char *base = ctx->anisoOut.as<char>();
-  const int s = ctx->st.cur;
-  const AnisoConsts<N> k{N(g->smoothing), N(g->k_r), N(g->k_s), N(g->k_n), g->min_neighbours};
-  int rc;
-  if (ctx->fast) {
-    typename AnisotropyOp<N, true>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                           ctx->type[s].as<const uint8_t>(), reinterpret_cast<N *>(base + oCentre),
-                                           reinterpret_cast<N *>(base + oG), reinterpret_cast<N *>(base + oAxes),
-                                           reinterpret_cast<N *>(base + oRadii), reinterpret_cast<uint32_t *>(base + oNbr), k};
-    rc = launch_gather<N, AnisotropyOp<N, true>>(ctx, c, a);
-  } else {
-    typename AnisotropyOp<N, false>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                            ctx->type[s].as<const uint8_t>(), reinterpret_cast<N *>(base + oCentre),
-                                            reinterpret_cast<N *>(base + oG), reinterpret_cast<N *>(base + oAxes),
-                                            reinterpret_cast<N *>(base + oRadii), reinterpret_cast<uint32_t *>(base + oNbr), k};
-    rc = launch_gather<N, AnisotropyOp<N, false>>(ctx, c, a);
-  }
-  if (rc != PBF_OK) return rc;
-  auto back = [&](void *host, size_t off, size_t bytes) {
-    return host ? hipMemcpyAsync(host, base + off, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  };
-  HIPCHK(ctx, back(o->centre, oCentre, 3 * n * sizeof(N)));
-  HIPCHK(ctx, back(o->G, oG, 6 * n * sizeof(N)));
-  HIPCHK(ctx, back(o->axes, oAxes, 9 * n * sizeof(N)));
-  HIPCHK(ctx, back(o->radii, oRadii, 3 * n * sizeof(N)));
-  HIPCHK(ctx, back(o->neighbours, oNbr, n * 4));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return PBF_OK;
+  return DISPATCH_FAST(ctx, anisotropy_pass, ctx, c, g, o);
 }
 
 // pbf_whitewater_*: see csrc/pbf_whitewater.hpp for the passes.  Like pbf_diagnostics it reads what the last step left and
@@ -2063,32 +2127,11 @@ template <typename N> WwConsts<N> ww_consts(const pbf_ctx *ctx) {
   return w;
 }
 // the pool's own buffers, sized to its capacity (pbf_whitewater_configure); k_sample's SoA outputs in one allocation
-struct WwSampleLayout {
-  size_t rho, weight, mv, count, outside, bytes;
-};
-WwSampleLayout ww_sample_layout(size_t cap, size_t esz) {
-  WwSampleLayout l{};
-  size_t at = 0;
-  auto place = [&](size_t bytes) {
-    const size_t here = at;
-    at += (bytes + 255) / 256 * 256;
-    return here;
-  };
-  l.rho = place(cap * esz), l.weight = place(cap * esz), l.mv = place(3 * cap * esz), l.count = place(2 * cap * 4);
-  l.outside = place(cap), l.bytes = at;
-  return l;
-}
-int release(pbf_ctx *ctx, DevBuf &b) {
-  if (b.p) HIPCHK(ctx, hipFree(b.p));
-  b.p = nullptr, b.cap = 0;
-  return PBF_OK;
-}
 int ww_resize_pool(pbf_ctx *ctx, size_t cap) {
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   DevBuf *pool[] = {&ctx->wwPos[0], &ctx->wwPos[1], &ctx->wwVel[0], &ctx->wwVel[1], &ctx->wwKind[0], &ctx->wwKind[1],
                     &ctx->wwParent[0], &ctx->wwParent[1], &ctx->wwSample, &ctx->wwAlive, &ctx->wwAliveOff, &ctx->wwSums};
-  for (DevBuf *b : pool)
-    if (int rc = release(ctx, *b)) return rc;
+  for (DevBuf *b : pool) HIPCHK(ctx, b->reset());
   ctx->wwCount = 0, ctx->wwCur = 0;
   if (!cap) return PBF_OK;
   const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4), esz = v / 4;
@@ -2098,7 +2141,7 @@ int ww_resize_pool(pbf_ctx *ctx, size_t cap) {
     if (int rc = ensure(ctx, ctx->wwKind[s], cap)) return rc;
     if (int rc = ensure(ctx, ctx->wwParent[s], cap * 8)) return rc;
   }
-  if (int rc = ensure(ctx, ctx->wwSample, ww_sample_layout(cap, esz).bytes)) return rc;
+  if (int rc = ensure(ctx, ctx->wwSample, SamplePlanes(cap, esz, /*withColour=*/false).bytes)) return rc;
   if (int rc = ensure(ctx, ctx->wwAlive, (cap + SCAN_TILE) * 4)) return rc;
   return ensure(ctx, ctx->wwAliveOff, (cap + SCAN_TILE) * 4);
 }
@@ -2111,11 +2154,7 @@ template <typename N, bool FAST> int whitewater_passes(pbf_ctx *ctx, const StepC
   uint32_t *alive = ctx->wwAlive.as<uint32_t>(), *aliveOff = ctx->wwAliveOff.as<uint32_t>();
   uint32_t *emit = ctx->wwEmit.as<uint32_t>(), *offset = ctx->wwOffset.as<uint32_t>();
   if (m) {  // 1: advect what is in the pool on the state the last step left
-    const WwSampleLayout l = ww_sample_layout(cap, sizeof(N));
-    char *base = ctx->wwSample.as<char>();
-    const SampleOut<N> out{reinterpret_cast<N *>(base + l.rho), reinterpret_cast<N *>(base + l.weight),
-                           reinterpret_cast<N *>(base + l.mv),  nullptr,
-                           reinterpret_cast<uint32_t *>(base + l.count), reinterpret_cast<uint8_t *>(base + l.outside)};
+    const SampleOut<N> out = SamplePlanes(cap, sizeof(N), /*withColour=*/false).in<N>(ctx->wwSample);
     const WwPoolSource<N> from{src.pos4, m};
     if (int rc = launch_sample<N, FAST>(ctx, c, from, m, SAMPLE_VELOCITY, out)) return rc;
     hipLaunchKernelGGL((k_ww_advect<N>), grid_for(m), dim3(BLOCK), 0, ctx->stream, c, w, m, src, out.weight, out.mv, out.count,
@@ -2154,7 +2193,7 @@ template <typename N, bool FAST> int whitewater_passes(pbf_ctx *ctx, const StepC
                        ctx->vel4[s].as<const vec4<N>>(), ctx->id[s].as<const uint64_t>(), ctx->wwPot.as<const vec4<N>>(), emit,
                        offset, ctx->wwChildKind.as<const uint8_t>(), m, alive, aliveOff, cap, dst);
   hipLaunchKernelGGL(k_ww_final, dim3(1), dim3(BLOCK), 0, ctx->stream, n, emit, offset, m, alive, aliveOff, cap, dst.kind,
-                     ctx->hostWw, seq);
+                     ctx->hostWw.rec.p, seq);
   LAUNCH_CHECK(ctx);
   return PBF_OK;
 }
@@ -2164,20 +2203,15 @@ template <typename N> int whitewater_step_impl(pbf_ctx *ctx, const pbf_params *p
   if (int rc = ensure_whitewater_fields(ctx)) return rc;
   const size_t nbSums = (ctx->cap + SCAN_TILE - 1) / SCAN_TILE + (size_t(ctx->ww.capacity) + SCAN_TILE - 1) / SCAN_TILE + 2;
   if (int rc = ensure(ctx, ctx->wwSums, nbSums * 4)) return rc;
-  if (!ctx->hostWw) {
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostWw), sizeof(WwRecord), hipHostMallocDefault));
-    std::memset(ctx->hostWw, 0, sizeof(WwRecord));
-  }
+  uint32_t seq;
+  HIPCHK(ctx, ctx->hostWw.arm(seq));
   if (int rc = join_diffuse(ctx)) return rc;
   if (int rc = materialise_pstar<N>(ctx)) return rc;
-  const uint32_t seq = ++ctx->wwSeq ? ctx->wwSeq : ++ctx->wwSeq;  // (never 0: the pinned word starts there)
-  if (int rc = ctx->fast ? whitewater_passes<N, true>(ctx, c, seq) : whitewater_passes<N, false>(ctx, c, seq)) return rc;
-  if (int rc = wait_for_word(ctx, &ctx->hostWw->seq, seq, "whitewater read-back")) return rc;
-  std::atomic_thread_fence(std::memory_order_acquire);
+  if (int rc = DISPATCH_FAST(ctx, whitewater_passes, ctx, c, seq)) return rc;
   pbf_whitewater_stats st;
-  std::memcpy(&st, ctx->hostWw, sizeof(st));
+  if (int rc = receive(ctx, ctx->hostWw, "whitewater read-back", st)) return rc;
   ctx->wwCount = size_t(st.alive), ctx->wwCur = 1 - ctx->wwCur, ctx->wwFrame++;
-  ctx->wwPotValid = ctx->n != 0;
+  ctx->wwPotAt = ctx->n ? ctx->orderEpoch : 0;
   if (out) *out = st;
   return PBF_OK;
 }
@@ -2274,9 +2308,9 @@ uint64_t pbf_scene_host_syncs(const pbf_ctx *ctx) { return ctx ? ctx->sceneHostS
 int pbf_query_cells(pbf_ctx *ctx, const pbf_params *p, size_t n_points, const double *points, uint32_t *counts, uint64_t *ids,
                     size_t cap_per_point) {
   if (int rc = check(ctx, p, false)) return rc;
-  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
-    return fail(ctx, PBF_ERR_STATE, "pbf_query_cells is not supported in slab mode");
-  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_query_cells needs a step first (no valid cell table)");
+  const Refuse refuse{ctx, "pbf_query_cells"};
+  if (int rc = refuse.slab_mode()) return rc;
+  if (int rc = refuse.no_step()) return rc;
   if (n_points == 0) return PBF_OK;
   if (!points || !counts || (cap_per_point && !ids)) return fail(ctx, PBF_ERR_INVALID, "pbf_query_cells: NULL argument");
   if (n_points >= (size_t(1) << 31) || cap_per_point >= (size_t(1) << 31))
@@ -2292,12 +2326,13 @@ int pbf_diagnostics(pbf_ctx *ctx, const pbf_params *p, uint32_t what, pbf_diag *
   if (what & ~uint32_t(PBF_DIAG_DENSITY)) return fail(ctx, PBF_ERR_INVALID, "pbf_diagnostics: unknown bits in `what`");
   const bool density = (what & PBF_DIAG_DENSITY) != 0;
   if (density && !p) return fail(ctx, PBF_ERR_INVALID, "pbf_diagnostics: PBF_DIAG_DENSITY needs params");
-  if (density && (!(p->scale > 0) || !(p->dt > 0))) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  const Refuse refuse{ctx, "pbf_diagnostics"};
+  if (density)
+    if (int rc = refuse.params(p)) return rc;
   // global sums would need an all-reduce, and the copies of the neighbours' boundary columns would have to be left out
-  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
-    return fail(ctx, PBF_ERR_STATE, "pbf_diagnostics is not supported in slab mode");
-  if (density && !ctx->st.sorted)
-    return fail(ctx, PBF_ERR_STATE, "pbf_diagnostics: the density part needs a step first (no valid cell table)");
+  if (int rc = refuse.slab_mode()) return rc;
+  if (density)
+    if (int rc = refuse.no_step(": the density part")) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return DISPATCH(ctx, diagnostics_impl, ctx, p, density, out);
 }
@@ -2338,16 +2373,16 @@ int pbf_sample_lattice(pbf_ctx *ctx, const pbf_params *p, const double origin[3]
 int pbf_anisotropy_compute(pbf_ctx *ctx, const pbf_params *p, const pbf_anisotropy *g, const pbf_anisotropy_out *out) {
   if (!ctx) return PBF_ERR_INVALID;
   if (!p || !g || !out) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: NULL argument");
-  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  const Refuse refuse{ctx, "pbf_anisotropy_compute"};
+  if (int rc = refuse.params(p)) return rc;
   if (!(g->smoothing >= 0 && g->smoothing <= 1)) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: smoothing must lie in [0, 1]");
   if (!(g->k_r >= 1) || !std::isfinite(g->k_r)) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: k_r must be finite and >= 1");
   if (!(g->k_s > 0) || !std::isfinite(g->k_s) || !(g->k_n > 0) || !std::isfinite(g->k_n))
     return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: k_s and k_n must be finite and > 0");
   // a particle near a cut needs both ranks' candidates, and the copies of the neighbours' columns would have to be left out
-  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
-    return fail(ctx, PBF_ERR_STATE, "pbf_anisotropy_compute is not supported in slab mode");
+  if (int rc = refuse.slab_mode()) return rc;
   if (ctx->n == 0) return PBF_OK;
-  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_anisotropy_compute needs a step first (no valid cell table)");
+  if (int rc = refuse.no_step()) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return DISPATCH(ctx, anisotropy_impl, ctx, p, g, out);
 }
@@ -2364,7 +2399,7 @@ int pbf_whitewater_configure(pbf_ctx *ctx, const pbf_whitewater *config) {
   ctx->ww = *config, ctx->wwFrame = 0;
   ctx->wwOn = config->capacity != 0;
   if (!ctx->wwOn) {
-    ctx->wwPotValid = false;
+    ctx->wwPotAt = 0;
     return PBF_OK;
   }
   return ensure_whitewater_fields(ctx);
@@ -2383,12 +2418,12 @@ int pbf_whitewater_upload(pbf_ctx *ctx, size_t n, const void *pos, const void *v
 int pbf_whitewater_step(pbf_ctx *ctx, const pbf_params *p, pbf_whitewater_stats *out) {
   if (!ctx) return PBF_ERR_INVALID;
   if (!p) return fail(ctx, PBF_ERR_INVALID, "pbf_whitewater_step: params == NULL");
-  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  const Refuse refuse{ctx, "pbf_whitewater_step"};
+  if (int rc = refuse.params(p)) return rc;
   // a diffuse particle near a cut needs both ranks' candidates, and the pool would have to migrate with the fluid
-  if (ctx->comm || ctx->slabActive || ctx->ghostsPending || ctx->slabConfigured)
-    return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_step is not supported in slab mode");
+  if (int rc = refuse.slab_mode()) return rc;
   if (!ctx->wwOn) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_step: not configured (pbf_whitewater_configure)");
-  if (!ctx->st.sorted) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_step needs a step first (no valid cell table)");
+  if (int rc = refuse.no_step()) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return DISPATCH(ctx, whitewater_step_impl, ctx, p, out);
 }
@@ -2431,12 +2466,12 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
       src = ctx->surfB.p, avail = std::min(ctx->n * v, ctx->surfB.cap);
       break;
     case PBF_BUF_WHITEWATER:
-      if (!ctx->wwPotValid || !ctx->st.sorted)
+      if (!record_current(ctx, ctx->wwPotAt))
         return fail(ctx, PBF_ERR_STATE, "no whitewater step since the arrays last changed (pbf_whitewater_step)");
       src = ctx->wwPot.p, avail = std::min(ctx->n * v, ctx->wwPot.cap);
       break;
     case PBF_BUF_DENSITY:
-      if (!ctx->diagDensityValid || !ctx->st.sorted)
+      if (!record_current(ctx, ctx->diagRhoAt))
         return fail(ctx, PBF_ERR_STATE, "no density pass since the arrays last changed (pbf_diagnostics with PBF_DIAG_DENSITY)");
       src = ctx->diagRho.p, avail = std::min(ctx->n * (v / 4), ctx->diagRho.cap);
       break;
@@ -2826,7 +2861,7 @@ template <typename N, bool FAST> int slab_extras_impl(pbf_ctx *ctx, const pbf_pa
 }
 
 // Spin on the pinned word k_slab_counts writes last (wait_for_word).
-int wait_for_counts(pbf_ctx *ctx, uint32_t seq) { return wait_for_word(ctx, ctx->hostCounts + 7, seq, "slab read-back"); }
+int wait_for_counts(pbf_ctx *ctx, uint32_t seq) { return wait_for_word(ctx, ctx->hostCounts.p + 7, seq, "slab read-back"); }
 
 // One step of the slab protocol, everything on the solver's stream (round 3: ONE select pass, no compaction, no
 // re-histogram, finalise + predict fused between the steps of one pbf_slab_steps call):
@@ -2860,7 +2895,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = ensure(ctx, ctx->ghostSrcL, size_t(ctx->wireCap) * 4)) return rc;
   if (int rc = ensure(ctx, ctx->ghostSrcR, size_t(ctx->wireCap) * 4)) return rc;
   uint32_t *counts = ctx->selCounts.as<uint32_t>(), *tot = ctx->selTotals.as<uint32_t>();
-  volatile uint32_t *h = ctx->hostCounts;
+  volatile uint32_t *h = ctx->hostCounts.p;
   // ---- the select: one pass for both rounds --------------------------------------------------------------------
   hipLaunchKernelGGL(k_slab_count, dim3(nb), dim3(BLOCK), 0, ctx->stream, nPrev, sc, ctx->key[a].as<const uint32_t>(),
                      ctx->type[a].as<const uint8_t>(), nb, counts);
@@ -2956,7 +2991,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
   }
   if (int rc = stage_finalise<N>(ctx, p)) return rc;
   if (extras_on(ctx, p))  // (surface tension is refused by pbf_slab_steps before anything runs)
-    if (int rc = ctx->fast ? slab_extras_impl<N, true>(ctx, p) : slab_extras_impl<N, false>(ctx, p)) return rc;
+    if (int rc = DISPATCH_FAST(ctx, slab_extras_impl, ctx, p)) return rc;
   if (int rc = join_diffuse(ctx)) return rc;
   // The copies stay where they are: the next step's predict marks them dead and its sort drops them; whoever looks at
   // the arrays from outside calls drop_ghosts() first.
@@ -3074,10 +3109,7 @@ int pbf_slab_attach(pbf_ctx *ctx, pbf_comm *comm, const uint32_t *cuts, uint32_t
     if (int rc = ensure(ctx, ctx->wireRecv[k], bytes)) return rc;
     if (int rc = ensure(ctx, ctx->wireGhost[k], bytes)) return rc;
   }
-  if (!ctx->hostCounts) {
-    HIPCHK(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->hostCounts), 64, hipHostMallocDefault));
-    std::memset(ctx->hostCounts, 0, 64);
-  }
+  HIPCHK(ctx, ctx->hostCounts.ensure(16));
   return pbf_slab_set_cuts(ctx, cuts);
 }
 
@@ -3268,6 +3300,39 @@ int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uin
   return PBF_OK;
 }
 
+// The last mesh's arrays, as (device buffer, bytes) parts in the order the caller names them.
+struct MeshPart {
+  const DevBuf *dev;
+  size_t bytes;
+};
+// each part the caller asked for, straight into its array
+int download_mesh_parts(pbf_ctx *ctx, std::initializer_list<MeshPart> parts, void *const *host) {
+  for (const MeshPart &part : parts)
+    if (void *to = *host++) HIPCHK(ctx, hipMemcpyAsync(to, part.dev->p, part.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
+}
+// the parts staged once per surface, back to back in the pinned buffer (grown when they do not fit); at[k]: where part k begins
+int map_mesh_parts(pbf_ctx *ctx, std::initializer_list<MeshPart> parts, const void **at) {
+  size_t total = 0;
+  for (const MeshPart &part : parts) total += part.bytes;
+  if (ctx->meshHost.count < total) {
+    HIPCHK(ctx, ctx->meshHost.ensure(total + total / 4 + 4096, /*zero=*/false));
+    ctx->meshStaged = false;
+  }
+  char *h = ctx->meshHost.p;
+  for (const MeshPart &part : parts) {
+    if (!ctx->meshStaged) HIPCHK(ctx, hipMemcpyAsync(h, part.dev->p, part.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    *at++ = h, h += part.bytes;
+  }
+  // (one wait behind all the parts: handing the arrays out one by one, an event behind each, so that the caller's copy of the
+  // vertices overlaps the normals' DMA was measured — no faster at 0.75 M vertices, 11 % slower at 1.35 M: the host copies
+  // and the DMA share the memory system)
+  if (!ctx->meshStaged) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->meshStaged = true;
+  return PBF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3298,12 +3363,9 @@ int pbf_download_mesh_indexed(pbf_ctx *ctx, void *vs, void *ns, void *cs, uint32
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t nv = ctx->mcVertices, nt = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
   if (nt == 0) return PBF_OK;
-  if (vs) HIPCHK(ctx, hipMemcpyAsync(vs, ctx->meshV.p, nv * 3 * e, hipMemcpyDeviceToHost, ctx->stream));
-  if (ns) HIPCHK(ctx, hipMemcpyAsync(ns, ctx->meshN.p, nv * 3 * e, hipMemcpyDeviceToHost, ctx->stream));
-  if (cs) HIPCHK(ctx, hipMemcpyAsync(cs, ctx->meshC.p, nv * 4 * e, hipMemcpyDeviceToHost, ctx->stream));
-  if (tris) HIPCHK(ctx, hipMemcpyAsync(tris, ctx->meshT.p, nt * 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return PBF_OK;
+  void *const host[] = {vs, ns, cs, tris};
+  return download_mesh_parts(
+      ctx, {{&ctx->meshV, nv * 3 * e}, {&ctx->meshN, nv * 3 * e}, {&ctx->meshC, nv * 4 * e}, {&ctx->meshT, nt * 3 * 4}}, host);
 }
 
 int pbf_map_mesh_indexed(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs, const uint32_t **tris) {
@@ -3314,25 +3376,11 @@ int pbf_map_mesh_indexed(pbf_ctx *ctx, const void **vs, const void **ns, const v
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t nv = ctx->mcVertices, nt = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
   if (nt == 0) return PBF_OK;
-  const size_t bv = nv * 3 * e, bc = nv * 4 * e, bt = nt * 3 * 4, total = 2 * bv + bc + bt;
-  if (ctx->meshHostCap < total) {
-    if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
-    ctx->meshHost = nullptr, ctx->meshHostCap = 0;
-    const size_t want = total + total / 4 + 4096;
-    HIPCHK(ctx, hipHostMalloc(&ctx->meshHost, want, hipHostMallocDefault));
-    ctx->meshHostCap = want;
-    ctx->meshStaged = false;
-  }
-  char *h = static_cast<char *>(ctx->meshHost);
-  if (!ctx->meshStaged) {
-    HIPCHK(ctx, hipMemcpyAsync(h, ctx->meshV.p, bv, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h + bv, ctx->meshN.p, bv, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h + 2 * bv, ctx->meshC.p, bc, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h + 2 * bv + bc, ctx->meshT.p, bt, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->meshStaged = true;
-  }
-  *vs = h, *ns = h + bv, *cs = h + 2 * bv, *tris = reinterpret_cast<const uint32_t *>(h + 2 * bv + bc);
+  const void *at[4];
+  const int rc = map_mesh_parts(
+      ctx, {{&ctx->meshV, nv * 3 * e}, {&ctx->meshN, nv * 3 * e}, {&ctx->meshC, nv * 4 * e}, {&ctx->meshT, nt * 3 * 4}}, at);
+  if (rc) return rc;
+  *vs = at[0], *ns = at[1], *cs = at[2], *tris = static_cast<const uint32_t *>(at[3]);
   return PBF_OK;
 }
 
@@ -3343,11 +3391,8 @@ int pbf_download_mesh(pbf_ctx *ctx, void *vs, void *ns, void *cs) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t n = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
   if (n == 0) return PBF_OK;
-  if (vs) HIPCHK(ctx, hipMemcpyAsync(vs, ctx->meshV.p, n * 9 * e, hipMemcpyDeviceToHost, ctx->stream));
-  if (ns) HIPCHK(ctx, hipMemcpyAsync(ns, ctx->meshN.p, n * 9 * e, hipMemcpyDeviceToHost, ctx->stream));
-  if (cs) HIPCHK(ctx, hipMemcpyAsync(cs, ctx->meshC.p, n * 12 * e, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return PBF_OK;
+  void *const host[] = {vs, ns, cs};
+  return download_mesh_parts(ctx, {{&ctx->meshV, n * 9 * e}, {&ctx->meshN, n * 9 * e}, {&ctx->meshC, n * 12 * e}}, host);
 }
 
 int pbf_map_mesh(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs) {
@@ -3358,27 +3403,9 @@ int pbf_map_mesh(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs
   const size_t n = ctx->mcTriangles, e = ctx->fp64 ? 8 : 4;
   *vs = *ns = *cs = nullptr;
   if (n == 0) return PBF_OK;
-  const size_t bv = n * 9 * e, bc = n * 12 * e, total = 2 * bv + bc;
-  if (ctx->meshHostCap < total) {
-    if (ctx->meshHost) (void)hipHostFree(ctx->meshHost);
-    ctx->meshHost = nullptr, ctx->meshHostCap = 0;
-    const size_t want = total + total / 4 + 4096;
-    HIPCHK(ctx, hipHostMalloc(&ctx->meshHost, want, hipHostMallocDefault));
-    ctx->meshHostCap = want;
-    ctx->meshStaged = false;
-  }
-  char *h = static_cast<char *>(ctx->meshHost);
-  if (!ctx->meshStaged) {
-    // (one wait behind all three: handing the arrays out one by one, an event behind each, so that the caller's copy of the
-    // vertices overlaps the normals' DMA was measured — no faster at 0.75 M vertices, 11 % slower at 1.35 M: the host copies
-    // and the DMA share the memory system)
-    HIPCHK(ctx, hipMemcpyAsync(h, ctx->meshV.p, bv, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h + bv, ctx->meshN.p, bv, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h + 2 * bv, ctx->meshC.p, bc, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->meshStaged = true;
-  }
-  *vs = h, *ns = h + bv, *cs = h + 2 * bv;
+  const void *at[3];
+  if (int rc = map_mesh_parts(ctx, {{&ctx->meshV, n * 9 * e}, {&ctx->meshN, n * 9 * e}, {&ctx->meshC, n * 12 * e}}, at)) return rc;
+  *vs = at[0], *ns = at[1], *cs = at[2];
   return PBF_OK;
 }
 

@@ -7,25 +7,13 @@
 #include <cstring>
 
 #include "hipsph.hpp"
+#include "shim_check.hpp"
 
 using T = size_t;
 using N = float;
 using P = sph::Particle<T, N, sph::vec>;
 
-static int failures = 0;
-static void check(const char *name, bool ok) {
-  std::printf("%s %s\n", ok ? "ok" : "FAIL", name);
-  failures += ok ? 0 : 1;
-}
-static bool same(const std::vector<P> &a, const std::vector<P> &b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); ++i)
-    if (a[i].id != b[i].id || a[i].type != b[i].type || std::memcmp(&a[i].mass, &b[i].mass, sizeof(N)) ||
-        std::memcmp(&a[i].position, &b[i].position, 3 * sizeof(N)) || std::memcmp(&a[i].velocity, &b[i].velocity, 3 * sizeof(N)) ||
-        std::memcmp(&a[i].colour, &b[i].colour, 4 * sizeof(N)))
-      return false;
-  return true;
-}
+using shim::check;
 static bool close(double a, double b, double scale) { return std::fabs(a - b) <= 1e-12 * scale; }
 
 int main() {
@@ -70,8 +58,7 @@ int main() {
   a.step(config), b.step(config);
   std::vector<P> ya, yb;
   a.download(ya), b.download(yb);
-  check("diag_shim_observer", same(ya, yb));
+  check("diag_shim_observer", shim::same_particles(ya, yb));
 
-  std::printf(failures ? "FAILED\n" : "ALL OK\n");
-  return failures ? 1 : 0;
+  return shim::finish();
 }

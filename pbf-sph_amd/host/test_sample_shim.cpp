@@ -8,17 +8,12 @@
 #include <string>
 
 #include "hipsph.hpp"
+#include "shim_check.hpp"
 
 using T = size_t;
 
-static int failures = 0;
-static void check(const std::string &name, bool ok) {
-  std::printf("%s %s\n", ok ? "ok" : "FAIL", name.c_str());
-  failures += ok ? 0 : 1;
-}
-template <typename A> static bool same_bytes(const std::vector<A> &a, const std::vector<A> &b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(A)) == 0);
-}
+using shim::check;
+using shim::same_bytes;
 
 template <typename N> static void run(const std::string &tag) {
   using P = sph::Particle<T, N, sph::vec>;
@@ -89,16 +84,11 @@ template <typename N> static void run(const std::string &tag) {
   a.step(config), b.step(config);
   std::vector<P> ya, yb;
   a.download(ya), b.download(yb);
-  bool same = ya.size() == yb.size();
-  for (size_t i = 0; i < ya.size() && same; ++i)
-    same = ya[i].id == yb[i].id && !std::memcmp(&ya[i].position, &yb[i].position, 3 * sizeof(N)) &&
-           !std::memcmp(&ya[i].velocity, &yb[i].velocity, 3 * sizeof(N)) && !std::memcmp(&ya[i].colour, &yb[i].colour, 4 * sizeof(N));
-  check(tag + "sample_shim_observer", same);
+  check(tag + "sample_shim_observer", shim::same_particles(ya, yb));
 }
 
 int main() {
   run<float>("fp32_");
   run<double>("fp64_");
-  std::printf(failures ? "FAILED\n" : "ALL OK\n");
-  return failures ? 1 : 0;
+  return shim::finish();
 }

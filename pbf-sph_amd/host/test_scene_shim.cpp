@@ -3,10 +3,8 @@
 // drain, an obstacle, queries; reference behaviour: src/omp/ompsph.hpp:91-126,167-186) — the same particles in the
 // same order with the same bytes, the same query answers.  Prints "ok <name>" / "FAIL <name>" lines and "ALL OK";
 // tests/test_scene_resident_gpu.py runs it on a GPU.
-#include <cstdio>
-#include <cstring>
-
 #include "hipsph.hpp"
+#include "shim_check.hpp"
 
 using T = size_t;
 using N = float;
@@ -14,21 +12,7 @@ using P = sph::Particle<T, N, sph::vec>;
 using V3 = sph::vec<3, N>;
 using V4 = sph::vec<4, N>;
 
-static int failures = 0;
-static void check(const char *name, bool ok) {
-  std::printf("%s %s\n", ok ? "ok" : "FAIL", name);
-  failures += ok ? 0 : 1;
-}
-
-static bool same(const std::vector<P> &a, const std::vector<P> &b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); ++i)
-    if (a[i].id != b[i].id || a[i].type != b[i].type || std::memcmp(&a[i].mass, &b[i].mass, sizeof(N)) ||
-        std::memcmp(&a[i].position, &b[i].position, sizeof(V3)) || std::memcmp(&a[i].velocity, &b[i].velocity, sizeof(V3)) ||
-        std::memcmp(&a[i].colour, &b[i].colour, sizeof(V4)))
-      return false;
-  return true;
-}
+using shim::check;
 
 int main() {
   auto [mc, config, particles] = sph::simpleConfigWith2Cubes<T, N, sph::vec>(2048, 4, N(500));
@@ -56,7 +40,7 @@ int main() {
   std::vector<P> ys;
   resident.download(ys);
   check("scene_resident_count", resident.count() == xs.size());
-  check("scene_resident_equals_advance", same(xs, ys));
+  check("scene_resident_equals_advance", shim::same_particles(xs, ys));
   bool q = answers.size() == last.queries.size();
   for (size_t i = 0; q && i < answers.size(); ++i)
     q = answers[i].id == last.queries[i].id && answers[i].neighbours == last.queries[i].neighbours;
@@ -69,11 +53,10 @@ int main() {
   for (uint32_t f = 0; f < frames; ++f) single.step(config, scene);
   std::vector<P> zs;
   single.download(zs);
-  check("scene_resident_stepwise", same(xs, zs));
+  check("scene_resident_stepwise", shim::same_particles(xs, zs));
   // an empty scene clears both settings again
   single.step(config);
   check("scene_resident_cleared", single.count() == zs.size());
 
-  std::printf(failures ? "FAILED\n" : "ALL OK\n");
-  return failures ? 1 : 0;
+  return shim::finish();
 }

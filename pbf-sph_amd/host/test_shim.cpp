@@ -9,6 +9,7 @@
 #include <string>
 
 #include "hipsph.hpp"
+#include "shim_check.hpp"
 
 using T = size_t;
 using N = float;
@@ -16,17 +17,7 @@ using P = sph::Particle<T, N, sph::vec>;
 using V3 = sph::vec<3, N>;
 using V4 = sph::vec<4, N>;
 
-static int failures = 0;
-#define CHECK(name, cond, ...)                  \
-  do {                                          \
-    if (cond) std::printf("ok %s\n", name);     \
-    else {                                      \
-      ++failures;                               \
-      std::printf("FAIL %s ", name);            \
-      std::printf(__VA_ARGS__);                 \
-      std::printf("\n");                        \
-    }                                           \
-  } while (0)
+using shim::check;
 
 // --dump <dir>: one fixed scene with sources, a drain, an obstacle and queries run through advance() for two frames;
 // the particles and the query answers after each frame go to <dir> as raw arrays.  tests/test_cli_gpu.py replays the
@@ -88,10 +79,10 @@ int main(int argc, char **argv) {
     solver.advance(config, scene, xs);
     size_t n777 = 0, n888 = 0;
     for (const auto &p : xs) n777 += p.id == 100777, n888 += p.id == 100888;
-    CHECK("sources_count", xs.size() == before + 16 + 12 && n777 == 16 && n888 == 12, "size %zu n777 %zu n888 %zu",
+    check("sources_count", xs.size() == before + 16 + 12 && n777 == 16 && n888 == 12, "size %zu n777 %zu n888 %zu",
           xs.size(), n777, n888);
     solver.advance(config, scene, xs);
-    CHECK("sources_accumulate", xs.size() == before + 2 * 28, "size %zu", xs.size());
+    check("sources_accumulate", xs.size() == before + 2 * 28, "size %zu", xs.size());
   }
   {  // drains: fluid within `width` of the centre disappears, obstacles stay (ompsph.hpp:107-118)
     auto xs = particles;
@@ -107,7 +98,7 @@ int main(int argc, char **argv) {
     solver.advance(config, scene, xs);
     bool obstacleKept = false;
     for (const auto &p : xs) obstacleKept |= p.id == particles[0].id && p.type == sph::Type::Obstacle;
-    CHECK("drains", expectGone > 3 && xs.size() == before - expectGone && obstacleKept, "gone %zu size %zu->%zu", expectGone,
+    check("drains", expectGone > 3 && xs.size() == before - expectGone && obstacleKept, "gone %zu size %zu->%zu", expectGone,
           before, xs.size());
   }
   {  // queries: ids of the fluid particles in the query point's cell (ompsph.hpp:167-186); particles at rest
@@ -130,14 +121,14 @@ int main(int argc, char **argv) {
         expect.insert(p.id);
     const auto res = solver.advance(still, scene, xs);
     std::set<T> got(res.queries[0].neighbours.begin(), res.queries[0].neighbours.end());
-    CHECK("queries", res.queries.size() == 2 && res.queries[0].id == 5 && got == expect && got.count(id100) == 1 &&
+    check("queries", res.queries.size() == 2 && res.queries[0].id == 5 && got == expect && got.count(id100) == 1 &&
                          res.queries[1].neighbours.empty(),
           "got %zu expect %zu", got.size(), expect.size());
   }
   {  // depletion (ompsph.hpp:122-126)
     std::vector<P> none;
     const auto res = solver.advance(config, {}, none);
-    CHECK("depleted", none.empty() && res.mesh.vs.empty() && res.queries.empty(), "-");
+    check("depleted", none.empty() && res.mesh.vs.empty() && res.queries.empty(), "-");
   }
   {  // advance() per frame == device-resident stepping, bit for bit
     auto a = particles, b = particles;
@@ -146,9 +137,7 @@ int main(int argc, char **argv) {
     resident.upload(b);
     for (int f = 0; f < 3; ++f) resident.step(sph::applyMotionSinXCosZ(config, f));
     resident.download(b);
-    bool same = a.size() == b.size();
-    for (size_t i = 0; same && i < a.size(); ++i) same = a[i] == b[i];
-    CHECK("advance_equals_resident", same, "sizes %zu %zu", a.size(), b.size());
+    check("advance_equals_resident", a == b, "sizes %zu %zu", a.size(), b.size());
   }
   {  // Solver(h, {devices...}): three x-slabs (sharing this GPU: in-process exchange behind the library's host-callback
      // transport; distinct GPUs take RCCL) == ONE solver up to summation order; nothing lost; cuts re-balanced
@@ -175,13 +164,13 @@ int main(int argc, char **argv) {
       const double e = std::sqrt(double(d.x) * d.x + double(d.y) * d.y + double(d.z) * d.z);
       worst = std::max(worst, e), sum += e;
     }
-    CHECK("multi_device_slabs", ids && slabs.deviceCount() == 3 && sum / double(a.size()) <= 0.05 && slabs.cuts() != cuts0,
+    check("multi_device_slabs", ids && slabs.deviceCount() == 3 && sum / double(a.size()) <= 0.05 && slabs.cuts() != cuts0,
           "sizes %zu %zu worst %g mean %g", a.size(), b.size(), worst, sum / double(a.size()));
     // advance() on several devices keeps the reference's contract too (upload -> step -> download)
     auto c = dparticles;
     sph::hip_impl::Solver<T, N> two(N(0.1), std::vector<int>{0, 0});
     two.advance(dparam, {}, c);
-    CHECK("multi_device_advance", c.size() == dparticles.size(), "size %zu", c.size());
+    check("multi_device_advance", c.size() == dparticles.size(), "size %zu", c.size());
   }
   {  // the surface across slabs (round 3): every slab extracts the cubes of its own node planes — ghost layer for the
      // 27-cell neighbourhoods, the owners' diffused colours refreshed on the copies, one node plane handed to the left —
@@ -212,15 +201,14 @@ int main(int argc, char **argv) {
           worstC = std::max({worstC, double(std::fabs(ma.cs[i].x - mb.cs[i].x)), double(std::fabs(ma.cs[i].y - mb.cs[i].y)),
                              double(std::fabs(ma.cs[i].z - mb.cs[i].z)), double(std::fabs(ma.cs[i].w - mb.cs[i].w))});
         }
-        CHECK("multi_device_surface_exact", same && badN <= ma.vs.size() / 1000 && worstC <= 1e-5, "vertices %zu vs %zu, normals off %zu, colours off by %g",
+        check("multi_device_surface_exact", same && badN <= ma.vs.size() / 1000 && worstC <= 1e-5, "vertices %zu vs %zu, normals off %zu, colours off by %g",
               ma.vs.size(), mb.vs.size(), badN, worstC);
       } else {
         const double ra_n = double(ma.vs.size()), rb_n = double(mb.vs.size());
-        CHECK("multi_device_surface_solved", rb_n > 3000 && std::fabs(ra_n - rb_n) <= 0.02 * rb_n + 60, "vertices %zu vs %zu", ma.vs.size(),
+        check("multi_device_surface_solved", rb_n > 3000 && std::fabs(ra_n - rb_n) <= 0.02 * rb_n + 60, "vertices %zu vs %zu", ma.vs.size(),
               mb.vs.size());
       }
     }
   }
-  std::printf(failures ? "FAILED %d\n" : "ALL OK\n", failures);
-  return failures ? 1 : 0;
+  return shim::finish();
 }

@@ -7,27 +7,15 @@
 #include <string>
 
 #include "hipsph.hpp"
+#include "shim_check.hpp"
 
 using T = size_t;
 
-static int failures = 0;
-static void check(const std::string &name, bool ok) {
-  std::printf("%s %s\n", ok ? "ok" : "FAIL", name.c_str());
-  failures += ok ? 0 : 1;
-}
-template <typename A> static bool same_bytes(const std::vector<A> &a, const std::vector<A> &b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(A)) == 0);
-}
+using shim::check;
+using shim::same_bytes;
 template <typename W> static bool same_pool(const W &a, const W &b) {
   return same_bytes(a.positions, b.positions) && same_bytes(a.velocities, b.velocities) && same_bytes(a.life, b.life) &&
          same_bytes(a.kind, b.kind) && same_bytes(a.parentId, b.parentId);
-}
-template <typename P, typename N> static bool same_fluid(const std::vector<P> &a, const std::vector<P> &b) {
-  bool same = a.size() == b.size();
-  for (size_t i = 0; i < a.size() && same; ++i)
-    same = a[i].id == b[i].id && !std::memcmp(&a[i].position, &b[i].position, 3 * sizeof(N)) &&
-           !std::memcmp(&a[i].velocity, &b[i].velocity, 3 * sizeof(N)) && !std::memcmp(&a[i].colour, &b[i].colour, 4 * sizeof(N));
-  return same;
 }
 
 template <typename N> static void run(const std::string &tag) {
@@ -78,7 +66,7 @@ template <typename N> static void run(const std::string &tag) {
   check(tag + "whitewater_shim_pool_bits", pa.positions.size() == sa.alive && same_pool(pa, pb));
   std::vector<P> ya, yp;
   a.download(ya), plain.download(yp);
-  check(tag + "whitewater_shim_observer", same_fluid<P, N>(ya, yp));
+  check(tag + "whitewater_shim_observer", shim::same_particles(ya, yp));
 
   // advance(): configured, one whitewater step after each fluid step — the same frames by hand on d
   sph::hip_impl::Solver<T, N> c(N(0.1)), d(N(0.1));
@@ -96,7 +84,7 @@ template <typename N> static void run(const std::string &tag) {
   }
   check(tag + "whitewater_shim_advance_steps", frames && c.whitewaterStats().alive > 0);
   check(tag + "whitewater_shim_advance_pool", same_pool(c.whitewaterParticles(), d.whitewaterParticles()));
-  check(tag + "whitewater_shim_advance_fluid", same_fluid<P, N>(xc, xd));
+  check(tag + "whitewater_shim_advance_fluid", shim::same_particles(xc, xd));
   ww.capacity = 0;
   c.whitewater(ww);
   (void)c.advance(config, scene, xc);
@@ -106,6 +94,5 @@ template <typename N> static void run(const std::string &tag) {
 int main() {
   run<float>("fp32_");
   run<double>("fp64_");
-  std::printf(failures ? "FAILED\n" : "ALL OK\n");
-  return failures ? 1 : 0;
+  return shim::finish();
 }

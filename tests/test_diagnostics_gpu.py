@@ -255,6 +255,78 @@ def test_refusals_leave_the_record_untouched(pkg):
     assert b"slab" in L.pbf_last_error(s.ctx)
 
 
+def test_records_go_stale_on_a_replayed_step(pkg):
+    """What the density pass and a whitewater step leave for pbf_read_buffer describes one sorted order.  A step replayed
+    from a captured graph launches its sort without running the host code of the sort stage: the records must go stale
+    there as well.  At least one of the single steps below has to be a replay, or the test has not reached that path."""
+    p = pkg.default_params(4, 1000.0)
+    s = solver(pkg, pkg.scene_cubes(2048, False), False, graph=1)
+    s.whitewater_configure(capacity=4096, k_ta=50.0, k_wc=50.0, tau_ta=(0.0, 0.5), tau_wc=(0.0, 0.5), tau_k=(0.0, 0.01))
+    for _ in range(4):
+        s.steps(p, 4)
+    rho, pot = np.empty(s.n, np.float32), np.empty((s.n, 4), np.float32)
+
+    def read():
+        return (s.L.pbf_read_buffer(s.ctx, pkg.BUF_DENSITY, rho.ctypes.data_as(C.c_void_p), rho.nbytes),
+                s.L.pbf_read_buffer(s.ctx, pkg.BUF_WHITEWATER, pot.ctypes.data_as(C.c_void_p), pot.nbytes))
+
+    replays = 0
+    for _ in range(4):
+        s.diagnostics(p, density=True)
+        s.whitewater_step(p)
+        assert read() == (0, 0)
+        before = s.graph_stats()
+        s.steps(p, 1)
+        after = s.graph_stats()
+        print("graph stats", before, "->", after)
+        assert read() == (ERR_STATE, ERR_STATE)
+        replays += after[1] == before[1] + 1
+    assert replays >= 1, "no single step was a replay: restore() was not reached"
+
+
+def touch_every_owner(pkg):
+    """One context that makes every lazily allocated owner allocate — the drain's, the diagnostics' and the whitewater
+    step's pinned records, the pinned mesh staging (mapped as a soup and as an indexed mesh), the observers' scratch — and
+    is then destroyed -> everything it handed out, as bytes."""
+    p = pkg.default_params(2, 1000.0)
+    sc = pkg.scene_cubes(2048, False)
+    s = solver(pkg, sc, False)
+    s.set_drains([(sc["pos"][7], 60.0)])
+    s.whitewater_configure(capacity=4096, k_ta=50.0, k_wc=50.0, tau_ta=(0.0, 0.5), tau_wc=(0.0, 0.5), tau_k=(0.0, 0.01))
+    s.steps(p, 2)
+    assert s.scene_host_syncs() == 2 and s.n > 0
+    out = {"diag": raw(s.diagnostics(p, density=True, raw=True)), "rho": s.density().tobytes()}
+    out["ww"] = repr(s.whitewater_step(p))
+    out.update(("ww_" + k, v.tobytes()) for k, v in s.whitewater_download().items())
+    out["pot"] = s.whitewater_potentials().tobytes()
+    for indexed in (False, True):
+        mesh = s.surface_indexed(p) if indexed else s.surface(p)
+        sizes = [a.nbytes for a in (mesh["vs"], mesh["ns"], mesh["cs"])] + ([mesh["tris"].nbytes] if indexed else [])
+        assert min(sizes) > 0
+        at = [C.c_void_p() for _ in sizes]
+        fn = s.L.pbf_map_mesh_indexed if indexed else s.L.pbf_map_mesh
+        assert fn(s.ctx, *[C.byref(a) for a in at]) == 0
+        for k, (a, n) in enumerate(zip(at, sizes)):
+            out["map%d_%d" % (indexed, k)] = C.string_at(a.value, n)
+        assert [out["map%d_%d" % (indexed, k)] for k in range(3)] == [mesh[k].tobytes() for k in ("vs", "ns", "cs")]
+    pts = sc["pos"][::97].astype(np.float64)
+    out["query"] = b"".join(ids.tobytes() for ids in s.query(p, pts))
+    out.update(("sample_" + k, v.tobytes()) for k, v in s.sample(p, pts, velocity=True, colour=True).items())
+    out.update(("aniso_" + k, np.ascontiguousarray(v).tobytes()) for k, v in s.anisotropy(p).items())
+    s.step(p)
+    out.update(("down_" + k, v.tobytes()) for k, v in s.download().items())
+    s.close()
+    return out
+
+
+def test_a_second_context_after_a_destroyed_one(pkg):
+    """every owner allocated, the context destroyed, and the same again in the same process: the same bytes"""
+    first, second = touch_every_owner(pkg), touch_every_owner(pkg)
+    print("bytes compared", {k: len(v) for k, v in first.items()})
+    assert first.keys() == second.keys()
+    assert [k for k in first if first[k] != second[k]] == []
+
+
 # ---- CLI and shim -----------------------------------------------------------------------------------------------------
 
 def test_benchmark_flag(pkg, tmp_path):
