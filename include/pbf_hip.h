@@ -81,7 +81,7 @@ int pbf_abi_version(void);
 /* Tuning / diagnostic knobs (no reference counterpart): "gather" (0 global walk, 1 neighbour lists = default, 3 LDS tiles
  * per brick), "list_max", "tile_cap", "reuse_lists", "split_build" (0 = lambda builds the lists while it gathers; 4 / 5 = a
  * list-build launch of its own with 2 / 4 pair loads per trip, then a list-driven lambda; 8 = DEFAULT: the quantised list
- * build with lambda riding on its flushes, one launch), "coop" (0 = one lane per particle in the list-driven lambda /
+ * build with lambda riding on its flushes, one launch — the same build kernel either way, with or without a rider), "coop" (0 = one lane per particle in the list-driven lambda /
  * delta-p, bit-exact, default; 2 / 4 / 8 = that many lanes share a particle's list and reduce the kernel sums with wave
  * shuffles: rounding-level differences), "cell_diffuse" (one colour walk per occupied cell, default 1), "fuse_diffuse",
  * "overlap_diffuse", "fuse_predict", "pipeline", "graph", "pad_lds", "timing_mask" (bit i = stage i of pbf_stage_times is

@@ -197,7 +197,7 @@ struct pbf_ctx {
   enum MeshKind { MESH_NONE, MESH_SOUP, MESH_INDEXED };
   MeshKind meshKind = MESH_NONE;  // what the last surface call left in meshV / meshN / meshC (3 per triangle, or 1 per crossed edge)
   uint64_t mcVertices = 0;
-  DevBuf qpos;               // 8-byte quantised pStar for the list build (k_build_lists_q)
+  DevBuf qpos;               // 8-byte quantised pStar for the list build (k_build_lists_op)
   DevBuf nbrList, nbrCount;  // neighbour lists handed from the lambda launch to the delta launch: NBR_ROWS slots per particle
   // option "row_major": the iterations' working set also laid out cell-row-major (csrc/pbf_kernels.hpp RowArrays)
   int rowMajor = 1;           // default ON since round 3: -3 % per step at 1 M, -10 % at 4 M (profiles/r03_matrix.txt)
@@ -273,9 +273,10 @@ struct pbf_ctx {
   bool haveParams = false;
   bool reuseLists = true;    // option "reuse_lists"
   // option "split_build": 0 = lambda builds the neighbour lists while it gathers on fp32 candidates (k_gather_lists<SAVE>);
-  // 4 / 5 = the build is a launch of its own (k_build_lists_q on quantised pairs, 2 / 4 pair loads per trip) followed by a
-  // list-driven lambda; 8 (default) = the quantised build with lambda riding on its flushes (k_build_lists_op: one launch,
-  // no list read for lambda).  (Round 1's intermediate build kernels, values 1-3, are gone.)
+  // 4 / 5 = the build is a launch of its own (k_build_lists_op<ListOnlyOp> on quantised pairs, 2 / 4 pair loads per trip)
+  // followed by a list-driven lambda; 8 (default) = the same kernel with lambda riding on its flushes
+  // (k_build_lists_op<LambdaOp>: one launch, no list read for lambda).  (Round 1's intermediate build kernels, values 1-3,
+  // are gone.)
   int splitBuild = 8;
   int pipeline = -1;         // option "pipeline": software-pipelined list readers (bit-identical either way); -1 = auto = off
                              // (measured at 1 M, round 3: fp32 +3 %, fp64 +2.4 % per step with it)
@@ -304,6 +305,7 @@ struct pbf_ctx {
   int numCUs = 256;
   uint32_t timingMask = 0xFFFFFFFFu;  // option "timing_mask": which stages PBF_FLAG_STAGE_TIMING brackets with events
   uint32_t padLds = 0;      // option "pad_lds": occupancy limiter for k_gather_global
+  std::map<const void *, size_t> ldsLimit;  // kernel -> the dynamic-LDS limit this context has raised it to (raise_lds_limit)
   int gatherKind = 1;       // 0 = global walk (k_gather_global), 1 = neighbour lists (default), 3 = LDS tiles per brick (pbf_tiles.hpp)
   uint32_t tileCap = 0, listMax = 0;  // 0 = defaults (env PBF_TILE_CAP / PBF_LIST_MAX override)
   size_t tableCap = 0;   // entries allocated in count/table
@@ -761,6 +763,50 @@ NbrLists nbr_lists(pbf_ctx *ctx, bool build) {
                   ctx->nbrExtraAt, ctx->nbrChunks};
 }
 
+// A launch with more than the default dynamic LDS needs the kernel's limit raised first.  The high-water mark is this
+// context's own: the attribute belongs to the device the context runs on, and contexts of other devices or threads raise it
+// themselves.
+int raise_lds_limit(pbf_ctx *ctx, const void *kernel, size_t lds) {
+  size_t &mark = ctx->ldsLimit[kernel];
+  if (lds <= mark) return PBF_OK;
+  HIPCHK(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+  mark = lds;
+  return PBF_OK;
+}
+
+// the quantised copy of pStar, made here only after a stage that moved pStar without refreshing it
+template <typename N> uint2 *ensure_qpos(pbf_ctx *ctx, const StepConsts<N> &c, const vec4<N> *pstar) {
+  uint2 *qp = ctx->qpos.as<uint2>();
+  if (!ctx->st.qposValid) {
+    hipLaunchKernelGGL((k_quantise<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, pstar, qp);
+    ctx->st.quantised();
+  }
+  return qp;
+}
+
+// the list-driven reader, one lane per particle (ROWS: on the row-major copy)
+// (option "pipeline", auto = off: with round 3's trimmed fp64 sqrt / divides the plain reader wins in fp64 too — 2.05 vs
+// 2.10 ms per step at 1 M; in round 2, on the compiler's IEEE forms, the pipelined one had been 1.3 % ahead there)
+template <typename N, typename Op, bool ROWS>
+void launch_from_lists(pbf_ctx *ctx, const StepConsts<N> &c, const typename Op::Args &args, const uint32_t *key,
+                       const uint32_t *table, const RowWalk &rw = {}) {
+  const dim3 g = grid_for(ctx->n), b(BLOCK);
+  const NbrLists ls = nbr_lists(ctx, false);
+  if (ctx->pipeline > 0)
+    hipLaunchKernelGGL((k_gather_from_lists<N, Op, true, ROWS>), g, b, 0, ctx->stream, c, args, key, table, ls, rw);
+  else
+    hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, ROWS>), g, b, 0, ctx->stream, c, args, key, table, ls, rw);
+}
+
+// the list build on the Morton-sorted arrays with `Ride` riding on it: W pair loads per trip, staging depth LMAX, FW survivors
+// per drain trip
+template <typename N, typename Ride, int W, int LMAX, int FW>
+void launch_build_lists(pbf_ctx *ctx, const StepConsts<N> &c, const typename Ride::Args &ride, const vec4<N> *pstar,
+                        const uint2 *qp, const uint8_t *type, const uint32_t *key, const uint32_t *table) {
+  hipLaunchKernelGGL((k_build_lists_op<N, Ride, W, LMAX, FW>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, ride, pstar, qp,
+                     type, key, table, nbr_lists(ctx, true));
+}
+
 template <typename N, typename Op>
 int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, GatherMode mode = GATHER_PLAIN) {
   const uint32_t *key = ctx->key[ctx->st.cur].as<const uint32_t>();
@@ -785,35 +831,25 @@ int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, 
       uint32_t *nl = ctx->nbrList.as<uint32_t>(), *nc = ctx->nbrCount.as<uint32_t>();
       uint32_t *ctl = ctx->brickCtl.as<uint32_t>();
       auto ticket = [&]() -> uint32_t * { return next_ticket(ctx); };
-      auto launch_dims = [&](const void *kernel, size_t lds, size_t &attrSet) {
-        if (lds > attrSet) {
-          (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-          attrSet = lds;
-        }
+      auto grid_of = [&](size_t lds) {
         const uint32_t perCU = uint32_t(std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / (lds + 512))));
         return dim3(uint32_t(ctx->numCUs) * perCU);
       };
       if (mode == GATHER_SAVE_LISTS) {
-        uint2 *qp = ctx->qpos.as<uint2>();
-        if (!ctx->st.qposValid) {
-          hipLaunchKernelGGL((k_quantise<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, Op::src(args), qp);
-          ctx->st.quantised();
-        }
+        const uint2 *qp = ensure_qpos<N>(ctx, c, Op::src(args));
         StageTimer tb(ctx, ST_BUILD);
         const size_t lds = B::HDR2 + size_t(cap + WAYS) * sizeof(uint2) + size_t(LMAX + WAYS) * TILE_THREADS * 2;
         if (lds > 160 * 1024 - 64) return fail(ctx, PBF_ERR_INVALID, "tile cap exceeds the CU's 160 KiB LDS");
         auto kernel = k_tile_build<N, WAYS, LMAX>;
-        static size_t attrSet = 0;
-        const dim3 grid = launch_dims(reinterpret_cast<const void *>(kernel), lds, attrSet);
-        hipLaunchKernelGGL(kernel, grid, dim3(TILE_THREADS), lds, ctx->stream, c, Op::src(args), qp, args.type, key, table,
+        if (int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kernel), lds)) return rc;
+        hipLaunchKernelGGL(kernel, grid_of(lds), dim3(TILE_THREADS), lds, ctx->stream, c, Op::src(args), qp, args.type, key, table,
                            ctx->bricks.as<const uint32_t>(), ctl, ticket(), cap, nl, nc);
       }
       const size_t lds = B::HDR2 + size_t(cap) * sizeof(typename Op::Src);
       if (lds > 160 * 1024 - 64) return fail(ctx, PBF_ERR_INVALID, "tile cap exceeds the CU's 160 KiB LDS");
       auto kernel = k_tile_from_lists<N, Op>;
-      static size_t attrSet = 0;  // per instantiation
-      const dim3 grid = launch_dims(reinterpret_cast<const void *>(kernel), lds, attrSet);
-      hipLaunchKernelGGL(kernel, grid, dim3(TILE_THREADS), lds, ctx->stream, c, args, key, table,
+      if (int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kernel), lds)) return rc;
+      hipLaunchKernelGGL(kernel, grid_of(lds), dim3(TILE_THREADS), lds, ctx->stream, c, args, key, table,
                          ctx->bricks.as<const uint32_t>(), ctl, ticket(), cap, nl, nc);
       LAUNCH_CHECK(ctx);
       return PBF_OK;
@@ -821,9 +857,9 @@ int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, 
   }
   if (ctx->gatherKind == 1 || ctx->gatherKind == 3) {
     const dim3 g = grid_for(ctx->n), b(BLOCK);
-    auto from_lists = [&]() {
-      const NbrLists ls = nbr_lists(ctx, false);  // the list-driven reader: one lane per particle, or (option "coop") a lane group per particle
+    auto from_lists = [&]() {  // the list-driven reader: one lane per particle, or (option "coop") a lane group per particle
       if constexpr (Op::kTileable && Op::kFilter) {
+        const NbrLists ls = nbr_lists(ctx, false);
         auto coop_grid = [&](int k) { return dim3(unsigned(std::max<size_t>(1, (ctx->n * k + BLOCK - 1) / BLOCK))); };
         switch (ctx->coop) {
           case 2: hipLaunchKernelGGL((k_gather_from_lists_coop<N, Op, 2>), coop_grid(2), b, 0, ctx->stream, c, args, key, table, ls); return;
@@ -832,40 +868,41 @@ int launch_gather(pbf_ctx *ctx, const StepConsts<N> &c, typename Op::Args args, 
           default: break;
         }
       }
-      // (auto = off: with round 3's trimmed fp64 sqrt / divides the plain reader wins in fp64 too — 2.05 vs 2.10 ms per step
-      // at 1 M; in round 2, on the compiler's IEEE forms, the pipelined one had been 1.3 % ahead there)
-      if (ctx->pipeline > 0)
-        hipLaunchKernelGGL((k_gather_from_lists<N, Op, true>), g, b, 0, ctx->stream, c, args, key, table, ls);
-      else
-        hipLaunchKernelGGL((k_gather_from_lists<N, Op, false>), g, b, 0, ctx->stream, c, args, key, table, ls);
+      launch_from_lists<N, Op, false>(ctx, c, args, key, table);
     };
     if (mode == GATHER_FROM_LISTS) {
       from_lists();
     } else if (mode == GATHER_SAVE_LISTS && ctx->splitBuild &&
-               uint64_t(ctx->n) * sizeof(typename Op::Src) <= 0xFFFFFFFFull) {  // (k_build_lists: 32-bit offsets)  // build the lists, then run the op list-driven
+               uint64_t(ctx->n) * sizeof(typename Op::Src) <= 0xFFFFFFFFull) {  // (k_build_lists_op: 32-bit offsets)
+      // One build kernel; split_build says what rides on it.  8: the op itself — nothing is left to run list-driven.
+      // 4 / 5: nothing (ListOnlyOp), with 2 / 4 pair loads per trip — the op then runs list-driven.
       if constexpr (Op::kTileable && Op::kFilter) {  // (the ops that filter on pStar itself: lambda, delta-p)
-        uint2 *qp = ctx->qpos.as<uint2>();
-        if (!ctx->st.qposValid) {  // (only after a stage that moved pStar without refreshing its quantised copy)
-          hipLaunchKernelGGL((k_quantise<N>), g, b, 0, ctx->stream, c, Op::src(args), qp);
-          ctx->st.quantised();
-        }
-        if (ctx->splitBuild == 8) {  // the op rides on the build
+        const vec4<N> *ps = Op::src(args);
+        const uint2 *qp = ensure_qpos<N>(ctx, c, ps);
+        if (ctx->splitBuild == 8) {
           // (staging depth 32 and four survivors per drain trip: measured best of 16 / 24 / 32 x 2 / 4 / 6 / 8)
 #ifndef PBF_BUILD_LMAX
 #define PBF_BUILD_LMAX 32
 #endif
-          hipLaunchKernelGGL((k_build_lists_op<N, Op, 4, PBF_BUILD_LMAX, 4>), g, b, 0, ctx->stream, c, args, Op::src(args), qp, args.type, key, table, nbr_lists(ctx, true));
+          launch_build_lists<N, Op, 4, PBF_BUILD_LMAX, 4>(ctx, c, args, ps, qp, args.type, key, table);
           LAUNCH_CHECK(ctx);
           return PBF_OK;
         }
+        // survivors per drain trip of a build that only stores them
+#ifndef PBF_LISTONLY_FW
+#define PBF_LISTONLY_FW 1
+#endif
+        using Lists = ListOnlyOp<N>;
+        constexpr int FW = PBF_LISTONLY_FW;
+        const typename Lists::Args only{args.type};
         StageTimer tb(ctx, ST_BUILD);
         if (ctx->splitBuild == 4)
-          hipLaunchKernelGGL((k_build_lists_q<N, 2>), g, b, 0, ctx->stream, c, Op::src(args), qp, args.type, key, table, nbr_lists(ctx, true));
+          launch_build_lists<N, Lists, 2, 16, FW>(ctx, c, only, ps, qp, args.type, key, table);
         else  // staging depth (option "list_max", default 32: one flush for most particles beats the two more workgroups per CU that 16 leaves room for: -2 % per step)
           switch (ctx->listMax ? ctx->listMax : 32u) {
-            case 16: hipLaunchKernelGGL((k_build_lists_q<N, 4, 16>), g, b, 0, ctx->stream, c, Op::src(args), qp, args.type, key, table, nbr_lists(ctx, true)); break;
-            case 24: hipLaunchKernelGGL((k_build_lists_q<N, 4, 24>), g, b, 0, ctx->stream, c, Op::src(args), qp, args.type, key, table, nbr_lists(ctx, true)); break;
-            default: hipLaunchKernelGGL((k_build_lists_q<N, 4, 32>), g, b, 0, ctx->stream, c, Op::src(args), qp, args.type, key, table, nbr_lists(ctx, true)); break;
+            case 16: launch_build_lists<N, Lists, 4, 16, FW>(ctx, c, only, ps, qp, args.type, key, table); break;
+            case 24: launch_build_lists<N, Lists, 4, 24, FW>(ctx, c, only, ps, qp, args.type, key, table); break;
+            default: launch_build_lists<N, Lists, 4, 32, FW>(ctx, c, only, ps, qp, args.type, key, table); break;
           }
       }
       from_lists();
@@ -916,11 +953,7 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
     // is inversely proportional to that number (measured: 1 024 records 68 us, 768 61 us, 640 51 us, 576 51 us)
     const uint32_t cap = ctx->diffuseCap ? ctx->diffuseCap : 640u;
     const size_t lds = size_t(cap + 8) * sizeof(vec4<N>) + size_t(DIFFUSE_ROW_THREADS) * (4 * sizeof(N) + 4) + cap + 8;  // (+ 8 records / types: the fold reads ahead)
-    static size_t attrSet = 0;  // per instantiation
-    if (lds > attrSet) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_diffuse_rows<N>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-      attrSet = lds;
-    }
+    if (int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(k_diffuse_rows<N>), lds)) return rc;
     const uint32_t perCU = uint32_t(std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / (lds + 256))));
     const uint32_t blocks = std::max(8u, (uint32_t(ctx->numCUs) * perCU) & ~7u);  // (the kernel deals segments per XCD: a multiple of 8)
     hipLaunchKernelGGL((k_diffuse_rows<N>), dim3(blocks), dim3(DIFFUSE_ROW_THREADS), lds, ctx->stream, c,
@@ -1032,14 +1065,10 @@ template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *
   StageTimer t(ctx, ST_DELTA);
   const int s = ctx->st.cur;
   if (ctx->st.delta_on_rows()) {  // list-driven delta-p on the row-major copy
-    const dim3 g = grid_for(ctx->n), b(BLOCK);
-    const RowWalk rw = row_walk<N>(ctx);
     const int rin = ctx->st.rcur, rout = 1 - rin;
-    const NbrLists ls = nbr_lists(ctx, false);
     const uint32_t *key = ctx->key[s].as<const uint32_t>(), *table = ctx->table.as<const uint32_t>();
     typename Op::Args a{ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()};
-    if (ctx->pipeline > 0) hipLaunchKernelGGL((k_gather_from_lists<N, Op, true, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
-    else hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, true>), g, b, 0, ctx->stream, c, a, key, table, ls, rw);
+    launch_from_lists<N, Op, true>(ctx, c, a, key, table, row_walk<N>(ctx));
     LAUNCH_CHECK(ctx);
     ctx->st.pstar_moved(/*rows=*/true, rout);
     return PBF_OK;

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(BLOCK) void k_scan_apply(ScanJobs jobs) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Quantised positions (the list build's 8-byte candidates, see k_build_lists_q): written by every producer of a
+// Quantised positions (the list build's 8-byte candidates, see k_quantise): written by every producer of a
 // sorted pStar — the sort's move, delta-p's epilogue, the slab refresh — so no pass of its own is needed.
 // ------------------------------------------------------------------------------------------------
 constexpr int QPOS_BITS = 11;                       // sub-cell resolution h / 2048
@@ -263,6 +263,31 @@ template <typename N> __device__ inline uint2 quantise_position(const StepConsts
   const uint32_t x = uint32_t(int32_t(fx)), y = uint32_t(int32_t(fy)), z = uint32_t(int32_t(fz));
   return make_uint2((x & 0xFFFFu) | (y << 16), z & 0xFFFFu);
 }
+// |d|^2 of two packed int16 pairs: v_dot2_i32_i16 with an inline-zero / register addend (the builtin
+// lowers to the accumulate-in-place form and spends a v_mov on the zero)
+__device__ inline int qdot2(uint32_t d) {
+  int r;
+  asm("v_dot2_i32_i16 %0, %1, %1, 0" : "=v"(r) : "v"(d));
+  return r;
+}
+__device__ inline int qdot2(uint32_t d, int acc) {
+  int r;
+  asm("v_dot2_i32_i16 %0, %1, %1, %2" : "=v"(r) : "v"(d), "v"(acc));
+  return r;
+}
+// The list builders' candidate test, the same in every one of them: is the candidate (qx, qy) within QPOS_T units of the
+// walker `own`?  Differences modulo 2^16 per axis, squared and summed by two v_dot2; a walker whose own coordinates are
+// not usable takes every candidate.
+struct QuantFilter {
+  qpair axy, azw;
+  uint32_t t2;
+  __device__ QuantFilter(uint2 own, bool usable)
+      : axy(__builtin_bit_cast(qpair, own.x)), azw(__builtin_bit_cast(qpair, own.y)), t2(usable ? QPOS_T * QPOS_T : 0xFFFFFFFFu) {}
+  __device__ bool within(uint32_t qx, uint32_t qy) const {
+    const qpair dxy = __builtin_bit_cast(qpair, qx) - axy, dzw = __builtin_bit_cast(qpair, qy) - azw;
+    return uint32_t(qdot2(__builtin_bit_cast(uint32_t, dzw), qdot2(__builtin_bit_cast(uint32_t, dxy)))) <= t2;
+  }
+};
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1599,7 +1624,7 @@ __global__ __launch_bounds__(BLOCK) void k_gather_lists(StepConsts<N> c, typenam
   if constexpr (FUSED) extra.end(c, xargs, i);
 }
 
-// Neighbour-list build on its own (no pair terms), on 8-byte quantised positions -------------------------------
+// The neighbour-list builds test their candidates on 8-byte quantised positions ------------------------------
 // The build is bound by the texture-address path (64 lanes x 16 B per candidate load), so the test
 // runs on a compact copy of pStar: per axis the LOW 16 bits of floor((p - gridMin) * 2048 / h).
 // Differences are taken modulo 2^16 (v_pk_sub_i16), i.e. exact whenever the true separation is below
@@ -1629,120 +1654,49 @@ struct __attribute__((aligned(4))) TablePair {
 struct __attribute__((aligned(4))) TableTriple {
   uint32_t t0, t1, t2;  // table[code .. code + 2]
 };
-// |d|^2 of two packed int16 pairs: v_dot2_i32_i16 with an inline-zero / register addend (the builtin
-// lowers to the accumulate-in-place form and spends a v_mov on the zero)
-__device__ inline int qdot2(uint32_t d) {
-  int r;
-  asm("v_dot2_i32_i16 %0, %1, %1, 0" : "=v"(r) : "v"(d));
-  return r;
-}
-__device__ inline int qdot2(uint32_t d, int acc) {
-  int r;
-  asm("v_dot2_i32_i16 %0, %1, %1, %2" : "=v"(r) : "v"(d), "v"(acc));
-  return r;
-}
 constexpr uint32_t QPOS_PAD = 64;  // spare qpos entries: tail pairs of a run read (and mask) what follows it
 
-template <typename N, int W, int LMAX = 16>
-__global__ __launch_bounds__(BLOCK) void k_build_lists_q(StepConsts<N> c, const vec4<N> *__restrict__ pstar,
-                                                         const uint2 *__restrict__ qpos,
-                                                         const uint8_t *__restrict__ type,
-                                                         const uint32_t *__restrict__ key,
-                                                         const uint32_t *__restrict__ table,
-                                                         NbrLists lists) {
-  static_assert(4 * W + 2 <= QPOS_PAD, "qpos padding");
-  __shared__ uint32_t list[(LMAX + 2 * W) * BLOCK];  // per-lane staging: a trip appends up to 2 W past LMAX - 1
-  const uint32_t tid = threadIdx.x;
-  const uint32_t chunk = xcd_chunk();
-  const uint32_t i = chunk * BLOCK + tid;
-  if (i >= c.n) return;
-  if (c.hasObstacles && type[i] != 0) {
-    lists.count[i] = 0;
-    return;
-  }
-  // 32-bit byte offsets from uniform bases: one shift per address
-  const char *qbase = reinterpret_cast<const char *>(qpos), *tbase = reinterpret_cast<const char *>(table);
-  bool usable;
-  const uint2 qa = quantise_position<N>(c, pstar[i], &usable);
-  const qpair axy = __builtin_bit_cast(qpair, qa.x), azw = __builtin_bit_cast(qpair, qa.y);
-  const uint32_t t2 = usable ? QPOS_T * QPOS_T : 0xFFFFFFFFu;
-  auto within = [&](uint32_t qx, uint32_t qy) {
-    const qpair dxy = __builtin_bit_cast(qpair, qx) - axy, dzw = __builtin_bit_cast(qpair, qy) - azw;
-    return uint32_t(qdot2(__builtin_bit_cast(uint32_t, dzw), qdot2(__builtin_bit_cast(uint32_t, dxy)))) <= t2;
-  };
-  NbrWriter wr(lists, chunk, tid);
-  uint32_t written = 0, nl = 0;
-  auto flush = [&]() {
-    wr.reserve(lists, written, nl);
-    for (uint32_t q = 0; __any(q < nl); ++q) wr.put(written + q, list[q * BLOCK + tid], q < nl);
-    written += nl;
-    nl = 0;
-  };
-  // A (dy, dz) row of three x cells is TWO runs of the sorted array: the cells (2m, 2m + 1) have
-  // adjacent codes, so for an odd own x the row is [x-1, x] + [x+1], for an even one [x-1] + [x, x+1].
-  // Two loads per row: table[pair .. pair + 2] and table[single .. single + 1] (the table keeps entries
-  // up to tableN + 1).  A cell outside the table, and the table's last cell, are empty (sph.hpp:206-208).
-  const uint32_t k0 = key[i];
-  const Neigh nb = neigh_codes(k0);
-  const bool odd = (k0 & 1u) != 0u;
-  const uint32_t xPair = odd ? nb.xs[0] : nb.xs[1], xSingle = odd ? nb.xs[2] : nb.xs[0];
-  struct Row {
-    uint32_t sA, lA, sB, lB;
-  };
-  auto load_row = [&](int r) {
-    const uint32_t yz = nb.ys[r % 3] | nb.zs[r / 3];
-    const uint32_t cP = xPair | yz, cS = xSingle | yz;
-    const TableTriple tp = *reinterpret_cast<const TableTriple *>(tbase + min(cP, c.tableN) * 4u);
-    const TablePair ts = *reinterpret_cast<const TablePair *>(tbase + min(cS, c.tableN) * 4u);
-    const uint32_t lP0 = (cP + 1u) < c.tableN ? tp.t1 - tp.t0 : 0u, lP1 = (cP + 2u) < c.tableN ? tp.t2 - tp.t1 : 0u;
-    const uint32_t sP = lP0 ? tp.t0 : tp.t1, lP = lP0 + lP1;
-    const uint32_t lS = (cS + 1u) < c.tableN ? ts.t1 - ts.t0 : 0u;
-    Row row;
-    row.sA = odd ? sP : ts.t0, row.lA = odd ? lP : lS;
-    row.sB = odd ? ts.t0 : sP, row.lB = odd ? lS : lP;
-    return row;
-  };
-  Row next = load_row(0);
+// One trip of a list-driven drain: the W list entries at slots q .. q + W - 1 (fetch(slot); slots from `end` on are padding:
+// the walker itself, masked), then their W candidates — all gathers in flight together — then, between the loads and
+// their first use, whatever the caller does with the entries (put(slot, entry, valid): a builder stores them to the row),
+// then the W pair terms, which interleave.
+template <int W, typename N, typename Op, typename Fetch, typename Put>
+__device__ inline void list_trip(const StepConsts<N> &c, const typename Op::Args &args, Op &op, uint32_t self, uint32_t q,
+                                 uint32_t end, Fetch &&fetch, Put &&put) {
+  uint32_t b[W];
+  typename Op::Src cnd[W];
 #pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    const Row row = next;
-    if (r < 8) next = load_row(r + 1);
-    // One slot sequence for the row, walked in PAIRS (slot 2j, 2j + 1 -> one 16-byte load): run A is
-    // padded to an even length so that no pair straddles the two runs; the pad slot is masked.
-    const uint32_t lA = row.lA, lAe = (lA + 1u) & ~1u, L = lAe + row.lB, oB = row.sB - lAe;
-    for (uint32_t t = 0; __any(t < L); t += 2 * W) {
-      if (t < L) {
-        uint32_t b[W], lim[W];
-        QPair cnd[W];
+  for (uint32_t w = 0; w < W; ++w) b[w] = q + w < end ? fetch(q + w) : self;
 #pragma unroll
-        for (uint32_t w = 0; w < W; ++w) {
-          const uint32_t sl = t + 2 * w;  // slots past L read what follows run B (QPOS_PAD) and are masked
-          const bool inA = sl < lAe;
-          b[w] = sl + (inA ? row.sA : oB);
-          lim[w] = inA ? lA : L;
-          cnd[w] = *reinterpret_cast<const QPair *>(qbase + b[w] * 8u);
-        }
+  for (uint32_t w = 0; w < W; ++w) cnd[w] = Op::load(args, b[w]);
 #pragma unroll
-        for (uint32_t w = 0; w < W; ++w) {
-          const bool hit0 = (t + 2 * w < lim[w]) & within(cnd[w].ax, cnd[w].ay);
-          list[nl * BLOCK + tid] = b[w];  // branch-free append: the slot is kept only on a hit
-          nl += hit0 ? 1u : 0u;
-          const bool hit1 = (t + 2 * w + 1 < lim[w]) & within(cnd[w].bx, cnd[w].by);
-          list[nl * BLOCK + tid] = b[w] + 1u;
-          nl += hit1 ? 1u : 0u;
-        }
-      }
-      if (__any(nl >= uint32_t(LMAX))) flush();
-    }
-  }
-  flush();
-  lists.count[i] = wr.finish(written);
+  for (uint32_t w = 0; w < W; ++w) put(q + w, b[w], q + w < end);
+#pragma unroll
+  for (uint32_t w = 0; w < W; ++w) op.add_bf(c, cnd[w], q + w < end);
+}
+template <int W, typename N, typename Op, typename Fetch>
+__device__ inline void list_trip(const StepConsts<N> &c, const typename Op::Args &args, Op &op, uint32_t self, uint32_t q,
+                                 uint32_t end, Fetch &&fetch) {
+  list_trip<W>(c, args, op, self, q, end, fetch, [](uint32_t, uint32_t, bool) {});
 }
 
-// The same build with an op riding on it (option split_build = 8): the survivors staged in LDS are not only flushed to
-// their row but folded through the op's exact pair terms on the way — lambda needs no launch and no list read of its own,
-// and its arithmetic runs in the issue slots the build (bound by the texture-address path, 4 waves per SIMD by its LDS)
-// leaves idle.  Same candidates in the same order as the list-driven reader: the same bits.
+// The op of a build that is a launch of its own (option split_build = 4 / 5): nothing rides, the lists alone are written.
+template <typename N> struct ListOnlyOp {
+  struct Src {};
+  struct Args {
+    const uint8_t *type;
+  };
+  __device__ static Src load(const Args &, uint32_t) { return {}; }
+  __device__ bool begin(const StepConsts<N> &c, const Args &a, uint32_t i) { return !(c.hasObstacles && a.type[i] != 0); }
+  __device__ void add_bf(const StepConsts<N> &, const Src &, bool) {}
+  __device__ void end(const StepConsts<N> &, const Args &, uint32_t) {}
+};
+
+// The list build on the Morton-sorted arrays, with an op riding on it (option split_build = 8: LambdaOp; 4 / 5:
+// ListOnlyOp): the survivors staged in LDS are not only flushed to their row but folded through the op's exact pair terms
+// on the way — lambda needs no launch and no list read of its own, and its arithmetic runs in the issue slots the build
+// (bound by the texture-address path, 4 waves per SIMD by its LDS) leaves idle.  Same candidates in the same order as the
+// list-driven reader: the same bits.
 template <typename N, typename Op, int W, int LMAX = 32, int FW = 4>
 __global__ __launch_bounds__(BLOCK) void k_build_lists_op(StepConsts<N> c, typename Op::Args args, const vec4<N> *__restrict__ pstar,
                                                          const uint2 *__restrict__ qpos,
@@ -1765,29 +1719,15 @@ __global__ __launch_bounds__(BLOCK) void k_build_lists_op(StepConsts<N> c, typen
   const char *qbase = reinterpret_cast<const char *>(qpos), *tbase = reinterpret_cast<const char *>(table);
   bool usable;
   const uint2 qa = quantise_position<N>(c, pstar[i], &usable);
-  const qpair axy = __builtin_bit_cast(qpair, qa.x), azw = __builtin_bit_cast(qpair, qa.y);
-  const uint32_t t2 = usable ? QPOS_T * QPOS_T : 0xFFFFFFFFu;
-  auto within = [&](uint32_t qx, uint32_t qy) {
-    const qpair dxy = __builtin_bit_cast(qpair, qx) - axy, dzw = __builtin_bit_cast(qpair, qy) - azw;
-    return uint32_t(qdot2(__builtin_bit_cast(uint32_t, dzw), qdot2(__builtin_bit_cast(uint32_t, dxy)))) <= t2;
-  };
+  const QuantFilter filter(qa, usable);
   NbrWriter wr(lists, chunk, tid);
   uint32_t written = 0, nl = 0;
   auto flush = [&]() {
     wr.reserve(lists, written, nl);
-    for (uint32_t q = 0; __any(q < nl); q += FW) {  // FW survivors per trip: their gathers and pair terms interleave
-      uint32_t b[FW];
-      typename Op::Src cnd[FW];
-#pragma unroll
-      for (uint32_t w = 0; w < FW; ++w) b[w] = q + w < nl ? list[(q + w) * BLOCK + tid] : i;
-#pragma unroll
-      for (uint32_t w = 0; w < FW; ++w) cnd[w] = Op::load(args, b[w]);
-#pragma unroll
-      for (uint32_t w = 0; w < FW; ++w)
-        wr.put(written + q + w, b[w], q + w < nl);
-#pragma unroll
-      for (uint32_t w = 0; w < FW; ++w) op.add_bf(c, cnd[w], q + w < nl);
-    }
+    for (uint32_t q = 0; __any(q < nl); q += FW)  // FW survivors per trip: their gathers and pair terms interleave
+      list_trip<FW>(
+          c, args, op, i, q, nl, [&](uint32_t k) { return list[k * BLOCK + tid]; },
+          [&](uint32_t k, uint32_t e, bool valid) { wr.put(written + k, e, valid); });
     written += nl;
     nl = 0;
   };
@@ -1837,10 +1777,10 @@ __global__ __launch_bounds__(BLOCK) void k_build_lists_op(StepConsts<N> c, typen
         }
 #pragma unroll
         for (uint32_t w = 0; w < W; ++w) {
-          const bool hit0 = (t + 2 * w < lim[w]) & within(cnd[w].ax, cnd[w].ay);
+          const bool hit0 = (t + 2 * w < lim[w]) & filter.within(cnd[w].ax, cnd[w].ay);
           list[nl * BLOCK + tid] = b[w];  // branch-free append: the slot is kept only on a hit
           nl += hit0 ? 1u : 0u;
-          const bool hit1 = (t + 2 * w + 1 < lim[w]) & within(cnd[w].bx, cnd[w].by);
+          const bool hit1 = (t + 2 * w + 1 < lim[w]) & filter.within(cnd[w].bx, cnd[w].by);
           list[nl * BLOCK + tid] = b[w] + 1u;
           nl += hit1 ? 1u : 0u;
         }
@@ -2122,12 +2062,7 @@ __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typena
   // (the walker's own coordinates may be unusable — beyond +-2^22 units: it then takes everything; recomputed like the Morton build)
   bool usable;
   (void)quantise_position<N>(c, Op::load(args, i), &usable);
-  const qpair axy = __builtin_bit_cast(qpair, qa.x), azw = __builtin_bit_cast(qpair, qa.y);
-  const uint32_t t2 = usable ? QPOS_T * QPOS_T : 0xFFFFFFFFu;
-  auto within = [&](uint32_t qx, uint32_t qy) {
-    const qpair dxy = __builtin_bit_cast(qpair, qx) - axy, dzw = __builtin_bit_cast(qpair, qy) - azw;
-    return uint32_t(qdot2(__builtin_bit_cast(uint32_t, dzw), qdot2(__builtin_bit_cast(uint32_t, dxy)))) <= t2;
-  };
+  const QuantFilter filter(qa, usable);
   NbrWriter wr(lists, chunk, tid);
   uint32_t *const blockRows = lists.rows + size_t(chunk) * NBR_ROWS * BLOCK;  // (wave-uniform; wr.row = blockRows + tid)
   // the staging list's write cursor as an LDS ADDRESS (slot s of this lane at lbase + s * SLOT): appending is one store through
@@ -2178,7 +2113,7 @@ __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typena
     if (slow)
       row_for_each_candidate(rw, i, [&](uint32_t b) {
         const uint2 q = qpos[b];
-        if (within(q.x, q.y)) {
+        if (filter.within(q.x, q.y)) {
           if (cur >= lfull) {  // (lane-private drain: the others of the wave are not here)
             const uint32_t nl = uint32_t(cur - lbase) / SLOT;
             wr.reserve(lists, written, nl);
@@ -2213,9 +2148,9 @@ __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typena
           for (uint32_t w = 0; w < W; ++w) cnd[w] = *reinterpret_cast<const QPair *>(qbase + off + 16u * w);  // (slots past L: padding / the next run, masked)
 #pragma unroll
           for (uint32_t w = 0; w < W; ++w) {
-            const bool hit0 = (t + 2 * w < L) & within(cnd[w].ax, cnd[w].ay);
+            const bool hit0 = (t + 2 * w < L) & filter.within(cnd[w].ax, cnd[w].ay);
             append(cur, b0 + 2 * w, hit0);  // branch-free: the slot is kept only on a hit
-            const bool hit1 = (t + 2 * w + 1 < L) & within(cnd[w].bx, cnd[w].by);
+            const bool hit1 = (t + 2 * w + 1 < L) & filter.within(cnd[w].bx, cnd[w].by);
             append(cur, b0 + 2 * w + 1u, hit1);
           }
         }
@@ -2344,6 +2279,8 @@ __global__ __launch_bounds__(BLOCK) void k_gather_from_lists(StepConsts<N> c, ty
 #define PBF_READER_W 8
 #endif
     constexpr uint32_t RW = sizeof(N) == 4 ? PBF_READER_W : 4;
+    // (list_trip's steps, written out: behind a function the compiler drops the first slot's bound test and allocates this
+    // kernel's scalar registers differently — the iteration's hottest reader keeps the text it was measured with)
     for (uint32_t q = 0; q < head; q += RW) {
       uint32_t b[RW];
       typename Op::Src cnd[RW];

@@ -10,8 +10,8 @@
 //     sorted arrays — and stages the brick's 6 x 6 x 6 halo of cells into LDS once, x-fastest, so that the three x
 //     cells of a (dy, dz) row are ONE contiguous LDS run (cell start / end offsets from the grid table, scanned in LDS);
 //   * k_tile_build: the tile holds the 8-byte quantised positions; every home particle walks its 9 runs out of LDS
-//     in the reference's order and records the TILE SLOTS of the candidates inside h (superset test, as
-//     k_build_lists_q) into its neighbour-list row in HBM;
+//     in the reference's order and records the TILE SLOTS of the candidates inside h (superset test: QuantFilter,
+//     as every builder) into its neighbour-list row in HBM;
 //   * k_tile_from_lists<Op>: the tile holds the candidates' pStar (+ lambda); every home particle reads its row and
 //     takes the candidates from LDS by slot — same candidates, same order, same op code as every other gather
 //     kernel, hence the same bits.
@@ -19,7 +19,7 @@
 // ends when the ticket passes the list's end, an exit every wave reaches.  A brick whose halo holds more than `cap`
 // records (a pile-up) is handled with global loads by the same workgroup: its rows then hold global indices — every
 // kernel of the iteration takes the same decision from the same table.  Particles in no cell (key >= tableN) are
-// swept the same way.  Rows are the ones of k_build_lists_q / k_gather_from_lists: [i / 256][slot][i % 256].
+// swept the same way.  Rows are the ones of k_build_lists_op / k_gather_from_lists: [i / 256][slot][i % 256].
 #pragma once
 
 #include "pbf_kernels.hpp"
@@ -90,7 +90,7 @@ __device__ inline const uint32_t *nbr_row(const uint32_t *nbrList, uint32_t i) {
   return nbrList + size_t(i / BLOCK) * NBR_ROWS * BLOCK + (i % BLOCK);
 }
 
-// One particle's list with global loads and a store per hit: the same list k_build_lists_q writes (global indices, walk
+// One particle's list with global loads and a store per hit: the same list k_build_lists_op writes (global indices, walk
 // order).  Only for bricks beyond the tile and particles in no cell.
 template <typename N>
 __device__ inline void build_one_plain(const StepConsts<N> &c, const vec4<N> *__restrict__ pstar,
@@ -103,14 +103,12 @@ __device__ inline void build_one_plain(const StepConsts<N> &c, const vec4<N> *__
   }
   bool usable;
   const uint2 qa = quantise_position<N>(c, pstar[i], &usable);
-  const qpair axy = __builtin_bit_cast(qpair, qa.x), azw = __builtin_bit_cast(qpair, qa.y);
-  const uint32_t t2 = usable ? QPOS_T * QPOS_T : 0xFFFFFFFFu;
+  const QuantFilter filter(qa, usable);
   uint32_t *row = nbr_row(nbrList, i);
   uint32_t written = 0;
   for_each_candidate(key[i], table, c.tableN, [&](uint32_t b) {
     const uint2 q = qpos[b];
-    const qpair dxy = __builtin_bit_cast(qpair, q.x) - axy, dzw = __builtin_bit_cast(qpair, q.y) - azw;
-    if (uint32_t(qdot2(__builtin_bit_cast(uint32_t, dzw), qdot2(__builtin_bit_cast(uint32_t, dxy)))) <= t2) {
+    if (filter.within(q.x, q.y)) {
       if (written < NBR_ROWS) row[written * BLOCK] = b;
       ++written;
     }
@@ -131,16 +129,8 @@ __device__ inline void from_lists_one_global(const StepConsts<N> &c, const typen
   if (cnt == NBR_OVERFLOW) {
     for_each_candidate(key[i], table, c.tableN, [&](uint32_t b) { op.add(c, Op::load(args, b)); });
   } else {
-    for (uint32_t q = 0; q < cnt; q += 4) {
-      uint32_t b[4];
-      typename Op::Src cnd[4];
-#pragma unroll
-      for (uint32_t w = 0; w < 4; ++w) b[w] = q + w < cnt ? mine[(q + w) * BLOCK] : i;
-#pragma unroll
-      for (uint32_t w = 0; w < 4; ++w) cnd[w] = Op::load(args, b[w]);
-#pragma unroll
-      for (uint32_t w = 0; w < 4; ++w) op.add_bf(c, cnd[w], q + w < cnt);
-    }
+    for (uint32_t q = 0; q < cnt; q += 4)
+      list_trip<4>(c, args, op, i, q, cnt, [&](uint32_t k) { return mine[k * BLOCK]; });
   }
   op.end(c, args, i);
 }
@@ -196,12 +186,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_tile_build(StepConsts<N> c, co
       }
       bool usable;
       const uint2 qa = quantise_position<N>(c, pstar[i], &usable);
-      const qpair axy = __builtin_bit_cast(qpair, qa.x), azw = __builtin_bit_cast(qpair, qa.y);
-      const uint32_t t2 = usable ? QPOS_T * QPOS_T : 0xFFFFFFFFu;
-      auto within = [&](uint32_t qx, uint32_t qy) {
-        const qpair dxy = __builtin_bit_cast(qpair, qx) - axy, dzw = __builtin_bit_cast(qpair, qy) - azw;
-        return uint32_t(qdot2(__builtin_bit_cast(uint32_t, dzw), qdot2(__builtin_bit_cast(uint32_t, dxy)))) <= t2;
-      };
+      const QuantFilter filter(qa, usable);
       uint32_t *row = nbr_row(nbrList, i);
       // the staging list's write cursor as an LDS byte address: one select + one add per candidate
       constexpr uint32_t SLOT = THREADS * 2u;  // bytes per staging slot row
@@ -228,7 +213,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_tile_build(StepConsts<N> c, co
             for (uint32_t w = 0; w < WAYS; ++w) cnd[w] = src[w];
 #pragma unroll
             for (uint32_t w = 0; w < WAYS; ++w) {
-              const bool hit = (j + w < e) & within(cnd[w].x, cnd[w].y);
+              const bool hit = (j + w < e) & filter.within(cnd[w].x, cnd[w].y);
               *reinterpret_cast<uint16_t *>(lbase + cur) = uint16_t(j + w);  // branch-free append: kept only on a hit
               cur += hit ? SLOT : 0u;
             }

@@ -1,4 +1,4 @@
-"""The list build tests candidates on 8-byte quantised positions (k_quantise / k_build_lists_q,
+"""The list build tests candidates on 8-byte quantised positions (k_quantise / QuantFilter,
 pbf-sph_amd/csrc/pbf_kernels.hpp).  Its only obligation is to never drop a pair the exact fp test accepts.
 This restates the quantisation in numpy float32 — constants parsed from the kernel source — and attacks it
 with pairs at and just inside distance h, at small and large grid coordinates and below the grid minimum."""

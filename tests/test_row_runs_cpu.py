@@ -1,4 +1,4 @@
-"""k_build_lists_q walks a (dy, dz) row of three x cells as TWO runs of the sorted array (pair of adjacent Morton
+"""k_build_lists_op walks a (dy, dz) row of three x cells as TWO runs of the sorted array (pair of adjacent Morton
 codes + single cell, chosen by the parity of the own x) fetched with two table loads.  This restates that
 row logic in numpy and checks, for every cell of small and edge-case grids, that the candidate sequence equals
 the reference's per-cell walk (sph.hpp:206-234: x fastest, a cell outside the table and the table's last cell
@@ -39,7 +39,7 @@ def reference_walk(key, table, tn):
 
 
 def two_run_walk(key, table, tn):
-    """load_row + the slot sequence of k_build_lists_q (pairs, run A padded to an even length)."""
+    """load_row + the slot sequence of k_build_lists_op (pairs, run A padded to an even length)."""
     xs, ys, zs = neigh(key)
     odd = key & 1
     x_pair, x_single = (xs[0], xs[2]) if odd else (xs[1], xs[0])
