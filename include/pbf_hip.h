@@ -463,7 +463,25 @@ int pbf_reset_stage_times(pbf_ctx *ctx);
  * Runs on the state the last pbf_step left (its grid table is still valid): scalar field on a lattice of
  * floor(extent * resolution) + 1 nodes per axis, triangles per cube, emission in cube order.
  * pbf_surface returns the triangle count; pbf_download_mesh copies 3 vertices per triangle:
- * vs / ns = 9 values of N per triangle, cs = 12 (the reference's ColouredMesh, src/sph.hpp:105-112). */
+ * vs / ns = 9 values of N per triangle, cs = 12 (the reference's ColouredMesh, src/sph.hpp:105-112).
+ *
+ * Slab mode (a ctx attached with pbf_slab_attach, more than one rank):
+ *   - pbf_surface is COLLECTIVE: every rank calls it with the same params and mc (three exchange rounds: the copies'
+ *     colours, then the {v, normal} and the colour halves of one node plane).
+ *   - It must follow pbf_slab_step(s) directly, while the copies of the neighbours' boundary columns are still in the
+ *     arrays: after pbf_download / pbf_upload (they drop the copies) it returns PBF_ERR_STATE and exchanges nothing.  It may
+ *     be repeated, with other mc, until then.
+ *   - Rank r owns the node planes x of the global lattice with cuts[r] <= floor(N(x) / N(resolution)) < cuts[r + 1] and
+ *     returns the triangles of the cubes whose lower plane is one of them.  Concatenated in rank order, the ranks' meshes
+ *     are the global mesh in the global cube order (x-major).  A rank without particles returns its planes like far nodes
+ *     of a single device (v = 0, NaN normals and colours) and no triangle.
+ *   - pbf_read_lattice returns sample[0] = the rank's own planes, plus one where node planes remain to its right: the
+ *     first plane of the right-hand neighbour, received from it, byte for byte.  sample[1], sample[2] are the global ones.
+ *   - The indexed mesh is refused (pbf_surface_indexed below).
+ *   - PBF_ERR_INVALID, on every rank alike and before anything is exchanged (pbf_comm_rounds unchanged, the state intact, a
+ *     following pbf_surface at a workable resolution succeeds), when a rank with a left neighbour owns no node plane while
+ *     planes remain to its right — a slab narrower than one lattice step, e.g. one column at resolution 0.7: the plane its
+ *     left neighbour needs belongs to a rank the one-hop exchange does not reach.  A rightmost rank without planes is legal. */
 typedef struct pbf_mc_params {
   double resolution, isolevel, particle_size, particle_influence; /* sph::McParams */
 } pbf_mc_params;

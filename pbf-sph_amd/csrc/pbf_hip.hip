@@ -3214,7 +3214,23 @@ int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uin
       while (uint64_t(N(x) / m.res) < col) ++x;
       return std::min<uint64_t>(x, sampleG[0]);
     };
-    const uint64_t x0 = r > 0 ? first_node(ctx->cuts[r]) : 0, x1 = r + 1 < nr ? first_node(ctx->cuts[r + 1]) : sampleG[0];
+    // every rank's first node plane, from the cuts all ranks share: rank g owns the planes [firstX[g], firstX[g + 1])
+    std::vector<uint64_t> firstX(size_t(nr) + 1, 0);
+    for (int g = 1; g < nr; ++g) firstX[g] = first_node(ctx->cuts[g]);
+    firstX[nr] = sampleG[0];
+    // A rank between two others that owns no plane while nodes remain to its right cannot hand its left neighbour the plane
+    // that neighbour's last cubes need (it belongs to a rank further right; the exchange reaches one rank).  Refused on
+    // every rank alike, before anything is exchanged.  (A rank with no plane and none to its right is fine.)
+    for (int g = 1; g + 1 < nr; ++g)
+      if (firstX[g] == firstX[g + 1] && firstX[g + 1] < sampleG[0]) {
+        std::string cuts;
+        for (int k = 0; k <= nr; ++k) cuts += (k ? ", " : "") + std::to_string(ctx->cuts[k]);
+        return fail(ctx, PBF_ERR_INVALID,
+                    "pbf_surface in slab mode: rank " + std::to_string(g) + " (columns [" + std::to_string(ctx->cuts[g]) + ", " +
+                        std::to_string(ctx->cuts[g + 1]) + ") of the cuts {" + cuts + "}) owns no lattice node plane at resolution " +
+                        std::to_string(mp->resolution) + ": widen the slab or raise the resolution");
+      }
+    const uint64_t x0 = firstX[r], x1 = firstX[r + 1];
     hasRight = r + 1 < nr && x1 < sampleG[0];
     m.xoff = ctx->xoff, m.nodeX0 = uint32_t(x0), m.planes = uint32_t(x1 - x0);
     m.sample[0] = m.planes + (hasRight ? 1u : 0u);

@@ -34,6 +34,30 @@ PARAMS = {
     "cloud": [(2.0, 100.0, 25.0, 0.5), (1.5, 40.0, 25.0, 0.75), (1.0, 15.0, 25.0, 1.0), (3.0, 100.0, 25.0, 0.5)],
 }
 
+# The surface in slab mode (tests/test_slab_surface_cpu.py, tests/test_slab_surface_gpu.py): per case the scene, the
+# worker's --cuts, the cuts as cell columns, the precisions and the parameter sets in call order.  A set that begins with
+# "!" must be refused (an interior rank without a node plane).  Resolution 0.7 on `faces` (extent 10 on x: nodes in
+# the cells 0 1 2 4 5 7 8 10, so columns own one or no plane each); its isolevel 50 is near the median of v over the
+# nodes with hits (45; quartiles 31 and 66).
+FACES_07 = (0.7, 50.0, 25.0, 0.5)
+SLAB_PARAMS = {
+    "faces-3": dict(scene="faces", extent_x=10, cuts="c:3,7", columns=(0, 3, 7, 1024), fp64=(False, True),
+                    sets=PARAMS["faces"] + [FACES_07]),
+    # rank 2 is one column wide: its particles are in both neighbours' ghost sets
+    "faces-4": dict(scene="faces", extent_x=10, cuts="c:3,4,7", columns=(0, 3, 4, 7, 1024), fp64=(False, True),
+                    sets=PARAMS["faces"] + [("!",) + FACES_07, PARAMS["faces"][0]]),
+    # slab.column_of(210) = 6 runs through the obstacle sheet (columns 5 and 6), column_of(700) = 15 (1.4 + 0.2 rounds below
+    # 1.6) through the second cube
+    "obstacles-3": dict(scene="obstacles", extent_x=24, cuts="x:210,700", columns=(0, 6, 15, 1024), fp64=(False, True),
+                        sets=PARAMS["obstacles"][:2]),
+    # the cubes start in the columns 4-7 and 13-17 and spread to 2-9 and 12-19 by the third frame: rank 1 (columns 10-12)
+    # starts without a particle, steps with none, and is reached by migrants and copies from its right-hand neighbour
+    "blob-3": dict(scene="blob", extent_x=24, cuts="c:10,13", columns=(0, 10, 13, 1024), fp64=(False,), sets=PARAMS["blob"][:1]),
+    # nothing ever reaches column 20: ranks 1 and 2 own no particle and receive no copy, from the upload to the surface
+    "blob-empty": dict(scene="blob", extent_x=24, cuts="c:21,23", columns=(0, 21, 23, 1024), fp64=(False,),
+                       sets=PARAMS["blob"][:1]),
+}
+
 FACES_EXT = (10, 9, 8)
 ON_NODE = (8, 10, 6)            # lattice index of the node that carries a particle (resolution 2; (4, 5, 3) at 1)
 NEAR_NODE = (10, 9, 5)

@@ -3,8 +3,11 @@ Checks the N>1 host logic (cuts, migration, ghost copies, per-phase refresh, nei
 the union of the ranks' particles after S steps equals a single-rank run to summation-order noise,
 nothing is lost or duplicated, and particles really crossed the cut."""
 import os
+import queue
 import subprocess
 import sys
+import threading
+import time
 
 import numpy as np
 import pytest
@@ -12,7 +15,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def launch(world, out, *extra):
+def launch(world, out, *extra, timeout=600):
     port = 29500 + (os.getpid() % 2000)
     procs = []
     for r in range(world):
@@ -20,9 +23,33 @@ def launch(world, out, *extra):
                    OMP_NUM_THREADS="2")
         procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "slab_worker.py"), "--out", out, *extra],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = [p.communicate(timeout=600)[0] for p in procs]
-    # (the rank that fails FIRST holds the cause; the others only see their peer vanish)
-    assert all(p.returncode == 0 for p in procs), "\n".join(
+    # One watcher per rank drains its output (a rank must never block on a full pipe) and reports its exit.  The first
+    # failure, or the deadline, ends the remaining ranks at once: a rank stuck in an exchange with a vanished peer must
+    # not stay behind holding the device.
+    outs, ended = [""] * world, queue.Queue()
+
+    def watch(r):
+        outs[r] = procs[r].stdout.read()
+        ended.put(procs[r].wait())
+
+    watchers = [threading.Thread(target=watch, args=(r,), daemon=True) for r in range(world)]
+    for t in watchers:
+        t.start()
+    deadline = time.monotonic() + timeout
+    try:
+        for _ in range(world):
+            if ended.get(timeout=max(0.0, deadline - time.monotonic())) != 0:
+                break
+    except queue.Empty:
+        pass
+    finally:
+        late = [r for r, p in enumerate(procs) if p.poll() is None]
+        for r in late:
+            procs[r].kill()
+        for t in watchers:
+            t.join()
+    # (the rank that fails FIRST holds the cause; the others only see their peer vanish — or were ended here)
+    assert not late and all(p.returncode == 0 for p in procs), f"ranks ended by the launcher: {late}\n" + "\n".join(
         f"--- rank {r} (exit {p.returncode}) ---\n" + "\n".join(ln for ln in o.splitlines() if "socket.cpp" not in ln)[-1500:]
         for r, (p, o) in enumerate(zip(procs, outs)))
     return [np.load(os.path.join(out, f"rank{r}.npz")) for r in range(world)]
