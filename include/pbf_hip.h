@@ -513,6 +513,57 @@ int pbf_surface_indexed(pbf_ctx *ctx, const pbf_params *params, const pbf_mc_par
 int pbf_download_mesh_indexed(pbf_ctx *ctx, void *vs, void *ns, void *cs, uint32_t *tris);
 int pbf_map_mesh_indexed(pbf_ctx *ctx, const void **vs, const void **ns, const void **cs, const uint32_t **tris);
 
+/* ---- anisotropic-kernel surface: the iso-surface of Yu & Turk's field (no reference counterpart) -----------------------
+ * pbf_surface / pbf_surface_indexed with another scalar field: phi(a) = sum_j W(a - centre_j, G_j) over the ellipsoids of
+ * pbf_anisotropy_compute — flat where the fluid is a sheet, thin along a jet, smooth in the bulk — instead of the reference's
+ * sum size / |l|^infl over equal spheres, which stays what pbf_surface computes.  Only the field stage differs: the lattice
+ * geometry, the count, the scans, the emission (indexed != 0: one vertex per crossed edge, n_vertices required) and the rule
+ * that the two mesh kinds exclude each other are pbf_surface's, and pbf_download_mesh / pbf_map_mesh / their _indexed forms /
+ * pbf_read_lattice return this surface exactly as they return the stock one.
+ * The call discipline is pbf_anisotropy_compute's: its own call on the ctx stream, never part of a step or a captured
+ * hipGraph, no stage timer; a step after it, and a pbf_surface after it, produce the bytes they would have produced without.
+ * The same state and configuration give the same bytes under every setting of pbf_set_option.
+ *
+ * CONTRACT.  The field is a function of exactly these bytes: the arrays pbf_anisotropy_compute returns for the same state and
+ * `kernel` (centre, G, radii), the particles' positions, colours and types, and the predict-time cell table.  Everything in
+ * N, in the order written, not contracted (csrc/pbf_aniso_field.hpp holds the same text beside the code).
+ * Two DEVIATIONS from the paper: the support of pbf_anisotropy_compute is h, not 2 h; and each ellipsoid is shrunk uniformly
+ * by a factor f >= 1 (below) so that it stays inside the 27 cells a lattice node looks at.  The paper's m_j / rho_j is a
+ * constant here (the constraint holds the density at rho_0) and is absorbed into the isolevel — which therefore has no
+ * default: phi is 1 / (radii_1 radii_2 radii_3) at the centre of an isolated ellipsoid with f = 1.
+ *
+ * Record of fluid particle j, H = h * scale:
+ *   e = centre_j - pos_j (world);   disp = sqrt((e_x e_x + e_y e_y) + e_z e_z) / H;   f = max(1, radii_1 / (0.99 - disp))
+ *   G''_ab = G_ab * (f / scale)                      (world frame; largest semi-axis of |G''(a - centre_j)| < 1: H radii_1 / f,
+ *                                                    so the ellipsoid reaches at most disp + radii_1 / f <= 0.99 H from pos_j)
+ *   D = 1 / (((f f) f) ((radii_1 radii_2) radii_3))  (det(h f G): Yu & Turk's ||G|| normalisation)
+ *   rho2 = (((H radii_1) / f) ((H radii_1) / f)) * 1.5
+ *   An obstacle, a particle whose D or G'' is not finite (sigma_1 == 0 above) or one with disp >= 0.99 contributes nothing.
+ * Node a (coordinates and cell z as pbf_surface computes them): the candidates are the particles of the cells z - 1, z, z + 1
+ * per axis, a cell outside [0, extent - 1] SKIPPED (pbf_surface clamps it and visits face cells more than once; this field
+ * visits every cell once), slots in ascending order (x fastest), candidates in table order.  Per candidate:
+ *   d = a - centre;   no hit unless (d_x d_x + d_y d_y) + d_z d_z < rho2   (a conservative pre-test that never decides:
+ *                                                                          q2 < 1 implies |d| < H radii_1 / f)
+ *   y_a = (G''_ax d_x + G''_ay d_y) + G''_az d_z;   q2 = (y_x y_x + y_y y_y) + y_z y_z;   a hit iff q2 < 1
+ *   s = 1 - q2;   t = D ((s s) s);   phi += t
+ *   z_a = (G''_ax y_x + G''_ay y_y) + G''_az y_z;   g_a += ((-6 D) (s s)) z_a        (grad phi: points into the fluid)
+ *   C += t colour_j
+ * Stored: phi > 0: {phi, n}, n_a = (-g_a) / len with len = sqrt((g_x g_x + g_y g_y) + g_z g_z) (0 where len == 0): outwards,
+ * the stock convention — a value < isolevel is outside in both fields; colour C / phi.  Otherwise phi = 0, normal 0, colour 0:
+ * never NaN (pbf_surface stores NaN at a node without hits).
+ * Then every node with phi == 0 that has a 6-neighbour with phi > 0 takes as colour the sum of those neighbours' colours in
+ * the order -x +x -y +y -z +z divided by their number (its normal stays 0): the far end of a crossed edge has no hit when
+ * the support is compact, and the vertex colours would otherwise be mixed with zero.
+ *
+ * PBF_ERR_INVALID: a NULL argument; indexed without n_vertices; dt or scale <= 0; resolution or isolevel not finite or <= 0;
+ * what pbf_anisotropy_compute rejects in `kernel`; the lattice-size limits of pbf_surface / pbf_surface_indexed.
+ * PBF_ERR_STATE: no step has run or its table is stale; params describe another grid than the last step's; the ctx is
+ * slab-configured, attached or holds ghost copies.  On every error nothing is launched and the previous mesh and lattice stay
+ * readable.  pbf_count == 0 returns PBF_OK with zero triangles (after the argument and slab checks). */
+typedef struct pbf_aniso_surface { double resolution, isolevel; pbf_anisotropy kernel; } pbf_aniso_surface;
+int pbf_surface_anisotropic(pbf_ctx *ctx, const pbf_params *params, const pbf_aniso_surface *cfg,
+                            int indexed, uint64_t *n_vertices /* may be NULL unless indexed */, uint64_t *n_triangles);
+
 /* ---- multi-GPU: slab decomposition along x (no reference counterpart: it is single-device) ------
  * One process per GPU.  Every rank uses the GLOBAL grid (same pbf_params bounds), owns the cell columns
  * [xlo, xhi) and keeps a one-cell layer of COPIES ("ghosts", type bit PBF_TYPE_GHOST) of its x-neighbours'

@@ -10,6 +10,7 @@ The directory name has a hyphen (it mirrors the reference repo's name), so impor
 `load_package()` from tests/conftest.py / bench.py, or via importlib by path.
 """
 from .capi import (  # noqa: F401
+    AnisoSurface,
     Anisotropy,
     AnisotropyOut,
     BUF_DENSITY,

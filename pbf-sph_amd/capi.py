@@ -149,6 +149,11 @@ class AnisotropyOut(C.Structure):
                 ("neighbours", C.c_void_p)]
 
 
+class AnisoSurface(C.Structure):
+    """pbf_aniso_surface (include/pbf_hip.h)"""
+    _fields_ = [("resolution", C.c_double), ("isolevel", C.c_double), ("kernel", Anisotropy)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -216,6 +221,8 @@ _SIGS = {
     "pbf_map_mesh": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pbf_read_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_surface_indexed": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "pbf_surface_anisotropic": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(AnisoSurface), C.c_int, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64)]),
     "pbf_download_mesh_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_map_mesh_indexed": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_void_p)]),
@@ -603,20 +610,31 @@ class Solver:
         self._chk(self.L.pbf_read_buffer(self.ctx, BUF_OMEGA, _vp(a), a.nbytes), "read omega")
         return a[:, :3].copy()
 
-    def surface(self, p, mc=None):
-        """Marching cubes on the state the last step left -> dict(vs, ns, cs, sample, pn, c)."""
-        mc = mc or McParams()
-        nt = C.c_uint64()
-        self._chk(self.L.pbf_surface(self.ctx, C.byref(p), C.byref(mc), C.byref(nt)), "pbf_surface")
-        n = nt.value
-        vs, ns, cs = np.empty((3 * n, 3), self.dtype), np.empty((3 * n, 3), self.dtype), np.empty((3 * n, 4), self.dtype)
-        self._chk(self.L.pbf_download_mesh(self.ctx, _vp(vs), _vp(ns), _vp(cs)), "pbf_download_mesh")
+    def _read_lattice(self):
         smp = np.zeros(3, np.uint64)
         self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), None, None), "pbf_read_lattice")
         nn = int(smp.prod())
         pn, cc = np.empty((nn, 4), self.dtype), np.empty((nn, 4), self.dtype)
         self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), _vp(pn), _vp(cc)), "pbf_read_lattice")
-        return dict(vs=vs, ns=ns, cs=cs, sample=smp, pn=pn, c=cc)
+        return dict(sample=smp, pn=pn, c=cc)
+
+    def _read_soup(self, n):
+        vs, ns, cs = np.empty((3 * n, 3), self.dtype), np.empty((3 * n, 3), self.dtype), np.empty((3 * n, 4), self.dtype)
+        self._chk(self.L.pbf_download_mesh(self.ctx, _vp(vs), _vp(ns), _vp(cs)), "pbf_download_mesh")
+        return dict(vs=vs, ns=ns, cs=cs, **self._read_lattice())
+
+    def _read_indexed(self, v, t):
+        vs, ns, cs = np.empty((v, 3), self.dtype), np.empty((v, 3), self.dtype), np.empty((v, 4), self.dtype)
+        tris = np.empty((t, 3), np.uint32)
+        self._chk(self.L.pbf_download_mesh_indexed(self.ctx, _vp(vs), _vp(ns), _vp(cs), _vp(tris)), "pbf_download_mesh_indexed")
+        return dict(vs=vs, ns=ns, cs=cs, tris=tris, **self._read_lattice())
+
+    def surface(self, p, mc=None):
+        """Marching cubes on the state the last step left -> dict(vs, ns, cs, sample, pn, c)."""
+        mc = mc or McParams()
+        nt = C.c_uint64()
+        self._chk(self.L.pbf_surface(self.ctx, C.byref(p), C.byref(mc), C.byref(nt)), "pbf_surface")
+        return self._read_soup(nt.value)
 
     def surface_indexed(self, p, mc=None):
         """The same surface as an indexed mesh: one vertex per crossed lattice edge -> dict(vs (V,3), ns (V,3), cs (V,4),
@@ -624,16 +642,23 @@ class Solver:
         mc = mc or McParams()
         nv, nt = C.c_uint64(), C.c_uint64()
         self._chk(self.L.pbf_surface_indexed(self.ctx, C.byref(p), C.byref(mc), C.byref(nv), C.byref(nt)), "pbf_surface_indexed")
-        v, t = nv.value, nt.value
-        vs, ns, cs = np.empty((v, 3), self.dtype), np.empty((v, 3), self.dtype), np.empty((v, 4), self.dtype)
-        tris = np.empty((t, 3), np.uint32)
-        self._chk(self.L.pbf_download_mesh_indexed(self.ctx, _vp(vs), _vp(ns), _vp(cs), _vp(tris)), "pbf_download_mesh_indexed")
-        smp = np.zeros(3, np.uint64)
-        self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), None, None), "pbf_read_lattice")
-        nn = int(smp.prod())
-        pn, cc = np.empty((nn, 4), self.dtype), np.empty((nn, 4), self.dtype)
-        self._chk(self.L.pbf_read_lattice(self.ctx, _vp(smp), _vp(pn), _vp(cc)), "pbf_read_lattice")
-        return dict(vs=vs, ns=ns, cs=cs, tris=tris, sample=smp, pn=pn, c=cc)
+        return self._read_indexed(nv.value, nt.value)
+
+    def surface_anisotropic(self, p, resolution, isolevel, indexed=False, **kernel):
+        """The iso-surface of Yu & Turk's anisotropic-kernel field over the ellipsoids of anisotropy() (pbf_surface_anisotropic,
+        include/pbf_hip.h) -> the dict of surface(), or with indexed=True that of surface_indexed().  kernel: anisotropy()'s
+        smoothing, k_r, k_s, k_n, min_neighbours.  The isolevel has no default: the field's scale is not the stock one's."""
+        k = dict(smoothing=0.9, k_r=4.0, k_s=20.0 / 3.0, k_n=0.5, min_neighbours=25)
+        unknown = set(kernel) - set(k)
+        if unknown:
+            raise TypeError(f"surface_anisotropic: unknown kernel argument(s) {sorted(unknown)}")
+        k.update(kernel)
+        cfg = AnisoSurface(float(resolution), float(isolevel),
+                           Anisotropy(float(k["smoothing"]), float(k["k_r"]), float(k["k_s"]), float(k["k_n"]), int(k["min_neighbours"])))
+        nv, nt = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.pbf_surface_anisotropic(self.ctx, C.byref(p), C.byref(cfg), 1 if indexed else 0, C.byref(nv), C.byref(nt)),
+                  "pbf_surface_anisotropic")
+        return self._read_indexed(nv.value, nt.value) if indexed else self._read_soup(nt.value)
 
     def extent(self):
         e = np.zeros(3, np.uint64)

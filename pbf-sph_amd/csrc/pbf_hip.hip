@@ -24,6 +24,7 @@
 #include "pbf_mc.hpp"
 #include "pbf_whitewater.hpp"
 #include "pbf_anisotropy.hpp"
+#include "pbf_aniso_field.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 
@@ -254,6 +255,8 @@ struct pbf_ctx {
   // {centre 3, G 6, axes 9, radii 3} values of N and one uint32 per particle — made by the first call.  Scratch of an
   // observer: no step reads or writes it.
   DevBuf anisoOut;
+  // pbf_surface_anisotropic (csrc/pbf_aniso_field.hpp): three vec4 per particle, made from anisoOut by k_aniso_pack
+  DevBuf anisoRec;
   // advance() path: the caller's std::vector<Particle> buffer, page-locked in place (hipHostRegister) so the per-frame
   // 56-byte-per-particle upload and download are plain DMA instead of the runtime's pageable staging
   void *regPtr = nullptr;
@@ -2104,13 +2107,16 @@ int sample_check(pbf_ctx *ctx, const pbf_params *p, uint32_t what, const pbf_sam
 // pbf_anisotropy_compute: one AnisotropyOp launch over the final pStar on the last step's keys and table, through whichever
 // gather kernel the ctx is set to.  Like pbf_sample_points it touches nothing a step reads (materialise_pstar apart), takes no
 // ticket word and is never captured; the arrays asked for travel with plain async copies straight into the caller's memory.
+// AnisotropyOp's outputs in ctx->anisoOut: the planes are sized to the capacity; a plane has n elements
+struct AnisoPlanes : Planes {
+  size_t centre, G, axes, radii, nbr;
+  AnisoPlanes(size_t cap, size_t esz) {
+    centre = add(3 * cap * esz), G = add(6 * cap * esz), axes = add(9 * cap * esz), radii = add(3 * cap * esz), nbr = add(cap * 4);
+  }
+};
+// the launch alone: pbf_anisotropy_compute copies the planes back, pbf_surface_anisotropic packs them on the device
 template <typename N, bool FAST>
-int anisotropy_pass(pbf_ctx *ctx, const StepConsts<N> &c, const pbf_anisotropy *g, const pbf_anisotropy_out *o) {
-  // the outputs' planes are sized to the capacity; a plane has n elements
-  const size_t cap = ctx->cap, n = ctx->n;
-  Planes l;
-  const size_t centre = l.add(3 * cap * sizeof(N)), G = l.add(6 * cap * sizeof(N)), axes = l.add(9 * cap * sizeof(N)),
-               radii = l.add(3 * cap * sizeof(N)), nbr = l.add(cap * 4);
+int anisotropy_launch(pbf_ctx *ctx, const StepConsts<N> &c, const pbf_anisotropy *g, AnisoPlanes &l) {
   if (int rc = ensure(ctx, ctx->anisoOut, l.bytes)) return rc;
   if (int rc = join_diffuse(ctx)) return rc;
   if (int rc = materialise_pstar<N>(ctx)) return rc;
@@ -2118,16 +2124,29 @@ int anisotropy_pass(pbf_ctx *ctx, const StepConsts<N> &c, const pbf_anisotropy *
   const int s = ctx->st.cur;
   const AnisoConsts<N> k{N(g->smoothing), N(g->k_r), N(g->k_s), N(g->k_n), g->min_neighbours};
   typename AnisotropyOp<N, FAST>::Args a{ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->pos4[s].as<const vec4<N>>(),
-                                         ctx->type[s].as<const uint8_t>(), l.at<N>(centre), l.at<N>(G), l.at<N>(axes),
-                                         l.at<N>(radii), l.at<uint32_t>(nbr), k};
-  if (int rc = launch_gather<N, AnisotropyOp<N, FAST>>(ctx, c, a)) return rc;
-  HIPCHK(ctx, l.back(o->centre, centre, 3 * n * sizeof(N), ctx->stream));
-  HIPCHK(ctx, l.back(o->G, G, 6 * n * sizeof(N), ctx->stream));
-  HIPCHK(ctx, l.back(o->axes, axes, 9 * n * sizeof(N), ctx->stream));
-  HIPCHK(ctx, l.back(o->radii, radii, 3 * n * sizeof(N), ctx->stream));
-  HIPCHK(ctx, l.back(o->neighbours, nbr, n * 4, ctx->stream));
+                                         ctx->type[s].as<const uint8_t>(), l.at<N>(l.centre), l.at<N>(l.G), l.at<N>(l.axes),
+                                         l.at<N>(l.radii), l.at<uint32_t>(l.nbr), k};
+  return launch_gather<N, AnisotropyOp<N, FAST>>(ctx, c, a);
+}
+template <typename N, bool FAST>
+int anisotropy_pass(pbf_ctx *ctx, const StepConsts<N> &c, const pbf_anisotropy *g, const pbf_anisotropy_out *o) {
+  const size_t n = ctx->n;
+  AnisoPlanes l(ctx->cap, sizeof(N));
+  if (int rc = anisotropy_launch<N, FAST>(ctx, c, g, l)) return rc;
+  HIPCHK(ctx, l.back(o->centre, l.centre, 3 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->G, l.G, 6 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->axes, l.axes, 9 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->radii, l.radii, 3 * n * sizeof(N), ctx->stream));
+  HIPCHK(ctx, l.back(o->neighbours, l.nbr, n * 4, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return PBF_OK;
+}
+// what pbf_anisotropy_compute and pbf_surface_anisotropic reject in a pbf_anisotropy alike
+const char *anisotropy_config_error(const pbf_anisotropy *g) {
+  if (!(g->smoothing >= 0 && g->smoothing <= 1)) return "smoothing must lie in [0, 1]";
+  if (!(g->k_r >= 1) || !std::isfinite(g->k_r)) return "k_r must be finite and >= 1";
+  if (!(g->k_s > 0) || !std::isfinite(g->k_s) || !(g->k_n > 0) || !std::isfinite(g->k_n)) return "k_s and k_n must be finite and > 0";
+  return nullptr;
 }
 template <typename N> int anisotropy_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_anisotropy *g, const pbf_anisotropy_out *o) {
   StepConsts<N> c;
@@ -2404,10 +2423,7 @@ int pbf_anisotropy_compute(pbf_ctx *ctx, const pbf_params *p, const pbf_anisotro
   if (!p || !g || !out) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: NULL argument");
   const Refuse refuse{ctx, "pbf_anisotropy_compute"};
   if (int rc = refuse.params(p)) return rc;
-  if (!(g->smoothing >= 0 && g->smoothing <= 1)) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: smoothing must lie in [0, 1]");
-  if (!(g->k_r >= 1) || !std::isfinite(g->k_r)) return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: k_r must be finite and >= 1");
-  if (!(g->k_s > 0) || !std::isfinite(g->k_s) || !(g->k_n > 0) || !std::isfinite(g->k_n))
-    return fail(ctx, PBF_ERR_INVALID, "pbf_anisotropy_compute: k_s and k_n must be finite and > 0");
+  if (const char *why = anisotropy_config_error(g)) return fail(ctx, PBF_ERR_INVALID, std::string("pbf_anisotropy_compute: ") + why);
   // a particle near a cut needs both ranks' candidates, and the copies of the neighbours' columns would have to be left out
   if (int rc = refuse.slab_mode()) return rc;
   if (ctx->n == 0) return PBF_OK;
@@ -3174,19 +3190,49 @@ uint64_t pbf_slab_host_syncs(const pbf_ctx *ctx) { return ctx ? ctx->slabHostSyn
 // ================================================================================================
 namespace {
 
+// pbf_surface_anisotropic's field stage (csrc/pbf_aniso_field.hpp): AnisotropyOp into ctx->anisoOut exactly as
+// pbf_anisotropy_compute launches it, with no copies back; its planes packed into one record per particle; the field; the far
+// nodes' colours.  mcNear is already marked.
+template <typename N, bool FAST>
+int aniso_field_stage(pbf_ctx *ctx, const StepConsts<N> &c, const McConsts<N> &m, const pbf_anisotropy *kernel) {
+  const uint32_t n = uint32_t(ctx->n);
+  const int s = ctx->st.cur;
+  AnisoPlanes l(ctx->cap, sizeof(N));
+  if (int rc = ensure(ctx, ctx->anisoRec, size_t(3) * std::max<size_t>(ctx->cap, n) * sizeof(vec4<N>))) return rc;
+  if (int rc = anisotropy_launch<N, FAST>(ctx, c, kernel, l)) return rc;
+  hipLaunchKernelGGL((k_aniso_pack<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, n, N(c.h * c.scale), c.scale, c.hasObstacles,
+                     ctx->pos4[s].as<const vec4<N>>(), ctx->type[s].as<const uint8_t>(), l.at<const N>(l.centre),
+                     l.at<const N>(l.G), l.at<const N>(l.radii), ctx->anisoRec.as<vec4<N>>());
+  const uint64_t nodeBlocks = uint64_t((m.planes + 3) / 4) * ((m.sample[1] + 3) / 4) * ((m.sample[2] + 3) / 4);
+  hipLaunchKernelGGL((k_mc_field_aniso<N>), grid_for(nodeBlocks * 64), dim3(BLOCK), 0, ctx->stream, m,
+                     ctx->table.as<const uint32_t>(), ctx->anisoRec.as<const vec4<N>>(), ctx->col4[s].as<const vec4<N>>(),
+                     ctx->mcNear.as<const uint32_t>(), ctx->latticePN.as<vec4<N>>(), ctx->latticeC.as<vec4<N>>());
+  hipLaunchKernelGGL((k_mc_fill_far<N>), grid_for(size_t(m.sample[0]) * m.sample[1] * m.sample[2]), dim3(BLOCK), 0, ctx->stream,
+                     m.sample[0], m.sample[1], m.sample[2], ctx->latticePN.as<const vec4<N>>(), ctx->latticeC.as<vec4<N>>());
+  return PBF_OK;
+}
+
 // `nVertices` non-NULL: the indexed mesh (pbf_surface_indexed) — same field, count and scan, then one vertex per crossed
 // lattice edge and index triples instead of k_mc_emit's three private vertices per triangle
+// `aniso` non-NULL: pbf_surface_anisotropic — the same lattice, count, scans and emission around another field stage; never in
+// slab mode, and nothing is launched or changed before its last refusal
 template <typename N>
-int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uint64_t *nTriangles, uint64_t *nVertices) {
+int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uint64_t *nTriangles, uint64_t *nVertices,
+                 const pbf_anisotropy *aniso = nullptr) {
   const bool indexed = nVertices != nullptr;
   StepConsts<N> c;
-  if (int rc = make_consts<N>(ctx, p, c)) return rc;
+  if (aniso) {
+    if (int rc = consts_on_last_grid<N>(ctx, p, c, "pbf_surface_anisotropic")) return rc;
+  } else if (int rc = make_consts<N>(ctx, p, c)) {
+    return rc;
+  }
   // Slab mode (after pbf_slab_step; the copies of the neighbours' boundary columns are still in the arrays): every rank
   // extracts the part of the GLOBAL lattice whose nodes lie in its own cell columns — the ghost layer supplies exactly the
   // 27-cell neighbourhoods those nodes need — after refreshing the copies' colours (the owners diffused them during the
   // step), receives the one node plane its last cubes share with the right-hand neighbour, and emits its cubes'
   // triangles: the ranks' meshes, concatenated in rank order, ARE the single-device mesh's cube order (x-major).
-  if (int rc = materialise_pstar<N>(ctx)) return rc;  // (slab mode reads the copies' pStar)
+  if (!aniso)
+    if (int rc = materialise_pstar<N>(ctx)) return rc;  // (slab mode reads the copies' pStar)
   const bool slab = ctx->slabConfigured && ctx->comm && ctx->comm->nranks > 1;
   if (ctx->slabConfigured && !slab) return fail(ctx, PBF_ERR_STATE, "pbf_surface in slab mode needs pbf_slab_attach");
   if (slab && !ctx->ghostsPending) return fail(ctx, PBF_ERR_STATE, "pbf_surface in slab mode must follow pbf_slab_step directly");
@@ -3241,12 +3287,12 @@ int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uin
     if (int rc = exchange(ctx, ctx->sentL * fb, ctx->sentR * fb, ctx->gotL * fb, ctx->gotR * fb)) return rc;
     if (int rc = slab_unpack<N>(ctx, ctx->wireRecv[0].p, ctx->wireRecv[1].p, col)) return rc;
   }
-  for (int k = 0; k < 3; ++k) ctx->mcSample[k] = m.sample[k];
   const uint64_t planeN = uint64_t(m.sample[1]) * m.sample[2];
   const uint64_t latticeN = uint64_t(m.sample[0]) * planeN;
   if (latticeN >= (uint64_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "surface lattice too large (resolution x extent)");
   // (the 32-bit scan of up to three vertices per node must not wrap before the 2^29 test below sees its total)
   if (indexed && 3 * latticeN >= (uint64_t(1) << 32)) return fail(ctx, PBF_ERR_INVALID, "surface lattice too large for an indexed mesh");
+  for (int k = 0; k < 3; ++k) ctx->mcSample[k] = m.sample[k];  // (from here on the readers see this call's lattice)
   m.tableN = c.tableN, m.hasObstacles = c.hasObstacles;
   const int s = ctx->st.cur;
   if (int rc = ensure(ctx, ctx->latticePN, (latticeN + 1) * sizeof(vec4<N>))) return rc;
@@ -3265,10 +3311,14 @@ int surface_impl(pbf_ctx *ctx, const pbf_params *p, const pbf_mc_params *mp, uin
                        make_uint3(m.extent[0], m.extent[1], m.extent[2]), m.xoff, ctx->table.as<const uint32_t>(),
                        ctx->mcNear.as<uint32_t>());
     const uint64_t nodeBlocks = uint64_t((m.planes + 3) / 4) * ((m.sample[1] + 3) / 4) * ((m.sample[2] + 3) / 4);
-    hipLaunchKernelGGL((k_mc_field<N>), grid_for(nodeBlocks * 64), dim3(BLOCK), 0, ctx->stream, m, ctx->table.as<const uint32_t>(),
-                       ctx->pos4[s].as<const vec4<N>>(), ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->col4[s].as<const vec4<N>>(),
-                       ctx->type[s].as<const uint8_t>(), ctx->mcNear.as<const uint32_t>(), ctx->latticePN.as<vec4<N>>(),
-                       ctx->latticeC.as<vec4<N>>());
+    if (aniso) {
+      if (int rc = DISPATCH_FAST(ctx, aniso_field_stage, ctx, c, m, aniso)) return rc;
+    } else {
+      hipLaunchKernelGGL((k_mc_field<N>), grid_for(nodeBlocks * 64), dim3(BLOCK), 0, ctx->stream, m, ctx->table.as<const uint32_t>(),
+                         ctx->pos4[s].as<const vec4<N>>(), ctx->pstar[ctx->st.pcur].as<const vec4<N>>(), ctx->col4[s].as<const vec4<N>>(),
+                         ctx->type[s].as<const uint8_t>(), ctx->mcNear.as<const uint32_t>(), ctx->latticePN.as<vec4<N>>(),
+                         ctx->latticeC.as<vec4<N>>());
+    }
     LAUNCH_CHECK(ctx);
   }
   if (slab) {  // my first node plane -> the left neighbour's extra plane (two rounds: {v, normal} and colours)
@@ -3399,6 +3449,35 @@ int pbf_surface_indexed(pbf_ctx *ctx, const pbf_params *params, const pbf_mc_par
   if (!mc || !n_vertices || !n_triangles) return fail(ctx, PBF_ERR_INVALID, "NULL argument");
   if (!(mc->resolution > 0)) return fail(ctx, PBF_ERR_INVALID, "resolution must be > 0");
   return DISPATCH(ctx, surface_impl, ctx, params, mc, n_triangles, n_vertices);
+}
+
+int pbf_surface_anisotropic(pbf_ctx *ctx, const pbf_params *params, const pbf_aniso_surface *cfg, int indexed,
+                            uint64_t *n_vertices, uint64_t *n_triangles) {
+  if (!ctx) return PBF_ERR_INVALID;
+  const std::string who("pbf_surface_anisotropic: ");
+  if (!params || !cfg || !n_triangles) return fail(ctx, PBF_ERR_INVALID, who + "NULL argument");
+  if (indexed && !n_vertices) return fail(ctx, PBF_ERR_INVALID, who + "an indexed mesh needs n_vertices");
+  const Refuse refuse{ctx, "pbf_surface_anisotropic"};
+  if (int rc = refuse.params(params)) return rc;
+  if (!(cfg->resolution > 0) || !std::isfinite(cfg->resolution) || !(cfg->isolevel > 0) || !std::isfinite(cfg->isolevel))
+    return fail(ctx, PBF_ERR_INVALID, who + "resolution and isolevel must be finite and > 0");
+  if (const char *why = anisotropy_config_error(&cfg->kernel)) return fail(ctx, PBF_ERR_INVALID, who + why);
+  // a particle near a cut needs both ranks' candidates (pbf_anisotropy_compute), and so does a node
+  if (int rc = refuse.slab_mode()) return rc;
+  if (ctx->n == 0) {  // an empty surface of this call's kind, and no lattice
+    ctx->mcTriangles = ctx->mcVertices = 0;
+    ctx->meshStaged = false;
+    ctx->meshKind = indexed ? pbf_ctx::MESH_INDEXED : pbf_ctx::MESH_SOUP;
+    ctx->mcSample[0] = ctx->mcSample[1] = ctx->mcSample[2] = 0;
+    *n_triangles = 0;
+    if (indexed) *n_vertices = 0;
+    return PBF_OK;
+  }
+  if (int rc = refuse.no_step()) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const pbf_mc_params mc{cfg->resolution, cfg->isolevel, 0.0, 0.0};  // (size and influence belong to the stock field)
+  return DISPATCH(ctx, surface_impl, ctx, params, &mc, n_triangles, indexed ? n_vertices : static_cast<uint64_t *>(nullptr),
+                  &cfg->kernel);
 }
 
 int pbf_download_mesh_indexed(pbf_ctx *ctx, void *vs, void *ns, void *cs, uint32_t *tris) {

@@ -40,6 +40,10 @@ struct Args {
   bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
   double anisoCfg[4] = {0.9, 4.0, 20.0 / 3.0, 0.5};
   unsigned anisoMinNeighbours = 25;
+  bool anisoSurface = false;              // --anisotropic-surface=isolevel[,smoothing,k_r,k_s,k_n,min_neighbours] with --resident
+  double anisoSurfaceIso = 0;             // (no default: the field's scale is not the stock one's)
+  double anisoSurfaceCfg[4] = {0.9, 4.0, 20.0 / 3.0, 0.5};
+  unsigned anisoSurfaceMinNeighbours = 25;
   bool indexedMesh = false;               // --indexed-mesh: the frames' surface as an indexed mesh (one vertex per lattice edge)
   size_t diagnostics = 0;                 // --diagnostics[=every]: with --resident, a JSON line of pbf_diagnostics every `every` frames
 
@@ -97,6 +101,11 @@ struct Args {
           "                                        state, computed on the device; ellipsoids.ply beside cloud.ply (centre, three\n"
           "                                        radii, three axes and the neighbour count per fluid particle). Defaults:\n"
           "                                        0.9,4,6.6667,0.5,25. Single device only\n"
+          "      --anisotropic-surface=[iso[,s,k_r,k_s,k_n,N]]  With --resident: the frames' surface is the iso-surface of Yu &\n"
+          "                                        Turk's anisotropic-kernel field over those ellipsoids at isolevel iso (no\n"
+          "                                        default: its scale is not the stock field's; 0.3 ... 0.6 suits a fluid at\n"
+          "                                        rest density), at the stock resolution. Combines with --indexed-mesh;\n"
+          "                                        mesh.obj as before. Single device only\n"
           "      --indexed-mesh                    Extract the surface as an indexed mesh (one vertex per crossed lattice\n"
           "                                        edge, watertight by index); mesh.obj becomes an indexed OBJ.\n"
           "                                        Single device only\n"
@@ -166,6 +175,16 @@ struct Args {
           anisotropy = true;
           for (int k = 0; k < 4; ++k) anisoCfg[k] = f[size_t(k)];
           anisoMinNeighbours = unsigned(f[4]);
+        }
+        else if (a.rfind("--anisotropic-surface=", 0) == 0) {
+          const auto f = numbers(a.substr(22));
+          if ((f.size() != 1 && f.size() != 6) || (f.size() == 6 && !(f[5] >= 0)))
+            throw std::runtime_error("--anisotropic-surface: expected isolevel[,smoothing,k_r,k_s,k_n,min_neighbours]");
+          anisoSurface = true, anisoSurfaceIso = f[0];
+          if (f.size() == 6) {
+            for (int k = 0; k < 4; ++k) anisoSurfaceCfg[k] = f[size_t(k) + 1];
+            anisoSurfaceMinNeighbours = unsigned(f[5]);
+          }
         }
         else if (a == "--diagnostics") diagnostics = 1;
         else if (a.rfind("--diagnostics=", 0) == 0) {

@@ -133,6 +133,15 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   if (args.anisotropy && !args.resident) std::cout << "--anisotropy takes effect with --resident: ignored" << std::endl;
+  if (args.anisoSurface && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--anisotropic-surface is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (args.anisoSurface && !args.resident) std::cout << "--anisotropic-surface takes effect with --resident: ignored" << std::endl;
+  // --anisotropic-surface --resident: the frames' surface from pbf_surface_anisotropic, at the stock resolution
+  const sph::hip_impl::AnisoSurface anisoSurface{double(mc.resolution), args.anisoSurfaceIso,
+                                                 {args.anisoSurfaceCfg[0], args.anisoSurfaceCfg[1], args.anisoSurfaceCfg[2],
+                                                  args.anisoSurfaceCfg[3], args.anisoSurfaceMinNeighbours}};
   if (args.indexedMesh && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--indexed-mesh is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -187,7 +196,10 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
           wwConfigured = true;
         }
       }
-      if (param.surface && solver.count() && args.indexedMesh) indexed = solver.surfaceIndexed(frameParam(frame));
+      if (param.surface && solver.count() && args.anisoSurface) {
+        if (args.indexedMesh) indexed = solver.surfaceAnisotropicIndexed(frameParam(frame), anisoSurface, scene);
+        else result.mesh = solver.surfaceAnisotropic(frameParam(frame), anisoSurface, scene);
+      } else if (param.surface && solver.count() && args.indexedMesh) indexed = solver.surfaceIndexed(frameParam(frame));
       else if (param.surface && solver.count()) result.mesh = solver.surface(frameParam(frame));
       solver.sync();  // per-frame time like the reference's blocking advance()
     } else {

@@ -197,6 +197,9 @@ template <typename N> struct Samples {
   std::vector<uint8_t> outside{};
 };
 
+// Solver::surfaceAnisotropic()'s configuration: {resolution, isolevel, kernel} (include/pbf_hip.h)
+using AnisoSurface = pbf_aniso_surface;
+
 // What Solver::anisotropy() returns: the arrays of pbf_anisotropy_out (include/pbf_hip.h) in device order, COMPONENT-MAJOR —
 // value k of particle i at [k * n + i], n = neighbours.size(): centre 3 planes (world), G 6 (xx yy zz xy xz yz, solver frame),
 // axes 9 (three unit rows, descending), radii 3.
@@ -752,6 +755,23 @@ public:
   }
   const IndexedMesh<N, V> &lastIndexedMesh() const { return lastIndexed_; }
 
+  // The iso-surface of Yu & Turk's anisotropic-kernel field over the ellipsoids of anisotropy() (pbf_surface_anisotropic,
+  // include/pbf_hip.h; no reference counterpart) on the state the last step() left, as a soup or as an indexed mesh: the stock
+  // count, scans and emission around another field.  config.surface is not read — the resolution and the isolevel (no
+  // default: the field's scale is not the stock one's) are `cfg`'s.  Single device: on several the library's refusal is thrown.
+  sph::ColouredMesh<N, V> surfaceAnisotropic(const sph::SphParams<T, N, V> &config, const AnisoSurface &cfg,
+                                             const sph::Scene<T, N, V> &scene = {}) {
+    sph::ColouredMesh<N, V> mesh;
+    MeshCopy(*this, config, scene, mesh, &cfg).join();
+    return mesh;
+  }
+  IndexedMesh<N, V> surfaceAnisotropicIndexed(const sph::SphParams<T, N, V> &config, const AnisoSurface &cfg,
+                                              const sph::Scene<T, N, V> &scene = {}) {
+    IndexedMesh<N, V> mesh;
+    IndexedCopy(*this, config, scene, mesh, &cfg).join();
+    return mesh;
+  }
+
 private:
   // pbf_surface_indexed + the hand-over, shaped like MeshCopy below: one DMA into the page-locked staging, four range
   // assignments on threads of their own once the mesh is large enough to pay for them
@@ -762,13 +782,18 @@ private:
     const uint32_t *t3 = nullptr;
     size_t nv = 0, ni = 0;
     std::thread th[4];
-    IndexedCopy(Solver &s, const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene, IndexedMesh<N, V> &out)
+    IndexedCopy(Solver &s, const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene, IndexedMesh<N, V> &out,
+                const AnisoSurface *aniso = nullptr)
         : mesh(out) {
       const pbf_params p = s.params(config, scene);
-      const pbf_mc_params mc{double(config.surface->resolution), double(config.surface->isolevel),
-                             double(config.surface->particleSize), double(config.surface->particleInfluence)};
       uint64_t vertices = 0, triangles = 0;
-      s.check(pbf_surface_indexed(s.ctx_, &p, &mc, &vertices, &triangles), "pbf_surface_indexed");
+      if (aniso) {
+        s.check(pbf_surface_anisotropic(s.ctx_, &p, aniso, 1, &vertices, &triangles), "pbf_surface_anisotropic");
+      } else {
+        const pbf_mc_params mc{double(config.surface->resolution), double(config.surface->isolevel),
+                               double(config.surface->particleSize), double(config.surface->particleInfluence)};
+        s.check(pbf_surface_indexed(s.ctx_, &p, &mc, &vertices, &triangles), "pbf_surface_indexed");
+      }
       const void *pv = nullptr, *pn = nullptr, *pc = nullptr;
       s.check(pbf_map_mesh_indexed(s.ctx_, &pv, &pn, &pc, &t3), "pbf_map_mesh_indexed");
       nv = size_t(vertices), ni = size_t(triangles) * 3;
@@ -804,13 +829,18 @@ private:
     const V<4> *c4 = nullptr;
     size_t nv = 0;
     std::thread tv, tn, tc;
-    MeshCopy(Solver &s, const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene, sph::ColouredMesh<N, V> &out)
+    MeshCopy(Solver &s, const sph::SphParams<T, N, V> &config, const sph::Scene<T, N, V> &scene, sph::ColouredMesh<N, V> &out,
+             const AnisoSurface *aniso = nullptr)
         : mesh(out) {
       const pbf_params p = s.params(config, scene);
-      const pbf_mc_params mc{double(config.surface->resolution), double(config.surface->isolevel),
-                             double(config.surface->particleSize), double(config.surface->particleInfluence)};
       uint64_t triangles = 0;
-      s.check(pbf_surface(s.ctx_, &p, &mc, &triangles), "pbf_surface");
+      if (aniso) {
+        s.check(pbf_surface_anisotropic(s.ctx_, &p, aniso, 0, nullptr, &triangles), "pbf_surface_anisotropic");
+      } else {
+        const pbf_mc_params mc{double(config.surface->resolution), double(config.surface->isolevel),
+                               double(config.surface->particleSize), double(config.surface->particleInfluence)};
+        s.check(pbf_surface(s.ctx_, &p, &mc, &triangles), "pbf_surface");
+      }
       const void *pv = nullptr, *pn = nullptr, *pc = nullptr;
       s.check(pbf_map_mesh(s.ctx_, &pv, &pn, &pc), "pbf_map_mesh");
       nv = size_t(triangles) * 3;
