@@ -891,8 +891,16 @@ template <typename N, bool FAST> struct DeltaOp {
 // ------------------------------------------------------------------------------------------------
 // Opt-in extras named by the north star but ABSENT from the reference (only their constants survive,
 // sph_constants.h:13-14; SURVEY finding 3): vorticity confinement and XSPH viscosity after Macklin &
-// Mueller 2013 (eq. 15-17), applied to the post-solve velocity, Jacobi.  Parity unpinned: the only
-// checker is our own CPU restatement (oracle extras()).  Candidates need position AND velocity.
+// Mueller 2013 (eq. 15-17), applied to the post-solve velocity, Jacobi.  Candidates need position AND velocity.
+// Obstacles: an obstacle walker gets omega = 0 and keeps its velocity bit for bit; as a NEIGHBOUR it counts in eq. 15 and
+// eq. 17 with the velocity it carries (kNeedsCandidateType = false) and in eq. 16 with |omega| = 0.
+// Parity with the reference is unpinned (there is nothing to compare with), so these ops are held three ways instead
+// (DESIGN.md section 3): bit for bit against the CPU restatement (oracle extras()), obstacles with a velocity included;
+// per particle against an independent float64 all-pairs evaluation of the equations with the obstacle rule above
+// (tests/nversion.py, bars counted from the roundings of pair_geom and add_bf: tests/extras_ref.py); and every path
+// launch_gather can send them to — k_gather_global, k_gather_lists at every staging depth, row_major = 0, gather = 3, a
+// replayed graph — is held to the default path's bytes (tests/test_extras_paths_gpu.py).  The same holds for the three
+// surface-tension ops below.
 // ------------------------------------------------------------------------------------------------
 template <typename N> struct PosVel {
   vec4<N> p, v;

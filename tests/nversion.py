@@ -102,26 +102,37 @@ def predict(pos, vel, mass, dt, scale, force):
 
 # ---- the opt-in extras, from Macklin & Mueller 2013 (eq. 15-17) with the reference's kernels and constants ----------
 
-def vorticity(ps, vel, h, cells=None):
-    """eq. 15: omega_i = sum_j (v_j - v_i) x grad_{p_j} W(p_i - p_j);  grad_{p_j} W = -grad_{p_i} W"""
+def vorticity(ps, vel, h, cells=None, obstacle=None):
+    """eq. 15: omega_i = sum_j (v_j - v_i) x grad_{p_j} W(p_i - p_j);  grad_{p_j} W = -grad_{p_i} W.
+    obstacle (bool mask, from the comment above VorticityOp in pbf_kernels.hpp): an obstacle has no vorticity of its
+    own, omega = 0; as a NEIGHBOUR it counts like any particle, with the velocity it carries."""
     _, g = pair_tables(ps, h, cells)                            # grad_{p_i} W
     vij = vel[None, :, :] - vel[:, None, :]
-    return np.cross(vij, -g).sum(1)
+    w = np.cross(vij, -g).sum(1)
+    return w if obstacle is None else np.where(np.asarray(obstacle, bool)[:, None], 0.0, w)
 
 
-def vorticity_force_dv(ps, omega, h, dt, cells=None, return_eta=False):
-    """eq. 16: f = eps (N x omega), N = eta / |eta|, eta = grad |omega|; returns the velocity increment f dt"""
+def vorticity_force_dv(ps, omega, h, dt, cells=None, return_eta=False, obstacle=None):
+    """eq. 16: f = eps (N x omega), N = eta / |eta|, eta = grad |omega|; returns the velocity increment f dt.
+    obstacle: an obstacle's velocity is never changed (increment 0), and as a neighbour it adds |omega_b| = 0 to eta
+    whatever `omega` holds in its row."""
     _, g = pair_tables(ps, h, cells)
     mag = np.sqrt((omega * omega).sum(-1))
+    if obstacle is not None:
+        mag = np.where(np.asarray(obstacle, bool), 0.0, mag)
     eta = (g * mag[None, :, None]).sum(1)
     ln = np.sqrt((eta * eta).sum(-1))
     nn = np.where((ln > EPSILON)[:, None], eta / np.where(ln > EPSILON, ln, 1.0)[:, None], 0.0)
     dv = np.cross(nn, omega) * (VORTICITY_EPSILON * dt)
+    if obstacle is not None:
+        dv = np.where(np.asarray(obstacle, bool)[:, None], 0.0, dv)
     return (dv, ln) if return_eta else dv
 
 
-def xsph(ps, vel, h, cells=None):
-    """eq. 17: v_i <- v_i + c sum_j (v_j - v_i) W(p_i - p_j)"""
+def xsph(ps, vel, h, cells=None, obstacle=None):
+    """eq. 17: v_i <- v_i + c sum_j (v_j - v_i) W(p_i - p_j).
+    obstacle: an obstacle keeps its velocity; as a neighbour it counts with the velocity it carries."""
     r, _ = pair_tables(ps, h, cells)
     w = poly6(r, h)
-    return vel + C_XSPH * ((vel[None, :, :] - vel[:, None, :]) * w[..., None]).sum(1)
+    out = vel + C_XSPH * ((vel[None, :, :] - vel[:, None, :]) * w[..., None]).sum(1)
+    return out if obstacle is None else np.where(np.asarray(obstacle, bool)[:, None], vel, out)

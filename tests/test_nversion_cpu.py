@@ -35,6 +35,27 @@ def scene(name):
         sc = O.scene_cubes(1024, True)
         sc["type"][::5] = 1
         sc["mass"] = 0.5 + rng.random(len(sc["id"]))
+    elif name == "obstacles_moving":   # the obstacles CARRY a velocity (predict and finalise never touch it): what the
+        sc = scene("obstacles")        # opt-in velocity passes read from an obstacle neighbour is then not 0
+        obstacle = sc["type"] == 1
+        sc["vel"] = sc["vel"].copy()
+        sc["vel"][obstacle] = (rng.random((int(obstacle.sum()), 3)) - 0.5) * 2.0
+    elif name == "pile":       # 300 fluid + 20 obstacles inside 0.045 solver units, across a cell corner: every particle
+        n = 320                # is within h of nearly every other.  r = 0 with DIFFERENT velocities: five fluid particles
+        pos = rng.random((n, 3)) * 22.5 + 489.0        # at rest lie on five obstacles that carry a velocity (a fluid
+        vel = (rng.random((n, 3)) - 0.5) * 2.0         # particle at rest stays put with no force and no iterations, a
+        type_ = np.zeros(n, np.uint8)                  # moving one would leave), and two fluid pairs at rest coincide
+        type_[300:] = 1
+        pos[10:15], vel[10:15] = pos[300:305], 0.0
+        pos[20:22], vel[20:24] = pos[22:24], 0.0
+        sc = dict(id=np.arange(n, dtype=np.uint64), type=type_, mass=0.5 + rng.random(n), pos=pos, vel=vel,
+                  colour=rng.random((n, 4)))
+    elif name.startswith("edges"):   # edges1 / edges65 / edges257: a line-by-line filled block at rest spacing, moving
+        n = int(name[5:])
+        k = int(np.ceil(n ** (1.0 / 3.0)))
+        g = np.stack(np.meshgrid(*[np.arange(k)] * 3, indexing="ij"), -1).reshape(-1, 3)[:n]
+        sc = dict(id=np.arange(n, dtype=np.uint64), type=np.zeros(n, np.uint8), mass=np.ones(n),
+                  pos=g * 27.0 + 437.0, vel=(rng.random((n, 3)) - 0.5) * 2.0, colour=rng.random((n, 4)))
     else:
         raise KeyError(name)
     return sc
@@ -88,11 +109,12 @@ def test_oracle_predict_equals_formula():
     assert rel_err(o.pstar(), ps) <= REL and rel_err(o.get_particles()["vel"], v) <= REL
 
 
-@pytest.mark.parametrize("name", ["cubes1024", "cloud"])
+@pytest.mark.parametrize("name", ["cubes1024", "cloud", "obstacles_moving"])
 def test_oracle_extras_equal_all_pairs_evaluation(name):
     """The opt-in extras (absent from the reference; Macklin & Mueller 2013 eq. 15-17) against the same equations
     evaluated over all pairs — including the SIGN of the vorticity (eq. 15 differentiates with respect to the
-    neighbour's position)."""
+    neighbour's position) and, on obstacles_moving, the obstacle rule: no vorticity and no velocity change of its own, a
+    full neighbour with the velocity it carries."""
     sc = scene(name)
     q = O.make_params(iteration=2)
     o = O.Oracle(True)
@@ -107,16 +129,19 @@ def test_oracle_extras_equal_all_pairs_evaluation(name):
     o.finalise(q0)                             # extras run on the post-solve state, in the predict-time cells
     ps = o.pstar().astype(np.float64)
     vel = o.get_vec(0).astype(np.float64)
+    obstacle = o.get_particles()["type"] == 1      # (all False but on obstacles_moving)
+    assert obstacle.any() == (name == "obstacles_moving")
     o.vorticity(q0)
-    w = NV.vorticity(ps, vel, q0.h, cells)
+    w = NV.vorticity(ps, vel, q0.h, cells, obstacle=obstacle)
     assert rel_err(o.get_vec(1), w) <= 1e-11
     o.vorticity_force(q0)
-    dv = NV.vorticity_force_dv(ps, w, q0.h, q0.dt, cells)
+    dv = NV.vorticity_force_dv(ps, w, q0.h, q0.dt, cells, obstacle=obstacle)
     assert np.abs((o.get_vec(0) - vel) - dv).max() <= 1e-9 * np.abs(dv).max()
     vel2 = o.get_vec(0).astype(np.float64)
     o.xsph(q0)
-    dx = NV.xsph(ps, vel2, q0.h, cells) - vel2
+    dx = NV.xsph(ps, vel2, q0.h, cells, obstacle=obstacle) - vel2
     assert np.abs((o.get_vec(0) - vel2) - dx).max() <= 1e-9 * np.abs(dx).max()
+    assert np.array_equal(o.get_vec(0)[obstacle], vel[obstacle])
 
 
 def rotating_blob(n_side=14, spacing=27.0, omega_z=3.0, centre=(500.0, 500.0, 500.0), fp64=True):
