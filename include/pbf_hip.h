@@ -108,6 +108,63 @@ int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value);
  * pbf_slab_step / a slab-mode finalise with it enabled, return PBF_ERR_STATE. */
 int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion);
 
+/* Opt-in static collider: a signed-distance lattice that delta-p projects the fluid out of, so that a bowl, a ramp or a
+ * pillar needs no obstacle particles (no reference counterpart).  Default off: with no collider set every launch and every
+ * byte of a step is what it is without this feature.
+ *
+ * pbf_set_collider copies the lattice to the device, rounded to N (float / double as the ctx), together with N(origin),
+ * inv = N(1) / N(spacing) and N(margin).  The setting persists in the ctx and applies to every later pbf_stage_delta,
+ * pbf_step and pbf_steps (hipGraph replays included: every call, clearing too, changes a captured step's key, so a replay
+ * never uses a stale lattice).  It allocates nothing inside a step.  sdf == NULL clears the collider and frees the lattice.
+ * PBF_ERR_INVALID, the setting unchanged: a dim < 2; a dims product >= 2^31; a non-finite origin, spacing or margin;
+ * spacing <= 0; margin < 0; phi == NULL; a NaN in phi (infinities are legal: "no solid anywhere near").
+ * Slab mode is not supported (a collider across slabs is out of scope): setting one on a slab-attached or slab-configured
+ * ctx, and pbf_slab_step(s) / a delta-p stage of a slab-configured ctx with one set, return PBF_ERR_STATE.
+ *
+ * The contract.  One device function (csrc/pbf_collider.hpp) is shared by delta-p's epilogue and pbf_collider_sample.
+ * Everything is in N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it.  The input is the q that
+ * delta-p computes without a collider: after the world-frame box clamp and the division by scale.
+ *   w_a = q_a * scale                         u_a = (w_a - origin_a) * inv
+ *   inside = for every a: u_a >= 0 && u_a <= N(dims_a - 1)            (NaN compares false: outside)
+ *   i_a = min(int(u_a), dims_a - 2)           f_a = u_a - N(i_a)       (the last node: i = dims - 2, f = 1)
+ *   c[x][y][z] = the eight nodes (i_x + x, i_y + y, i_z + z)
+ *   d[x][y]  = c[x][y][1] - c[x][y][0]        cz[x][y] = c[x][y][0] + f_z * d[x][y]
+ *   e[x]     = cz[x][1] - cz[x][0]            cy[x]    = cz[x][0] + f_y * e[x]
+ *   g_x = cy[1] - cy[0]                       phi = cy[0] + f_x * g_x
+ *   g_y = e[0] + f_x * (e[1] - e[0])
+ *   t[x] = d[x][0] + f_y * (d[x][1] - d[x][0])     g_z = t[0] + f_x * (t[1] - t[0])
+ *   len = sqrt((g_x g_x + g_y g_y) + g_z g_z)       (IEEE sqrt)
+ *   hit = inside && phi < margin && len > 0
+ *   s = (margin - phi) / len                         (IEEE divide)
+ *   q'_a = hit ? min(maxB_a / scale, max(minB_a / scale, (w_a + s * g_a) / scale)) : q_a
+ * g is the gradient of the trilinear interpolant in lattice units; the spacing is isotropic, so only its direction
+ * matters.  A particle that does not hit keeps its q bit for bit (a select).  The second clamp uses the images of the box
+ * under the stock clamp, so the box always wins over the collider.  The stored lambda is untouched; the quantised copy of
+ * pStar is formed from q'.  Obstacles and ghost copies are never moved.  One projection runs per delta-p iteration; the K
+ * iterations converge it.  Every gather path ("gather" 0 / 1 / 3, "row_major", "pipeline", "graph", PBF_FLAG_NO_LDS)
+ * gives the same bytes; "coop" 2 / 4 / 8 differs at rounding level as it does without a collider.
+ * Limitations: there is no friction or restitution term — finalise derives the velocity from the projected position, as it
+ * does for the box.  Whitewater's diffuse particles and the observers (surface, sampling, diagnostics, anisotropy) do not
+ * see the collider.  One static collider per ctx; mesh-to-SDF conversion is the caller's.
+ *
+ * pbf_collider_sample is the window onto that device function, for debugging an uploaded collider: its own synchronising
+ * call, never part of a step.  For each point: round to N, q = point / scale in N, then exactly the function above with
+ * params' scale and bounds.  phi receives the interpolated value (+inf outside the lattice), moved the q' delta-p would
+ * store, hit whether the point was projected; any output pointer may be NULL.  A non-finite point is legal: it is outside,
+ * hit = 0, moved = its q.  PBF_ERR_INVALID: params == NULL; points == NULL with n > 0; dt or scale <= 0; n >= 2^31.  n == 0
+ * then returns PBF_OK and launches nothing.  PBF_ERR_STATE without a collider. */
+typedef struct pbf_collider_sdf {
+  uint32_t dims[3];   /* nodes per axis, each >= 2; dims[0]*dims[1]*dims[2] < 2^31 */
+  double origin[3];   /* world position of node (0,0,0) */
+  double spacing;     /* world units between nodes, the same on all three axes, > 0 */
+  double margin;      /* fluid is kept at phi >= margin (world units), >= 0 */
+  const void *phi;    /* host, N[dims product] (float / double as the ctx), node (i,j,k) at (i*dims[1]+j)*dims[2]+k —
+                         pbf_sample_lattice's order; signed distance in world units, NEGATIVE inside the solid */
+} pbf_collider_sdf;
+int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf);   /* NULL clears and frees the lattice */
+int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const double *points /* 3n, world */,
+                        void *phi /* N[n] */, void *moved /* N[3n], solver frame */, uint8_t *hit /* [n] */);
+
 /* ---- particle state (replaces the std::vector<Particle>& in/out argument, src/sph.hpp:124) */
 int pbf_upload(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type, const void *mass, const void *pos,
                const void *vel, const void *colour);

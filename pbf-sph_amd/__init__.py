@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     AnisotropyOut,
     BUF_DENSITY,
     BUF_WHITEWATER,
+    ColliderSdf,
     DIAG_DENSITY,
     Diag,
     FLAG_FAST_MATH,
@@ -40,5 +41,9 @@ from .capi import (  # noqa: F401
     lib,
     scene_cubes,
     scene_dambreak,
+    sdf_box,
+    sdf_lattice,
+    sdf_plane,
+    sdf_sphere,
     whitewater_config,
 )

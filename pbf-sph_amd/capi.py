@@ -154,6 +154,12 @@ class AnisoSurface(C.Structure):
     _fields_ = [("resolution", C.c_double), ("isolevel", C.c_double), ("kernel", Anisotropy)]
 
 
+class ColliderSdf(C.Structure):
+    """pbf_collider_sdf (include/pbf_hip.h)"""
+    _fields_ = [("dims", C.c_uint32 * 3), ("origin", C.c_double * 3), ("spacing", C.c_double), ("margin", C.c_double),
+                ("phi", C.c_void_p)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -174,6 +180,8 @@ _SIGS = {
     "pbf_abi_version": (C.c_int, []),
     "pbf_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "pbf_set_surface_tension": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "pbf_set_collider": (C.c_int, [C.c_void_p, C.POINTER(ColliderSdf)]),
+    "pbf_collider_sample": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_create": (C.c_int, [C.POINTER(Desc), C.POINTER(C.c_void_p)]),
     "pbf_destroy": (None, [C.c_void_p]),
     "pbf_last_error": (C.c_char_p, [C.c_void_p]),
@@ -333,6 +341,49 @@ def whitewater_config(capacity, tau_ta, tau_wc, tau_k, k_ta=0.0, k_wc=0.0, lifet
     return w
 
 
+# ---- host-only helpers for pbf_set_collider: analytic signed distances (float64, NEGATIVE inside the solid) and their
+# evaluation on a lattice.  Union = np.minimum, complement = negation (a bowl is the negated sphere).
+def sdf_sphere(centre, radius):
+    """points (..., 3) -> distance to the sphere's surface, negative inside"""
+    c = np.asarray(centre, np.float64).reshape(3)
+
+    def f(x):
+        d = np.asarray(x, np.float64) - c
+        return np.sqrt((d * d).sum(axis=-1)) - float(radius)
+    return f
+
+
+def sdf_box(lo, hi):
+    """points (..., 3) -> distance to the axis-aligned box [lo, hi], negative inside"""
+    lo, hi = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    centre, half = (lo + hi) / 2, (hi - lo) / 2
+
+    def f(x):
+        q = np.abs(np.asarray(x, np.float64) - centre) - half
+        out = np.maximum(q, 0)
+        return np.sqrt((out * out).sum(axis=-1)) + np.minimum(q.max(axis=-1), 0)
+    return f
+
+
+def sdf_plane(normal, d):
+    """points (..., 3) -> n.x - d with n = normal / |normal|: the half space n.x < d is solid"""
+    n = np.asarray(normal, np.float64).reshape(3)
+    n = n / np.sqrt((n * n).sum())
+
+    def f(x):
+        return np.asarray(x, np.float64) @ n - float(d)
+    return f
+
+
+def sdf_lattice(fn, origin, spacing, dims):
+    """fn on the nodes origin + (i, j, k) * spacing, i < dims[0] ..., in float64 -> array of shape dims (C order: node
+    (i, j, k) at (i * dims[1] + j) * dims[2] + k, the layout pbf_set_collider takes)"""
+    o = np.asarray(origin, np.float64).reshape(3)
+    ax = [o[a] + np.arange(int(dims[a]), dtype=np.float64) * float(spacing) for a in range(3)]
+    x = np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1)
+    return np.ascontiguousarray(np.asarray(fn(x), np.float64).reshape([int(v) for v in dims]))
+
+
 class Solver:
     """Mirror of sph::hip_impl::Solver<T,N> (host/hipsph.hpp) over the C ABI: ctor takes h like
     omp_impl::Solver(N h) (ompsph.hpp:83); state is device-resident between steps."""
@@ -405,6 +456,33 @@ class Solver:
         Persists in the solver and applies to every later step (include/pbf_hip.h)."""
         self._chk(self.L.pbf_set_surface_tension(self.ctx, float(cohesion), float(adhesion)), "pbf_set_surface_tension")
         return self
+
+    def set_collider(self, phi, origin=(0.0, 0.0, 0.0), spacing=1.0, margin=0.0):
+        """Opt-in static collider (pbf_set_collider, include/pbf_hip.h): phi = signed distances in world units on a lattice
+        of shape (nx, ny, nz), negative inside the solid (sdf_lattice makes one); origin = world position of node (0, 0, 0);
+        delta-p keeps the fluid at phi >= margin.  phi=None clears it.  Persists in the solver."""
+        if phi is None:
+            self._chk(self.L.pbf_set_collider(self.ctx, None), "pbf_set_collider")
+            return self
+        a = np.ascontiguousarray(phi, self.dtype)
+        if a.ndim != 3:
+            raise ValueError("set_collider: phi must have shape (nx, ny, nz)")
+        sdf = ColliderSdf()
+        sdf.dims[:] = [int(v) for v in a.shape]
+        sdf.origin[:] = [float(v) for v in origin]
+        sdf.spacing, sdf.margin, sdf.phi = float(spacing), float(margin), a.ctypes.data
+        self._chk(self.L.pbf_set_collider(self.ctx, C.byref(sdf)), "pbf_set_collider")
+        return self
+
+    def collider_sample(self, p, points):
+        """The collider's device function at world points (pbf_collider_sample) -> dict(phi (n,) interpolated distance, +inf
+        outside the lattice; moved (n,3) the solver-frame position delta-p would store; hit (n,) uint8)"""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = len(pts)
+        o = dict(phi=np.zeros(n, self.dtype), moved=np.zeros((n, 3), self.dtype), hit=np.zeros(n, np.uint8))
+        self._chk(self.L.pbf_collider_sample(self.ctx, C.byref(p), n, _vp(pts), _vp(o["phi"]), _vp(o["moved"]), _vp(o["hit"])),
+                  "pbf_collider_sample")
+        return o
 
     def surface_state(self):
         """(n,4): {n.xyz, rho} of the last surface-tension pass — surface normal and density per particle, device order

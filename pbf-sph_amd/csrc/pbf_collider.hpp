@@ -1,0 +1,102 @@
+// pbf_collider.hpp — static signed-distance collider (pbf_set_collider, include/pbf_hip.h): ONE device function, shared by
+// DeltaOp::end (csrc/pbf_kernels.hpp) and the sample kernel behind pbf_collider_sample.
+//
+// The contract (the same text as the header's).  Everything is in N, in the order written, not contracted (the library is
+// built with -ffp-contract=off); PBF_FLAG_FAST_MATH does not reach it.  The input is the q that DeltaOp::end computes
+// without a collider: after the world-frame box clamp and the division by scale.
+//
+//   w_a = q_a * scale                         u_a = (w_a - origin_a) * inv
+//   inside = for every a: u_a >= 0 && u_a <= N(dims_a - 1)            (NaN compares false: outside)
+//   i_a = min(int(u_a), dims_a - 2)           f_a = u_a - N(i_a)       (the last node: i = dims - 2, f = 1)
+//   c[x][y][z] = the eight nodes (i_x + x, i_y + y, i_z + z)
+//   d[x][y]  = c[x][y][1] - c[x][y][0]        cz[x][y] = c[x][y][0] + f_z * d[x][y]
+//   e[x]     = cz[x][1] - cz[x][0]            cy[x]    = cz[x][0] + f_y * e[x]
+//   g_x = cy[1] - cy[0]                       phi = cy[0] + f_x * g_x
+//   g_y = e[0] + f_x * (e[1] - e[0])
+//   t[x] = d[x][0] + f_y * (d[x][1] - d[x][0])     g_z = t[0] + f_x * (t[1] - t[0])
+//   len = sqrt((g_x g_x + g_y g_y) + g_z g_z)       (IEEE sqrt)
+//   hit = inside && phi < margin && len > 0
+//   s = (margin - phi) / len                         (IEEE divide)
+//   q'_a = hit ? min(maxB_a / scale, max(minB_a / scale, (w_a + s * g_a) / scale)) : q_a
+//
+// g is the gradient of the trilinear interpolant in lattice units: the spacing is isotropic, so only its direction matters.
+// A particle that does not hit keeps its q bit for bit (a select).  The second clamp uses the images of the box under the
+// stock clamp, so the box always wins over the collider.  One projection runs per delta-p iteration; the K iterations
+// converge it.  There is no friction or restitution term: finalise derives the velocity from the projected position, as it
+// does for the box.
+//
+// The eight lattice loads are scalar-per-lane gathers from a read-only array that is small against L2 and shared by every
+// wave of the launch (neighbouring particles read neighbouring nodes): plain loads, nothing staged.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+// the lattice as the kernels see it: phi == NULL means no collider
+template <typename N> struct ColliderSdf {
+  const N *phi;      // device, N[dims product], node (i, j, k) at (i * dims[1] + j) * dims[2] + k
+  uint32_t dims[3];  // nodes per axis, each >= 2, product < 2^31
+  N origin[3];       // world position of node (0, 0, 0)
+  N inv;             // N(1) / N(spacing)
+  N margin;          // fluid is kept at phi >= margin
+};
+
+// q: in, the clamped position in the solver frame; out, q' (unchanged bit for bit without a hit).  Returns hit; *phiOut (may
+// be NULL) receives the interpolated value, +inf outside the lattice.
+template <typename N>
+__device__ inline bool collider_project(const ColliderSdf<N> &s, N scale, const N *minB, const N *maxB, N &qx, N &qy, N &qz,
+                                        N *phiOut) {
+  const N *__restrict__ lat = s.phi;
+  const N wx = qx * scale, wy = qy * scale, wz = qz * scale;
+  const N ux = (wx - s.origin[0]) * s.inv, uy = (wy - s.origin[1]) * s.inv, uz = (wz - s.origin[2]) * s.inv;
+  const bool inside = ux >= N(0) && ux <= N(s.dims[0] - 1u) && uy >= N(0) && uy <= N(s.dims[1] - 1u) && uz >= N(0) &&
+                      uz <= N(s.dims[2] - 1u);
+  if (!inside) {  // (no load: an outside u indexes nothing)
+    if (phiOut) *phiOut = N(INFINITY);
+    return false;
+  }
+  const uint32_t ix = min(uint32_t(ux), s.dims[0] - 2u), iy = min(uint32_t(uy), s.dims[1] - 2u), iz = min(uint32_t(uz), s.dims[2] - 2u);
+  const N fx = ux - N(ix), fy = uy - N(iy), fz = uz - N(iz);
+  // (ix + 1, iy + 1, iz + 1) <= dims - 1 each, so the largest index is the product - 1 < 2^31
+  const uint32_t sy = s.dims[2], sx = s.dims[1] * s.dims[2];
+  const uint32_t b = (ix * s.dims[1] + iy) * s.dims[2] + iz;
+  const N c000 = lat[b], c001 = lat[b + 1u], c010 = lat[b + sy], c011 = lat[b + sy + 1u];
+  const N c100 = lat[b + sx], c101 = lat[b + sx + 1u], c110 = lat[b + sx + sy], c111 = lat[b + sx + sy + 1u];
+  const N d00 = c001 - c000, d01 = c011 - c010, d10 = c101 - c100, d11 = c111 - c110;
+  const N cz00 = c000 + fz * d00, cz01 = c010 + fz * d01, cz10 = c100 + fz * d10, cz11 = c110 + fz * d11;
+  const N e0 = cz01 - cz00, e1 = cz11 - cz10;
+  const N cy0 = cz00 + fy * e0, cy1 = cz10 + fy * e1;
+  const N gx = cy1 - cy0;
+  const N phi = cy0 + fx * gx;
+  const N gy = e0 + fx * (e1 - e0);
+  const N t0 = d00 + fy * (d01 - d00), t1 = d10 + fy * (d11 - d10);
+  const N gz = t0 + fx * (t1 - t0);
+  const N len = sqrt((gx * gx + gy * gy) + gz * gz);
+  if (phiOut) *phiOut = phi;
+  const bool hit = phi < s.margin && len > N(0);
+  const N k = (s.margin - phi) / len;
+  const N px = min(maxB[0] / scale, max(minB[0] / scale, (wx + k * gx) / scale));
+  const N py = min(maxB[1] / scale, max(minB[1] / scale, (wy + k * gy) / scale));
+  const N pz = min(maxB[2] / scale, max(minB[2] / scale, (wz + k * gz) / scale));
+  qx = hit ? px : qx, qy = hit ? py : qy, qz = hit ? pz : qz;
+  return hit;
+}
+
+// the box and scale of a pbf_params, rounded to N (pbf_collider_sample; DeltaOp::end takes them from its StepConsts)
+template <typename N> struct ColliderFrame {
+  N scale, minB[3], maxB[3];
+};
+
+// pbf_collider_sample: one lane per point.  points are already rounded to N (world); q = point / scale.
+template <typename N>
+__global__ void k_collider_sample(ColliderSdf<N> s, ColliderFrame<N> f, uint32_t n, const N *__restrict__ points,
+                                  N *__restrict__ phi, N *__restrict__ moved, uint8_t *__restrict__ hit) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  N qx = points[3 * i] / f.scale, qy = points[3 * i + 1] / f.scale, qz = points[3 * i + 2] / f.scale;
+  N v;
+  const bool h = collider_project<N>(s, f.scale, f.minB, f.maxB, qx, qy, qz, &v);
+  phi[i] = v;
+  moved[3 * i] = qx, moved[3 * i + 1] = qy, moved[3 * i + 2] = qz;
+  hit[i] = h ? 1 : 0;
+}

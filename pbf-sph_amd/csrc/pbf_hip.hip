@@ -142,6 +142,7 @@ struct GraphKey {
   StepState before;
   unsigned char params[sizeof(double) * 11 + 32];  // dt, scale, force, bounds, iteration, xsph, vorticity, cohesion, adhesion
   uint64_t n;
+  uint64_t collider;  // pbf_ctx::colliderGen (pbf_set_collider): a replay never runs on a lattice that has been replaced
   int options[10];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
@@ -213,6 +214,12 @@ struct pbf_ctx {
   // pbf_set_surface_tension (opt-in, Akinci 2013): coefficients, the two Jacobi fields of its passes (allocated on first use)
   double cohesion = 0, adhesion = 0;
   DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE, while st.surfaceValid)
+  // pbf_set_collider (opt-in, csrc/pbf_collider.hpp): the lattice in N on the device (NULL = off) and the setting as given.
+  // colliderGen changes with every call: it is part of a captured step's key (graph_key).
+  DevBuf colliderPhi;
+  uint32_t colliderDims[3] = {0, 0, 0};
+  double colliderOrigin[3] = {0, 0, 0}, colliderSpacing = 0, colliderMargin = 0;
+  uint64_t colliderGen = 0;
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
   // the compaction's per-tile counts and total, the pinned words of the drained count's read-back {total, sequence number}
   std::vector<pbf_source> sources;
@@ -1061,8 +1068,25 @@ template <typename N> int stage_lambda(pbf_ctx *ctx, const pbf_params *p, bool f
   return DISPATCH_FAST(ctx, lambda_impl, ctx, p, fuseDiffuse);
 }
 
-template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
-  using Op = DeltaOp<N, FAST>;
+// pbf_set_collider's lattice as DeltaOp<.., COLLIDE = true> and k_collider_sample take it (all zero, phi == NULL, without one)
+bool collider_on(const pbf_ctx *ctx) { return ctx->colliderPhi.p != nullptr; }
+template <typename N> ColliderSdf<N> collider_args(const pbf_ctx *ctx) {
+  ColliderSdf<N> s{};
+  if (!collider_on(ctx)) return s;
+  s.phi = ctx->colliderPhi.as<const N>();
+  for (int a = 0; a < 3; ++a) s.dims[a] = ctx->colliderDims[a], s.origin[a] = N(ctx->colliderOrigin[a]);
+  s.inv = N(1) / N(ctx->colliderSpacing), s.margin = N(ctx->colliderMargin);
+  return s;
+}
+constexpr const char *kColliderSlabError = "a collider is not supported in slab mode (pbf_set_collider(ctx, NULL) clears it)";
+
+template <typename N, bool FAST, bool COLLIDE> int delta_run(pbf_ctx *ctx, const pbf_params *p) {
+  using Op = DeltaOp<N, FAST, COLLIDE>;
+  // (with COLLIDE the lattice follows the stock arguments)
+  auto args = [&](const typename Op::ArgsPlain &plain) {
+    if constexpr (COLLIDE) return typename Op::Args{plain, collider_args<N>(ctx)};
+    else return plain;
+  };
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   StageTimer t(ctx, ST_DELTA);
@@ -1070,7 +1094,7 @@ template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *
   if (ctx->st.delta_on_rows()) {  // list-driven delta-p on the row-major copy
     const int rin = ctx->st.rcur, rout = 1 - rin;
     const uint32_t *key = ctx->key[s].as<const uint32_t>(), *table = ctx->table.as<const uint32_t>();
-    typename Op::Args a{ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()};
+    const typename Op::Args a = args({ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()});
     launch_from_lists<N, Op, true>(ctx, c, a, key, table, row_walk<N>(ctx));
     LAUNCH_CHECK(ctx);
     ctx->st.pstar_moved(/*rows=*/true, rout);
@@ -1079,13 +1103,17 @@ template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *
   if (int rc = materialise_pstar<N>(ctx)) return rc;
   const int in = ctx->st.pcur, out = other_pstar(ctx);
   // delta-p's epilogue also writes the quantised copy of the new pStar: the next iteration's list build needs it
-  typename Op::Args a{ctx->pstar[in].as<const vec4<N>>(), ctx->pstar[out].as<vec4<N>>(), ctx->type[s].as<const uint8_t>(),
-                      ctx->st.qposValid ? ctx->qpos.as<uint2>() : nullptr};
+  const typename Op::Args a = args({ctx->pstar[in].as<const vec4<N>>(), ctx->pstar[out].as<vec4<N>>(), ctx->type[s].as<const uint8_t>(),
+                                    ctx->st.qposValid ? ctx->qpos.as<uint2>() : nullptr});
   const int rc = launch_gather<N, Op>(ctx, c, a, ctx->st.delta_from_lists() ? GATHER_FROM_LISTS : GATHER_PLAIN);
   ctx->st.pstar_moved(/*rows=*/false, rc ? in : out);  // (launched or not: nothing derived from the old pStar is trusted any more)
   return rc;
 }
+template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
+  return collider_on(ctx) ? delta_run<N, FAST, true>(ctx, p) : delta_run<N, FAST, false>(ctx, p);
+}
 template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
+  if (collider_on(ctx) && (ctx->comm || ctx->slabActive || ctx->slabConfigured)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
   return DISPATCH_FAST(ctx, delta_impl, ctx, p);
 }
 
@@ -1741,6 +1769,7 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   std::memcpy(k.params + sizeof(v) + 8, xv, 8);
   std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
+  k.collider = ctx->colliderGen;
   const int opt[10] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
                        int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap)};
   std::memcpy(k.options, opt, sizeof(opt));
@@ -1864,6 +1893,7 @@ int pbf_stage_lambda(pbf_ctx *ctx, const pbf_params *p) {
   return DISPATCH(ctx, stage_lambda, ctx, p);
 }
 int pbf_stage_delta(pbf_ctx *ctx, const pbf_params *p) {
+  if (ctx && collider_on(ctx) && (ctx->comm || ctx->slabActive || ctx->slabConfigured)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
   if (int rc = check(ctx, p, true)) return rc;
   return DISPATCH(ctx, stage_delta, ctx, p);
 }
@@ -2316,6 +2346,90 @@ const char *whitewater_config_error(const pbf_whitewater *g) {
   return nullptr;
 }
 }  // namespace
+
+namespace {
+template <typename N> int set_collider_impl(pbf_ctx *ctx, const pbf_collider_sdf *sdf, size_t nodes, DevBuf &fresh) {
+  const N *phi = static_cast<const N *>(sdf->phi);
+  for (size_t k = 0; k < nodes; ++k)
+    if (phi[k] != phi[k]) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: a NaN in phi");
+  // an allocation of its own, exactly sized: the current lattice stays in place until the new one has arrived
+  HIPCHK(ctx, hipMalloc(&fresh.p, nodes * sizeof(N)));
+  fresh.cap = nodes * sizeof(N);
+  ctx->allocEpoch++;
+  HIPCHK(ctx, hipMemcpyAsync(fresh.p, phi, nodes * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (phi is the caller's)
+  return PBF_OK;
+}
+template <typename N>
+int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, N *phi, N *moved, uint8_t *hit) {
+  std::vector<N> pts(3 * n);
+  for (size_t k = 0; k < 3 * n; ++k) pts[k] = N(points[k]);
+  const size_t e = n * sizeof(N);
+  if (int rc = ensure(ctx, ctx->samplePoints, 3 * e)) return rc;
+  if (int rc = ensure(ctx, ctx->sampleOut, 4 * e + n)) return rc;  // {phi n, moved 3n, hit n bytes}
+  char *out = ctx->sampleOut.as<char>();
+  ColliderFrame<N> f;
+  f.scale = N(p->scale);
+  for (int a = 0; a < 3; ++a) f.minB[a] = N(p->min_bound[a]), f.maxB[a] = N(p->max_bound[a]);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->samplePoints.p, pts.data(), 3 * e, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL((k_collider_sample<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, collider_args<N>(ctx), f, uint32_t(n),
+                     ctx->samplePoints.as<const N>(), reinterpret_cast<N *>(out), reinterpret_cast<N *>(out + e),
+                     reinterpret_cast<uint8_t *>(out + 4 * e));
+  LAUNCH_CHECK(ctx);
+  if (phi) HIPCHK(ctx, hipMemcpyAsync(phi, out, e, hipMemcpyDeviceToHost, ctx->stream));
+  if (moved) HIPCHK(ctx, hipMemcpyAsync(moved, out + e, 3 * e, hipMemcpyDeviceToHost, ctx->stream));
+  if (hit) HIPCHK(ctx, hipMemcpyAsync(hit, out + 4 * e, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pts is a temporary; the caller reads the answers)
+  return PBF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
+  if (!ctx) return PBF_ERR_INVALID;
+  size_t nodes = 1;
+  if (sdf) {
+    for (int a = 0; a < 3; ++a) {
+      if (sdf->dims[a] < 2) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: every dim must be >= 2");
+      if ((nodes *= sdf->dims[a]) >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: 2^31 nodes or more");
+      if (!std::isfinite(sdf->origin[a])) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: origin must be finite");
+    }
+    if (!std::isfinite(sdf->spacing) || !(sdf->spacing > 0)) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: spacing must be finite and > 0");
+    if (!std::isfinite(sdf->margin) || sdf->margin < 0) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: margin must be finite and >= 0");
+    if (!sdf->phi) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: phi == NULL");
+    if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DevBuf fresh;
+  if (sdf)
+    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, sdf, nodes, fresh) : set_collider_impl<float>(ctx, sdf, nodes, fresh)) return rc;
+  // the steps captured so far hold the old lattice's address and can never be asked for again (colliderGen): drop them
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto &g : ctx->graphs)
+    if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
+  ctx->graphs.clear();
+  ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
+  ctx->colliderGen++;
+  for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
+  ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
+  return PBF_OK;
+}
+
+int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, void *phi, void *moved, uint8_t *hit) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!p) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_sample: params == NULL");
+  if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
+  if (n >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_sample: 2^31 points or more");
+  if (n == 0) return PBF_OK;
+  if (!points) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_sample: points == NULL");
+  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_collider_sample: no collider set (pbf_set_collider)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->fp64) return collider_sample_impl<double>(ctx, p, n, points, static_cast<double *>(phi), static_cast<double *>(moved), hit);
+  return collider_sample_impl<float>(ctx, p, n, points, static_cast<float *>(phi), static_cast<float *>(moved), hit);
+}
+
+}  // extern "C"
 
 extern "C" {
 
@@ -3161,6 +3275,7 @@ int pbf_slab_attach(pbf_ctx *ctx, pbf_comm *comm, const uint32_t *cuts, uint32_t
 int pbf_slab_step(pbf_ctx *ctx, const pbf_params *p) { return pbf_slab_steps(ctx, p, 1); }
 int pbf_slab_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   if (int rc = check(ctx, p, false)) return rc;
+  if (collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);  // (set before the ctx was configured or attached)
   if (!ctx->comm) return fail(ctx, PBF_ERR_STATE, "pbf_slab_step needs pbf_slab_attach first");
   if (surface_on(ctx))
     return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_set_surface_tension(ctx, 0, 0) turns it off)");

@@ -5,6 +5,7 @@
 
 #include <type_traits>
 
+#include "pbf_collider.hpp"
 #include "pbf_common.hpp"
 
 namespace pbf {
@@ -812,14 +813,21 @@ template <typename N, bool FAST> struct LambdaOp {
 };
 
 // delta-p + clamp (ompsph.hpp:235-248), Jacobi: reads pstarIn (xyz + lambda), writes pstarOut.
-template <typename N, bool FAST> struct DeltaOp {
+// COLLIDE: pbf_set_collider's projection after the clamp (csrc/pbf_collider.hpp).  A compile-time switch, so that without a
+// collider the kernels and their arguments are exactly what they are without the feature (measured: a run-time test on a
+// lattice pointer in the arguments cost 0.3 % of a 1 M-particle step, profiles/collider_1m.md).
+template <typename N, bool FAST, bool COLLIDE = false> struct DeltaOp {
   using Src = vec4<N>;
-  struct Args {
+  struct ArgsPlain {
     const vec4<N> *pstarIn;
     vec4<N> *pstarOut;
     const uint8_t *type;
     uint2 *qpos;  // may be NULL: the quantised copy of pstarOut for the next iteration's list build
   };
+  struct ArgsSdf : ArgsPlain {
+    ColliderSdf<N> sdf;  // the lattice, sdf.phi != NULL
+  };
+  using Args = std::conditional_t<COLLIDE, ArgsSdf, ArgsPlain>;
   static constexpr bool kNeedsCandidateType = false;
   static constexpr bool kFilter = true;
   static constexpr bool kTileable = true;
@@ -879,7 +887,9 @@ template <typename N, bool FAST> struct DeltaOp {
     x = min(c.maxB[0], max(c.minB[0], x));
     y = min(c.maxB[1], max(c.minB[1], y));
     z = min(c.maxB[2], max(c.minB[2], z));
-    const vec4<N> out = make_vec4<N>(x / c.scale, y / c.scale, z / c.scale, pa.w);
+    x = x / c.scale, y = y / c.scale, z = z / c.scale;
+    if constexpr (COLLIDE) collider_project<N>(a.sdf, c.scale, c.minB, c.maxB, x, y, z, nullptr);
+    const vec4<N> out = make_vec4<N>(x, y, z, pa.w);
     a.pstarOut[i] = out;
     if (a.qpos) {
       bool usable;

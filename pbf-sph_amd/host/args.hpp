@@ -35,6 +35,11 @@ struct Args {
   bool allDevices = false;                // --all-devices: EVERY device matching -d becomes one x-slab (RCCL halo)
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
+  // --collider=sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]] with --resident: opt-in static SDF collider
+  std::string colliderShape;              // "" = off
+  double colliderCfg[4] = {0, 0, 0, 0};
+  double colliderMargin = 13.5;           // half the rest spacing of 27 world units
+  double colliderSpacing = 0;             // 0 = h * scale / 2
   double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
   size_t wwCapacity = 0;                  // 0 = off
   bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
@@ -92,6 +97,12 @@ struct Args {
           "      --slabs=[K]                       K slabs on the first matching device (in-process exchange; tests)\n"
           "      --surface-tension=[g[,b]]         Opt-in surface tension (cohesion g) and adhesion to obstacles (b) after\n"
           "                                        Akinci et al. 2013; not in the reference. Single device only\n"
+          "      --collider=[shape:a,b,c,d[,margin[,spacing]]]  With --resident: an opt-in static solid the fluid is kept out of,\n"
+          "                                        as a signed-distance lattice over the box plus one spacing. shape:\n"
+          "                                        sphere:cx,cy,cz,r (solid ball), bowl:cx,cy,cz,r (solid outside the ball),\n"
+          "                                        plane:nx,ny,nz,d (solid where n.x < d, n normalised). The fluid stays\n"
+          "                                        `margin` world units off the solid (default 13.5); lattice spacing in\n"
+          "                                        world units (default h * scale / 2). Single device only\n"
           "      --whitewater=[k_ta,k_wc[,capacity]]  With --resident: spray, foam and air bubbles after Ihmsen et al. 2012,\n"
           "                                        one whitewater step after every frame at these rates; the tau ranges are\n"
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
@@ -207,6 +218,21 @@ struct Args {
           wwTa = f[0], wwWc = f[1];
           wwCapacity = f.size() == 3 ? size_t(f[2]) : size_t(262144);
           if (!(wwTa >= 0 && wwWc >= 0) || wwCapacity == 0) throw std::runtime_error("--whitewater: rates must be >= 0, capacity >= 1");
+        }
+        else if (value(i, a, "", "--collider", v)) {
+          const size_t colon = v.find(':');
+          const std::string shape = v.substr(0, colon);
+          if (colon == std::string::npos || (shape != "sphere" && shape != "bowl" && shape != "plane"))
+            throw std::runtime_error("--collider: expected sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]]");
+          const auto f = numbers(v.substr(colon + 1));
+          if (f.size() < 4 || f.size() > 6) throw std::runtime_error("--collider: expected four numbers and optionally margin, spacing");
+          colliderShape = shape;
+          for (int k = 0; k < 4; ++k) colliderCfg[k] = f[size_t(k)];
+          if (f.size() > 4) colliderMargin = f[4];
+          if (f.size() > 5) colliderSpacing = f[5];
+          if (shape != "plane" && !(colliderCfg[3] > 0)) throw std::runtime_error("--collider: the radius must be > 0");
+          if (shape == "plane" && !(f[0] * f[0] + f[1] * f[1] + f[2] * f[2] > 0)) throw std::runtime_error("--collider: the normal must not be zero");
+          if (!(colliderMargin >= 0) || !(colliderSpacing >= 0)) throw std::runtime_error("--collider: margin and spacing must be >= 0");
         }
         else if (value(i, a, "", "--surface-tension", v)) {
           const size_t comma = v.find(',');

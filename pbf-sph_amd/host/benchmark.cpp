@@ -112,6 +112,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cerr << "--surface-tension is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
   }
+  const bool collider = !args.colliderShape.empty();
+  if (collider && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--collider is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (collider && !args.resident) std::cout << "--collider takes effect with --resident: ignored" << std::endl;
   if (args.diagnostics && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--diagnostics is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -164,6 +170,33 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   }
   sph::hip_impl::Solver<T, N> solver(N(0.1), devices, flags);
   if (surfaceTension) solver.surfaceTension(N(args.cohesion), N(args.adhesion));
+  if (collider && args.resident) {
+    // the analytic distance on a lattice over the box plus one spacing (float64, rounded to N at the end)
+    const double spacing = args.colliderSpacing > 0 ? args.colliderSpacing : 0.1 * double(param.scale) / 2;
+    const double lo[3] = {double(param.minBound.x), double(param.minBound.y), double(param.minBound.z)};
+    const double hi[3] = {double(param.maxBound.x), double(param.maxBound.y), double(param.maxBound.z)};
+    std::array<uint32_t, 3> dims;
+    std::array<double, 3> origin;
+    for (int a = 0; a < 3; ++a) {
+      origin[size_t(a)] = lo[a] - spacing;
+      dims[size_t(a)] = uint32_t(std::ceil((hi[a] - lo[a]) / spacing)) + 3u;
+    }
+    const double *g = args.colliderCfg;
+    const double nl = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    std::vector<N> phi(size_t(dims[0]) * dims[1] * dims[2]);
+    for (uint32_t i = 0; i < dims[0]; ++i)
+      for (uint32_t j = 0; j < dims[1]; ++j)
+        for (uint32_t k = 0; k < dims[2]; ++k) {
+          const double x = origin[0] + i * spacing, y = origin[1] + j * spacing, z = origin[2] + k * spacing;
+          double d;
+          if (args.colliderShape == "plane") d = (g[0] * x + g[1] * y + g[2] * z) / nl - g[3];
+          else d = std::sqrt((x - g[0]) * (x - g[0]) + (y - g[1]) * (y - g[1]) + (z - g[2]) * (z - g[2])) - g[3];
+          phi[(size_t(i) * dims[1] + j) * dims[2] + k] = N(args.colliderShape == "bowl" ? -d : d);
+        }
+    solver.setCollider(dims, origin, spacing, args.colliderMargin, phi.data());
+    std::cout << "Collider             : " << args.colliderShape << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2]
+              << ", spacing " << spacing << ", margin " << args.colliderMargin << std::endl;
+  }
   if (args.indexedMesh) solver.indexedMesh(true);
   sph::hip_impl::IndexedMesh<N, sph::vec> indexed;  // --indexed-mesh --resident: the last frame's mesh
   // the resident arrays grow by what the inlets emit: room for every frame of the run

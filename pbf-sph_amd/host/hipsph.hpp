@@ -419,6 +419,24 @@ public:
     return *this;
   }
 
+  // Opt-in static collider (pbf_set_collider; no reference counterpart): a signed-distance lattice — phi[(i * dims[1] + j) *
+  // dims[2] + k] at origin + (i, j, k) * spacing, world units, negative inside the solid — that delta-p keeps the fluid out
+  // of, at phi >= margin.  Copied to the device; persists for every later step and advance() until clearCollider().  A
+  // single-device feature (not in slab mode).
+  Solver &setCollider(const std::array<uint32_t, 3> &dims, const std::array<double, 3> &origin, double spacing, double margin,
+                      const N *phi) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_collider_sdf sdf{};
+    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
+    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = phi;
+    check(pbf_set_collider(ctx_, &sdf), "pbf_set_collider");
+    return *this;
+  }
+  Solver &clearCollider() {
+    if (!multi()) check(pbf_set_collider(ctx_, nullptr), "pbf_set_collider");
+    return *this;
+  }
+
   // ---- device-resident path -------------------------------------------------------------------
   // Several devices: `config` places the cuts (its bounds and scale define the grid columns); the slabs start with
   // equal particle counts.
