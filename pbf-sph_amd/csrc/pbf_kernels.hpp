@@ -2058,6 +2058,31 @@ __global__ __launch_bounds__(DIFFUSE_ROW_THREADS) void k_diffuse_rows(StepConsts
   }
 }
 
+// The LAST trip of a wave-uniform loop, sized to what the wave's longest lane has left instead of a whole trip of FULL units:
+// the narrowest of STEP, 2 STEP, ... (< FULL), FULL that no lane's remainder exceeds.  more(k) is a wave vote: "some lane has
+// more than k units left"; trip(width) runs one trip of that compile-time width.  Same units in the same order as a full trip
+// (the executed slots beyond a lane's remainder are masked in either), so the choice cannot change a result.
+// STEP >= FULL: always the full trip, and no vote.
+template <uint32_t FULL, uint32_t STEP, uint32_t TW = STEP, typename More, typename Trip>
+__device__ __forceinline__ void narrowest_trip(More &&more, Trip &&trip) {
+  if constexpr (TW >= FULL) {
+    trip(std::integral_constant<uint32_t, FULL>{});
+  } else {
+    if (more(TW))
+      narrowest_trip<FULL, STEP, TW + STEP>(more, trip);
+    else
+      trip(std::integral_constant<uint32_t, TW>{});
+  }
+}
+// the widest trip narrower than FULL that narrowest_trip<FULL, STEP> can choose (0: none)
+template <uint32_t FULL, uint32_t STEP> constexpr uint32_t widest_partial_trip() { return STEP >= FULL ? 0u : (FULL - 1u) / STEP * STEP; }
+
+// the granularity of the last test trip of k_build_rows_op in pair loads (A/B builds override it; W reproduces the fixed-width
+// loop's text).  Measured at 1 M, per launch: 4 -> 188.1 us, 2 -> 186.2, 1 -> 184.2 (profiles/tail_trips_1m.md)
+#ifndef PBF_BUILD_TAIL
+#define PBF_BUILD_TAIL 1
+#endif
+
 // The list build with an op riding on it, on the row-major copy: lane = row slot.  A (dy, dz) row of three x cells is ONE
 // run [lintab[c - 1], lintab[c + 2]) — walked in pairs (one 16-byte load = two quantised candidates) from a per-lane byte
 // offset that advances by a constant per trip: no run select, no padding slot, one limit compare per slot.
@@ -2158,21 +2183,33 @@ __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typena
     // (two nested loops: the inner one — trips until a lane's staging list is full or the row is done — touches no state of
     // the drain, so its loop-carried registers are the walk's own four; with the drain inside the trip loop the compiler
     // copied the op's accumulators and the writer's state at the head of every trip: 8 v_mov per trip)
-    for (uint32_t t = 0; __any(t < L);) {
-      do {
-        if (t < L) {
-          QPair cnd[W];
+    uint32_t t = 0;
+    auto trip = [&](auto width) {  // TW pair loads = 2 TW candidate slots
+      constexpr uint32_t TW = decltype(width)::value;
+      if (t < L) {
+        QPair cnd[TW];
 #pragma unroll
-          for (uint32_t w = 0; w < W; ++w) cnd[w] = *reinterpret_cast<const QPair *>(qbase + off + 16u * w);  // (slots past L: padding / the next run, masked)
+        for (uint32_t w = 0; w < TW; ++w) cnd[w] = *reinterpret_cast<const QPair *>(qbase + off + 16u * w);  // (slots past L: padding / the next run, masked)
 #pragma unroll
-          for (uint32_t w = 0; w < W; ++w) {
-            const bool hit0 = (t + 2 * w < L) & filter.within(cnd[w].ax, cnd[w].ay);
-            append(cur, b0 + 2 * w, hit0);  // branch-free: the slot is kept only on a hit
-            const bool hit1 = (t + 2 * w + 1 < L) & filter.within(cnd[w].bx, cnd[w].by);
-            append(cur, b0 + 2 * w + 1u, hit1);
-          }
+        for (uint32_t w = 0; w < TW; ++w) {
+          const bool hit0 = (t + 2 * w < L) & filter.within(cnd[w].ax, cnd[w].ay);
+          append(cur, b0 + 2 * w, hit0);  // branch-free: the slot is kept only on a hit
+          const bool hit1 = (t + 2 * w + 1 < L) & filter.within(cnd[w].bx, cnd[w].by);
+          append(cur, b0 + 2 * w + 1u, hit1);
         }
-        off += 16u * W, b0 += 2 * W, t += 2 * W;
+      }
+      off += 16u * TW, b0 += 2 * TW, t += 2 * TW;
+    };
+    auto more = [&](uint32_t pairs) { return __any(t + 2 * pairs < L) != 0; };  // (among the lanes still here)
+    constexpr uint32_t TAIL = PBF_BUILD_TAIL, PARTIAL = widest_partial_trip<uint32_t(W), TAIL>();
+    for (; __any(t < L);) {
+      do {
+        // a full trip while some lane has more left than the widest partial trip covers; then the row's last trip, cut to the
+        // longest lane's remainder in steps of TAIL pair loads (a run is ~21 slots: the 8-slot last trip was mostly padding)
+        if (PARTIAL == 0u || more(PARTIAL))
+          trip(std::integral_constant<uint32_t, uint32_t(W)>{});
+        else
+          narrowest_trip<uint32_t(W), TAIL>(more, trip);
       } while (__any(t < L) && !__any(cur >= lfull));
       if (__any(cur >= lfull)) flush();
     }
