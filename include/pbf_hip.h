@@ -508,6 +508,22 @@ int pbf_anisotropy_compute(pbf_ctx *ctx, const pbf_params *params, const pbf_ani
  * terms' own operand ranges densely (csrc/pbf_kernels.hpp k_selftest_math64); all four must be 0. */
 int pbf_selftest_math(pbf_ctx *ctx, uint64_t mismatches[4]);
 
+/* The same sweep with a count of what it visited, and the trimmed divides at the operands their later callers hand them
+ * (csrc/pbf_kernels.hpp k_selftest_divides / k_selftest_divides64).  mismatches[k] / visited[k]:
+ *   [0 .. 3]  pbf_selftest_math's four categories; visited = operands compared (quotients, for [1]);
+ *   [4]  div_ranged(a, d) as the marching-cubes field uses it: every fp32 d with 1e-18 < d <= 64; a = 25, 1 and
+ *        `numerators` (<= 64) signed pseudo-random 2^e m, e uniform over [-100, 5], per divisor;
+ *   [5]  the same divisors with the numerators the field can also meet — +-0, denormals, |a| < 2^-100 (6 fixed +
+ *        `numerators` drawn per divisor) — in the field's form: the trimmed divide where every numerator of the hit is at
+ *        least 2^-100 in magnitude, the compiler's divide otherwise;
+ *   [6]  div_seeded(a, r, y) as surface tension uses it: r, y from the trimmed sqrt of every fp32 d2 whose root lies in
+ *        [1e-8, 0.2]; a = 0 and `numerators` signed pseudo-random 2^e m, e uniform over [-100, 20], per divisor;
+ *   [7]  the operands of [5] through div_ranged alone, without the fall-back (what the guard is for: reported only).
+ * Every fp32 category is exhaustive in the divisor, so visited[k] is a number the caller can compute.  On an fp64 context
+ * the categories are drawn pseudo-randomly (divisors log-uniform over the range and uniform over [0.03, 8]; numerators
+ * below 2^-100 for [5] and [7], as in fp32), 1.07e10 each — visited[k] = rounds x threads — and `numerators` is ignored. */
+int pbf_selftest_divides(pbf_ctx *ctx, uint32_t numerators, uint64_t mismatches[8], uint64_t visited[8]);
+
 /* Mean milliseconds per call of each stage since the last pbf_reset_stage_times (needs
  * PBF_FLAG_STAGE_TIMING).  names[i] points at static strings that follow the reference's Stopwatch
  * entries (ompsph.hpp:130,157,161,188,209,252); an entry named "stage/part" is a sub-interval of "stage"

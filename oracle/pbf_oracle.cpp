@@ -150,6 +150,7 @@ template <typename N> struct Oracle final : pbf_oracle {
   std::vector<V3<N>> meshV, meshN;
   std::vector<V4<N>> meshC;
   bool pow4 = false;
+  bool sqrtInfluence = false;
 
   size_t n() const { return id.size(); }
 
@@ -508,7 +509,9 @@ template <typename N> struct Oracle final : pbf_oracle {
               const V3<N> l = this->pos[b] - a;
               const N len = std::sqrt(dot(l, l));
               if (!(len < threshold)) continue;
-              const N denominator = std::pow(len, particleInfluence);
+              // `sqrtInfluence` (tests): with the stock influence 0.5 the correctly rounded square root, the device's
+              // form, stands in for the reference's glm::pow(len, 0.5); any other influence keeps std::pow
+              const N denominator = (sqrtInfluence && particleInfluence == N(0.5)) ? std::sqrt(len) : std::pow(len, particleInfluence);
               v += (particleSize / denominator);
               normal = normal + (l / denominator) * ((-particleInfluence) * particleSize);
               colourAcc = {colourAcc.x + colour[b].x, colourAcc.y + colour[b].y, colourAcc.z + colour[b].z,
@@ -874,6 +877,10 @@ int pbf_oracle_set_scratch(pbf_oracle *o, const uint64_t *keys, const void *psta
 
 void pbf_oracle_set_pow4(pbf_oracle *o, int on) {
   dispatch(o, [&](auto &s) { s.pow4 = on != 0; return 0; });
+}
+
+void pbf_oracle_set_sqrt_influence(pbf_oracle *o, int on) {
+  dispatch(o, [&](auto &s) { s.sqrtInfluence = on != 0; return 0; });
 }
 
 // ---- scene dynamics on the host side of advance() (ompsph.hpp:91-126, 167-186) ------------------------------

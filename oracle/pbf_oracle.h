@@ -130,6 +130,13 @@ int pbf_oracle_set_scratch(pbf_oracle *, const uint64_t *keys, const void *pstar
  * of the reference's std::pow (ompsph.hpp:240).  Default off = reference semantics. */
 void pbf_oracle_set_pow4(pbf_oracle *, int on);
 
+/* The second documented substitution (tests only): when on AND particle_influence == 0.5 (the stock value,
+ * sph.hpp:183), the marching-cubes field takes the correctly rounded std::sqrt(len), the device's form, where the
+ * reference takes glm::pow(len, 0.5) (ompsph.hpp:340) — nothing else changes, and any other influence keeps
+ * std::pow.  A libm pow has no bit contract; a correctly rounded square root has one, so with this switch the
+ * device's field can be held to the oracle's bit for bit.  Default off = reference semantics. */
+void pbf_oracle_set_sqrt_influence(pbf_oracle *, int on);
+
 const char *pbf_oracle_last_error(void);
 
 /* Scene dynamics on the host side of advance() (ompsph.hpp:91-126, 167-186): sources emit a floor(sqrt(rate)) x

@@ -220,6 +220,7 @@ _SIGS = {
     "pbf_read_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "pbf_table_size": (C.c_size_t, [C.c_void_p]),
     "pbf_selftest_math": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pbf_selftest_divides": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pbf_grid_extent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
                                   C.c_int]),
@@ -743,6 +744,12 @@ class Solver:
         m = np.zeros(3, np.float64)
         self._chk(self.L.pbf_grid_extent(self.ctx, _vp(e), _vp(m)), "grid_extent")
         return e, m
+
+    def selftest_divides(self, numerators=8):
+        """pbf_selftest_divides -> (mismatches[8], visited[8]) (include/pbf_hip.h names the categories)."""
+        bad, seen = np.zeros(8, np.uint64), np.zeros(8, np.uint64)
+        self._chk(self.L.pbf_selftest_divides(self.ctx, int(numerators), _vp(bad), _vp(seen)), "pbf_selftest_divides")
+        return bad, seen
 
     def stage_times(self):
         names = (C.c_char_p * 16)()

@@ -2643,35 +2643,61 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
   return PBF_OK;
 }
 
-int pbf_selftest_math(pbf_ctx *ctx, uint64_t mismatches[4]) {
-  if (!ctx || !mismatches) return PBF_ERR_INVALID;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (int rc = ensure(ctx, ctx->selTotals, 64)) return rc;
-  HIPCHK(ctx, hipMemsetAsync(ctx->selTotals.p, 0, 32, ctx->stream));
+// fp64 sweeps: 2^20 threads x 10240 rounds = 1.07e10 pseudo-random operands per category
+constexpr uint32_t kSelftestRounds64 = 10240, kSelftestBlocks64 = 4096;
+// the four categories of k_selftest_math / k_selftest_math64 into totals[0 .. 3], their visited counts into totals[4 .. 7]
+static int launch_selftest_math(pbf_ctx *ctx, unsigned long long *totals) {
   if (ctx->fp64) {  // 1.07e10 pseudo-random operands per category and run (exhaustive is impossible in fp64): 2^20 threads x 10240
     const double h = ctx->desc.h;
     const double p6 = poly6_factor<double>(h), r = double(CorrDeltaQ * h), d = (h * h) - r * r;
-    const uint32_t rounds = 10240, blocks = 4096;
-    hipLaunchKernelGGL(k_selftest_math64, dim3(blocks), dim3(BLOCK), 0, ctx->stream, ctx->selTotals.as<unsigned long long>(),
-                       p6 * (d * d * d), double(RHO), h, rounds);
+    hipLaunchKernelGGL(k_selftest_math64, dim3(kSelftestBlocks64), dim3(BLOCK), 0, ctx->stream, totals, p6 * (d * d * d),
+                       double(RHO), h, kSelftestRounds64);
     LAUNCH_CHECK(ctx);
-    unsigned long long hst[4] = {0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(hst, ctx->selTotals.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 4; ++k) mismatches[k] = hst[k];
     return PBF_OK;
   }
   // the two per-launch constant divisors of delta-p for this context's h: poly6(0.3 h) and the reference density
   const float h = float(ctx->desc.h);
   const float p6 = poly6_factor<float>(h), r = float(CorrDeltaQ * h), d = (h * h) - r * r;
   const float p6DeltaQ = p6 * (d * d * d);
-  hipLaunchKernelGGL(k_selftest_math, dim3(uint32_t(ctx->numCUs) * 8), dim3(BLOCK), 0, ctx->stream,
-                     ctx->selTotals.as<unsigned long long>(), p6DeltaQ, float(RHO), h);
+  hipLaunchKernelGGL(k_selftest_math, dim3(uint32_t(ctx->numCUs) * 8), dim3(BLOCK), 0, ctx->stream, totals, p6DeltaQ,
+                     float(RHO), h);
   LAUNCH_CHECK(ctx);
+  return PBF_OK;
+}
+
+int pbf_selftest_math(pbf_ctx *ctx, uint64_t mismatches[4]) {
+  if (!ctx || !mismatches) return PBF_ERR_INVALID;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure(ctx, ctx->selTotals, 128)) return rc;
+  HIPCHK(ctx, hipMemsetAsync(ctx->selTotals.p, 0, 64, ctx->stream));
+  if (int rc = launch_selftest_math(ctx, ctx->selTotals.as<unsigned long long>())) return rc;
   unsigned long long hst[4] = {0, 0, 0, 0};
   HIPCHK(ctx, hipMemcpyAsync(hst, ctx->selTotals.p, 32, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < 4; ++k) mismatches[k] = hst[k];
+  return PBF_OK;
+}
+
+int pbf_selftest_divides(pbf_ctx *ctx, uint32_t numerators, uint64_t mismatches[8], uint64_t visited[8]) {
+  if (!ctx || !mismatches || !visited) return PBF_ERR_INVALID;
+  if (numerators > 64u) return fail(ctx, PBF_ERR_INVALID, "pbf_selftest_divides: at most 64 numerators per divisor");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure(ctx, ctx->selTotals, 128)) return rc;
+  HIPCHK(ctx, hipMemsetAsync(ctx->selTotals.p, 0, 128, ctx->stream));
+  unsigned long long *totals = ctx->selTotals.as<unsigned long long>();
+  if (int rc = launch_selftest_math(ctx, totals)) return rc;
+  if (ctx->fp64) hipLaunchKernelGGL(k_selftest_divides64, dim3(kSelftestBlocks64), dim3(BLOCK), 0, ctx->stream, totals + 8,
+                                    kSelftestRounds64);
+  else hipLaunchKernelGGL(k_selftest_divides, dim3(uint32_t(ctx->numCUs) * 8), dim3(BLOCK), 0, ctx->stream, totals + 8,
+                          numerators);
+  LAUNCH_CHECK(ctx);
+  unsigned long long hst[16] = {};
+  HIPCHK(ctx, hipMemcpyAsync(hst, ctx->selTotals.p, 128, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 4; ++k) {
+    mismatches[k] = hst[k], visited[k] = hst[4 + k];
+    mismatches[4 + k] = hst[8 + k], visited[4 + k] = hst[12 + k];
+  }
   return PBF_OK;
 }
 

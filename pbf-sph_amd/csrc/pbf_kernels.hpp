@@ -581,7 +581,9 @@ __device__ inline double fast_rsq(double x) { return 1.0 / sqrt(x); }  // fp64 k
 //     correction — 5 fma / mul, no v_rcp (a second correction, as a general-purpose divide would carry, changes no
 //     result on the swept operands).  With 1e-8 <= r <= h nothing needs scaling or fixing and the result is the
 //     IEEE quotient bit for bit (swept: every fp32 d2 whose root lies in [1e-8, h], four h); outside that range the
-//     quotient is never used (selected away).
+//     quotient is never used (selected away).  Surface tension divides its signed `radial` by the same r with the same
+//     seed: swept for every fp32 d2 whose root lies in [1e-8, 0.2] against +0 and pseudo-random numerators of either sign,
+//     2^-100 ... 2^21 in magnitude (k_selftest_divides [2]; fp64: pseudo-random r of that range, k_selftest_divides64).
 //   * div_ranged (reciprocal of a per-launch CONSTANT divisor, hoisted out of the loops by the compiler) serves
 //     delta-p's poly6(r) / poly6(0.3 h) — numerator 0 or 1e-18 ... 1.6e3 in magnitude; k_selftest_math sweeps EVERY
 //     fp32 numerator between 1e-30 and 1e30: identical but for -0 -> +0, and the quotient is only ever squared — and
@@ -589,6 +591,11 @@ __device__ inline double fast_rsq(double x) { return 1.0 / sqrt(x); }  // fp64 k
 //     r = h): identical for every |numerator| >= 2^-100 (swept; again but for the sign of a zero, which only ever
 //     multiplies into a term that is added to a sum), and DeltaOp falls back to the compiler's divide for a whole wave
 //     when one lane's numerator is smaller than that.
+//     With a per-candidate divisor it serves the marching-cubes field (pbf_mc.hpp k_mc_field): swept over every fp32
+//     divisor in (1e-18, 64] against the numerators 25, 1 and pseudo-random ones of 2^-100 ... 2^6 in magnitude —
+//     identical —, and against -0, denormals and |numerator| < 2^-100 — NOT identical (-0 gives +0, a denormal loses
+//     its residual), so the field takes the compiler's divide for a whole wave there (div_ranged_ok_finite), as DeltaOp
+//     does (k_selftest_divides [0], [1], [3]).
 __device__ inline float sqrt_rsq(float x, float &y) {
   x += 0x1p-100f;
   y = __builtin_amdgcn_rsqf(x);
@@ -621,7 +628,8 @@ __device__ inline float div_seeded(float a, float b, float y) {
   y = fmaf(fmaf(-b, y, 1.0f), y, y);
   const float q = a * y;
   return fmaf(fmaf(-b, q, a), y, q);  // ONE residual correction: relative error ~2^-47 before the final rounding — enough
-                                      // for every operand the sweeps visit (k_selftest_math), which is every operand used
+                                      // for every operand the sweeps visit (k_selftest_math, k_selftest_divides: the ranges
+                                      // are listed above and at the kernels; a caller outside them has not been swept)
 }
 // a / b in fp64 from a seed y ~ 1 / b: hipcc's IEEE divide is v_div_scale x 2, v_rcp_f64, two Newton steps on the
 // reciprocal, the quotient, its exact residual (fma) and one correction (v_div_fmas), then v_div_fixup: 11 VALU, two of
@@ -647,6 +655,12 @@ __device__ inline double div_ranged(double a, double b) { return div_newton<2>(a
 // infinity into a NaN, which fails the compare like a NaN, a zero or a tiny numerator does)
 __device__ inline bool div_ranged_ok(float x) { return fabsf(fmaf(x, 0.0f, x)) >= 0x1p-100f; }
 __device__ inline bool div_ranged_ok(double x) { return fabs(fma(x, 0.0, x)) >= 0x1p-700; }  // (no scaling by v_div_scale)
+// The same for numerators known to be FINITE (the marching-cubes field's l = p - a), three at once: one min3 and one compare
+__device__ inline bool div_ranged_ok_finite(float x) { return fabsf(x) >= 0x1p-100f; }
+__device__ inline bool div_ranged_ok_finite(double x) { return fabs(x) >= 0x1p-100; }  // (the bound the sweep starts from)
+template <typename N> __device__ inline bool div_ranged_ok_finite(N x, N y, N z) {
+  return div_ranged_ok_finite(min(min(fabs(x), fabs(y)), fabs(z)));
+}
 
 template <typename N, bool FAST>
 __device__ inline PairGeom<N, FAST> pair_geom(const vec4<N> &a, const vec4<N> &b, N h) {
@@ -2517,9 +2531,11 @@ __global__ __launch_bounds__(BLOCK) void k_pack_aos(uint32_t n, uint8_t *__restr
 //           by-product of sqrt_rsq(d2) — exactly the operands pair_geom hands it — for four h;
 //   bad[2]  div_ranged(x, poly6(0.3 h)) over every fp32 x with 1e-30 <= |x| <= 1e30 or x == 0 (NaNs compare by class);
 //   bad[3]  DeltaOp's x / RHO — div_ranged where div_ranged_ok(x), the compiler's divide otherwise — over EVERY fp32 x.
+// bad[4 .. 7]: how many operands (quotients, for bad[1]) each category visited — a range filter that excluded everything
+// would otherwise read as "no mismatch" (pbf_selftest_divides hands them out).
 __global__ __launch_bounds__(BLOCK) void k_selftest_math(unsigned long long *__restrict__ bad, float divisorA,
                                                          float divisorB, float hOwn) {
-  unsigned long long badSqrt = 0, badDiv = 0, badA = 0, badB = 0;
+  unsigned long long badSqrt = 0, badDiv = 0, badA = 0, badB = 0, nSqrt = 0, nDiv = 0, nA = 0, nB = 0;
   const float hs[4] = {hOwn, 0.05f, 0.2f, 0.0999999f};  // the context's own h (0.1 in every shipped configuration) + three more
   for (uint64_t v = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; v < (1ull << 32); v += uint64_t(gridDim.x) * BLOCK) {
     const float x = __int_as_float(int(uint32_t(v)));
@@ -2527,12 +2543,14 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_math(unsigned long long *__r
       float y;
       const float r = sqrt_rsq(x, y), ref = sqrtf(x);
       badSqrt += __float_as_int(r) != __float_as_int(ref);
+      ++nSqrt;
       if (ref >= 1e-8f && ref <= fmaxf(0.2f, hOwn)) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           if (ref <= hs[k]) {
             const float hr = hs[k] - ref, num = hr * hr;
             badDiv += __float_as_int(div_seeded(num, ref, y)) != __float_as_int(num / ref);
+            ++nDiv;
           }
       }
     }
@@ -2542,12 +2560,14 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_math(unsigned long long *__r
       badA += mid && ((qa != qa) ? !(ra != ra) : __float_as_int(qa) != __float_as_int(ra));
       const float rb = x / divisorB, qb = div_ranged_ok(x) ? div_ranged(x, divisorB) : rb;
       badB += (qb != qb) ? !(rb != rb) : __float_as_int(qb) != __float_as_int(rb);
+      nA += mid, ++nB;
     }
   }
   if (badSqrt) atomicAdd(&bad[0], badSqrt);
   if (badDiv) atomicAdd(&bad[1], badDiv);
   if (badA) atomicAdd(&bad[2], badA);
   if (badB) atomicAdd(&bad[3], badB);
+  atomicAdd(&bad[4], nSqrt), atomicAdd(&bad[5], nDiv), atomicAdd(&bad[6], nA), atomicAdd(&bad[7], nB);
 }
 
 // The fp64 counterpart: an exhaustive sweep is impossible (2^64 operands), so `rounds` x gridDim x BLOCK pseudo-random
@@ -2573,7 +2593,7 @@ __device__ inline double pow2_times_mantissa(uint64_t u, int elo, int ehi) {    
 }
 __global__ __launch_bounds__(BLOCK) void k_selftest_math64(unsigned long long *__restrict__ bad, double divisorA,
                                                            double divisorB, double hOwn, uint32_t rounds) {
-  unsigned long long badSqrt = 0, badDiv = 0, badA = 0, badB = 0;
+  unsigned long long badSqrt = 0, badDiv = 0, badA = 0, badB = 0, nSqrt = 0, nDiv = 0, nA = 0, nB = 0;
   const double hs[4] = {hOwn, 0.05, 0.2, 0.0999999};
   const uint64_t tid = uint64_t(blockIdx.x) * BLOCK + threadIdx.x, stride = uint64_t(gridDim.x) * BLOCK;
   for (uint32_t k = 0; k < rounds; ++k) {
@@ -2587,6 +2607,7 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_math64(unsigned long long *_
       }
       double y;
       badSqrt += __double_as_longlong(sqrt_rsq(x, y)) != __double_as_longlong(sqrt(x));
+      ++nSqrt;
     }
     {
       const double hk = hs[(u0 >> 1) & 3u];
@@ -2597,6 +2618,7 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_math64(unsigned long long *_
       if (root >= 1e-8 && root <= hk) {
         const double hr = hk - root, num = hr * hr;
         badDiv += __double_as_longlong(div_seeded(num, root, y)) != __double_as_longlong(num / root);
+        ++nDiv;
       }
     }
     {
@@ -2608,12 +2630,124 @@ __global__ __launch_bounds__(BLOCK) void k_selftest_math64(unsigned long long *_
       if (u3 & 2u) z = -z;
       const double rb = z / divisorB, qb = div_ranged_ok(z) ? div_ranged(z, divisorB) : rb;
       badB += __double_as_longlong(qb) != __double_as_longlong(rb);
+      ++nA, ++nB;
     }
   }
   if (badSqrt) atomicAdd(&bad[0], badSqrt);
   if (badDiv) atomicAdd(&bad[1], badDiv);
   if (badA) atomicAdd(&bad[2], badA);
   if (badB) atomicAdd(&bad[3], badB);
+  atomicAdd(&bad[4], nSqrt), atomicAdd(&bad[5], nDiv), atomicAdd(&bad[6], nA), atomicAdd(&bad[7], nB);
+}
+
+// ---- the trimmed divides at the operands their LATER callers hand them (pbf_selftest_divides) ---------------------------
+// k_mc_field divides by a per-candidate denominator (sqrt(len), or len^influence), SurfaceTensionOp divides an arbitrary
+// signed `radial` by r.  Per category out[k] = mismatches against the compiler's IEEE divide, bit for bit, out[4 + k] =
+// quotients visited:
+//   [0]  div_ranged(a, d), every fp32 d with 1e-18 < d <= 64 (the field's own guard ... the largest threshold h * scale of a
+//        test scene, which bounds sqrt(len), len^0.75 and len alike); a = the particle sizes 25 and 1 and `numerators` signed
+//        pseudo-random 2^e m, e uniform over [-100, 5], hashed from d's bits and the numerator's number;
+//   [1]  the same divisors, the numerators k_mc_field's l = p - a can take beside those: +0, -0, the smallest and the largest
+//        denormal of either sign and `numerators` more, alternately a random denormal and a random |a| in [2^-126, 2^-100) —
+//        in the CALL SITE's form: div_ranged where div_ranged_ok_finite(a), the compiler's divide otherwise;
+//   [2]  div_seeded(a, r, y), r and y from sqrt_rsq(d2) for every fp32 d2 whose root lies in [1e-8, 0.2] (pair_geom's operands
+//        for every h up to 0.2); a = +0 and `numerators` signed pseudo-random 2^e m, e uniform over [-100, 20]: surface
+//        tension's radial / r;
+//   [3]  div_ranged itself on the operands of [1], no fall-back: what the guard is there for (reported, not required 0).
+__device__ inline float selftest_pow2m(uint64_t u, int elo, int ehi) {  // +-2^e m, m in [1, 2): assembled from the bits
+  const uint32_t e = uint32_t(elo + 127) + uint32_t((u >> 32) % uint64_t(ehi - elo + 1));
+  return __int_as_float(int((uint32_t(u >> 23) << 31) | (e << 23) | (uint32_t(u) & 0x7FFFFFu)));
+}
+__global__ __launch_bounds__(BLOCK) void k_selftest_divides(unsigned long long *__restrict__ out, uint32_t numerators) {
+  unsigned long long bad[4] = {0, 0, 0, 0}, seen[4] = {0, 0, 0, 0};
+  auto differ = [](float q, float ref) { return __float_as_int(q) != __float_as_int(ref); };
+  for (uint64_t v = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; v < (1ull << 32); v += uint64_t(gridDim.x) * BLOCK) {
+    const float d = __int_as_float(int(uint32_t(v)));
+    if (d > 1e-18f && d <= 64.0f) {
+      bad[0] += differ(div_ranged(25.0f, d), 25.0f / d) + differ(div_ranged(1.0f, d), 1.0f / d);
+      for (uint32_t j = 0; j < numerators; ++j) {
+        const float a = selftest_pow2m(splitmix64(v * 256u + j), -100, 5);
+        bad[0] += differ(div_ranged(a, d), a / d);
+      }
+      seen[0] += 2u + numerators;
+      const uint32_t fixed[6] = {0u, 0x80000000u, 1u, 0x80000001u, 0x007FFFFFu, 0x807FFFFFu};
+      for (uint32_t j = 0; j < 6u + numerators; ++j) {
+        float a;
+        if (j < 6u) a = __int_as_float(int(fixed[j]));
+        else {
+          const uint64_t u = splitmix64(v * 256u + 128u + j);
+          const uint32_t mant = uint32_t(u) & 0x7FFFFFu;
+          a = (j & 1u) ? selftest_pow2m(u, -126, -101) : __int_as_float(int((uint32_t(u >> 23) << 31) | (mant ? mant : 1u)));
+        }
+        const float ref = a / d, raw = div_ranged(a, d);
+        bad[1] += differ(div_ranged_ok_finite(a) ? raw : ref, ref);
+        bad[3] += differ(raw, ref);
+      }
+      seen[1] += 6u + numerators, seen[3] += 6u + numerators;
+    }
+    if (d >= 0x1p-75f && d <= 3.0e38f) {
+      float y;
+      const float r = sqrt_rsq(d, y);
+      if (r >= 1e-8f && r <= 0.2f) {
+        bad[2] += differ(div_seeded(0.0f, r, y), 0.0f / r);
+        for (uint32_t j = 0; j < numerators; ++j) {
+          const float a = selftest_pow2m(splitmix64(v * 256u + 64u + j), -100, 20);
+          bad[2] += differ(div_seeded(a, r, y), a / r);
+        }
+        seen[2] += 1u + numerators;
+      }
+    }
+  }
+  for (int k = 0; k < 4; ++k) {
+    if (bad[k]) atomicAdd(&out[k], bad[k]);
+    atomicAdd(&out[4 + k], seen[k]);
+  }
+}
+
+// The fp64 counterpart, drawn as k_selftest_math64 draws: `rounds` x gridDim x BLOCK quotients per category.  The divisor of
+// [0], [1] and [3] is log-uniform over (1e-18, 64] (half of the draws) or uniform over [0.03, 8]; the numerator of [0] is 25, 1
+// (one draw in eight each) or 2^e m with e uniform over [-100, 5]; of [1] and [3] +-0 (one draw in eight), a denormal (three) or
+// |a| = 2^e m with e uniform over [-1022, -101] (four) — below div_ranged_ok_finite's 2^-100; [2] takes d2 = r^2 with r log-uniform over
+// [1e-8, 0.2] (half) or uniform, kept where sqrt_rsq's root lies in [1e-8, 0.2] — every draw, by the margins taken —, and a = 0
+// (one draw in eight) or 2^e m with e uniform over [-100, 20].
+__global__ __launch_bounds__(BLOCK) void k_selftest_divides64(unsigned long long *__restrict__ out, uint32_t rounds) {
+  unsigned long long bad[4] = {0, 0, 0, 0}, seen[4] = {0, 0, 0, 0};
+  auto differ = [](double q, double ref) { return __double_as_longlong(q) != __double_as_longlong(ref); };
+  const uint64_t tid = uint64_t(blockIdx.x) * BLOCK + threadIdx.x, stride = uint64_t(gridDim.x) * BLOCK;
+  for (uint32_t k = 0; k < rounds; ++k) {
+    const uint64_t u0 = splitmix64((tid + k * stride) * 8u + 1u), u1 = splitmix64(u0), u2 = splitmix64(u1), u3 = splitmix64(u2),
+                   u4 = splitmix64(u3), u5 = splitmix64(u4);
+    // log2(1e-18) = -59.79..., log2(64) = 6: exp2 of [-59.79, 6) stays inside (1e-18, 64]
+    const double d = (u0 & 1u) ? exp2(-59.79 + unit53(u1) * 65.79) : 0.03 + unit53(u1) * 7.97;
+    if (d > 1e-18 && d <= 64.0) {
+      const uint32_t pick = uint32_t(u0 >> 1) & 7u;
+      double a = pick == 0u ? 25.0 : pick == 1u ? 1.0 : pow2_times_mantissa(u2, -100, 5);
+      if (u0 & 16u) a = -a;
+      bad[0] += differ(div_ranged(a, d), a / d), ++seen[0];
+      const uint32_t kind = uint32_t(u0 >> 5) & 7u;
+      double z = kind == 0u ? 0.0 : kind < 4u ? __longlong_as_double((long long)((u3 & 0xFFFFFFFFFFFFFull) | 1ull))
+                                              : pow2_times_mantissa(u3, -1022, -101);
+      if (u0 & 256u) z = -z;
+      const double ref = z / d, raw = div_ranged(z, d);
+      bad[1] += differ(div_ranged_ok_finite(z) ? raw : ref, ref), ++seen[1];
+      bad[3] += differ(raw, ref), ++seen[3];
+    }
+    {
+      // log2(1e-8) = -26.575..., log2(0.2) = -2.3219...: the margins keep the rounded root inside [1e-8, 0.2]
+      const double r0 = (u0 & 512u) ? exp2(-26.57 + unit53(u4) * 24.24) : 1.0e-7 + unit53(u4) * 0.1999;
+      double y;
+      const double r = sqrt_rsq(r0 * r0, y);
+      if (r >= 1e-8 && r <= 0.2) {
+        double a = ((u0 >> 10) & 7u) == 0u ? 0.0 : pow2_times_mantissa(u5, -100, 20);
+        if ((u0 & 8192u) && a != 0.0) a = -a;
+        bad[2] += differ(div_seeded(a, r, y), a / r), ++seen[2];
+      }
+    }
+  }
+  for (int k = 0; k < 4; ++k) {
+    if (bad[k]) atomicAdd(&out[k], bad[k]);
+    atomicAdd(&out[4 + k], seen[k]);
+  }
 }
 
 

@@ -123,10 +123,15 @@ __global__ __launch_bounds__(BLOCK) void k_mc_field(McConsts<N> m, const uint32_
     // The hits' arithmetic is what the kernel spends its time on (a libm-style pow and four IEEE divides per hit: ~130
     // VALU).  The stock influence 0.5 (sph.hpp:183) makes pow(len, 0.5) a square root — correctly rounded, i.e. at least
     // as close to the reference's glm::pow as the device's pow is —, and the four quotients share ONE refined reciprocal
-    // with an exact-residual correction each (div_ranged: the IEEE quotient for operands in the normal range, which a
-    // hit's are unless it sits on the node itself: then, wave-wide, the compiler's divide).
+    // with an exact-residual correction each.  div_ranged is the IEEE quotient, bit for bit, where it was swept on the device
+    // (k_selftest_divides, pbf_selftest_divides): every fp32 divisor in (1e-18, 64] — sqrt(len), len^0.75 and len for every
+    // threshold h * scale up to 64 — against the sizes 25 and 1 and pseudo-random numerators of 2^-100 ... 2^6 in magnitude;
+    // in fp64 the same ranges, drawn pseudo-randomly.  It is NOT the IEEE quotient for a numerator of -0
+    // (+0 comes out) or a smaller one (a denormal, which l = p - a is when a particle and a node nearly share a coordinate
+    // close to 0; exactly 0 when they share it, as a particle clamped to a bound at 0 and the node plane there do): a wave
+    // with such a hit, or with one that sits on the node itself, takes the compiler's divide.
     const N denominator = inflHalf ? sqrt(len) : pow(len, m.particleInfluence);
-    if (__any(!(denominator > N(1e-18)))) {
+    if (__any(!(denominator > N(1e-18)) || !div_ranged_ok_finite(lx, ly, lz))) {
       v += (m.particleSize / denominator);
       nx = nx + (lx / denominator) * ninf, ny = ny + (ly / denominator) * ninf, nz = nz + (lz / denominator) * ninf;
     } else {

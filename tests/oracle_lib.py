@@ -120,6 +120,7 @@ def _bind(L):
     L.pbf_oracle_scene_dambreak.argtypes = [C.c_int, C.c_size_t] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)]
     L.pbf_oracle_motion_offset.argtypes = [C.c_int, C.c_uint64, C.c_void_p]
     L.pbf_oracle_set_pow4.argtypes = [C.c_void_p, C.c_int]
+    L.pbf_oracle_set_sqrt_influence.argtypes = [C.c_void_p, C.c_int]
     L.pbf_oracle_set_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pbf_oracle_surface.argtypes = [C.c_void_p, C.POINTER(OracleParams), C.POINTER(OracleMc), C.POINTER(C.c_uint64)]
     L.pbf_oracle_surface_from_lattice.argtypes = [C.c_void_p, C.POINTER(OracleParams), C.POINTER(OracleMc), C.c_void_p,
@@ -199,9 +200,11 @@ def make_params(h=0.1, dt=0.0083 * 1.5, scale=500.0, iteration=4, force=(0.0, 9.
 class Oracle:
     """Stateful CPU oracle (one per precision)."""
 
-    def __init__(self, fp64=False, device_pow=False, so_path=None):
-        """device_pow=True evaluates pow(q, 4) as (q*q)*(q*q) like the HIP kernels do — the ONE
+    def __init__(self, fp64=False, device_pow=False, so_path=None, device_sqrt=False):
+        """device_pow=True evaluates pow(q, 4) as (q*q)*(q*q) like the HIP kernels do — the first
         arithmetic substitution of the device path; default False = std::pow as in ompsph.hpp:240.
+        device_sqrt=True is the second: the marching-cubes field takes sqrt(len) where the reference takes
+        pow(len, 0.5), for influence 0.5 only (pbf_oracle_set_sqrt_influence); default False = std::pow.
         so_path: another build of the same source (build_native(): timing only, never a checker)."""
         self.fp64 = bool(fp64)
         self.dtype = np.float64 if fp64 else np.float32
@@ -209,6 +212,12 @@ class Oracle:
         self.h = C.c_void_p(self.L.pbf_oracle_create(int(self.fp64)))
         if device_pow:
             self.L.pbf_oracle_set_pow4(self.h, 1)
+        if device_sqrt:
+            self.L.pbf_oracle_set_sqrt_influence(self.h, 1)
+
+    def set_device_sqrt(self, on):
+        """Switch the second substitution (see __init__) on or off; it acts on the next surface() only."""
+        self.L.pbf_oracle_set_sqrt_influence(self.h, int(bool(on)))
 
     def __del__(self):
         if getattr(self, "h", None):

@@ -1,8 +1,9 @@
 """Marching-cubes surface (reference src/omp/ompsph.hpp:277-477).
 
 CPU: the oracle's restatement produces a closed, consistently oriented mesh.
-GPU: field kernel vs oracle within libm noise (pow), count + emit kernels bit-exact against the oracle's emit
-stage fed with the DEVICE lattice, triangle counts of the two full pipelines agree, fp32 and fp64.
+GPU: field kernel bit-exact against the oracle under its second documented substitution (sqrt(len) for pow(len, 0.5),
+oracle_lib.Oracle(device_sqrt=True)), count + emit kernels bit-exact against the oracle's emit stage fed with the DEVICE
+lattice, the meshes of the two full pipelines equal, fp32 and fp64.
 Parity vs the reference binary is unpinned (no goldens, OpenMP backend unbuildable), and the case tables are
 our own (tools/gen_mc_tables.py), so triangle counts need not equal the reference's."""
 import numpy as np
@@ -21,6 +22,20 @@ def mesh_is_closed_and_oriented(vs, quantum):
             directed[e] = directed.get(e, 0) + 1
     bad = sum(1 for (a, b), n in directed.items() if directed.get((b, a), 0) != n)
     return bad, len(directed)
+
+
+def bits_equal(g, w, what=""):
+    """Same NaN places (by class: payload and sign of a NaN are not compared), same bytes everywhere else."""
+    assert g.dtype == w.dtype and g.shape == w.shape, what
+    nan = np.isnan(w)
+    assert np.array_equal(np.isnan(g), nan), (what, "NaN in other places")
+    it = np.int64 if g.dtype == np.float64 else np.int32
+    a, b = g[~nan].view(it), w[~nan].view(it)
+    diff = a != b
+    if diff.any():
+        k = np.nonzero(diff)[0][0]
+        raise AssertionError(f"{what}: {int(diff.sum())} of {diff.size} values differ, first {g[~nan][k]!r} vs {w[~nan][k]!r} "
+                             f"(bit patterns {int(a[k])} vs {int(b[k])})")
 
 
 def test_oracle_surface_closed(oracle):
@@ -48,7 +63,7 @@ def test_surface_gpu_vs_oracle(pkg, oracle, fp64):
     sc = pkg.scene_cubes(8192, fp64)
     s = pkg.Solver(h=0.1, fp64=fp64)
     s.upload(**sc)
-    o = oracle.Oracle(fp64, device_pow=True)
+    o = oracle.Oracle(fp64, device_pow=True, device_sqrt=True)
     o.set_particles(**sc)
     p = pkg.default_params(4, 1000.0)
     q = oracle.make_params(mode=oracle.JACOBI, sort=oracle.SORT_STABLE, threads=4)
@@ -58,18 +73,20 @@ def test_surface_gpu_vs_oracle(pkg, oracle, fp64):
     g = s.surface(p, pkg.McParams())
     w = o.surface(q, oracle.OracleMc())
     assert np.array_equal(g["sample"], w["sample"])
-    # field: same arithmetic except libm pow(len, 0.5) -> relative noise only; NaN (0/0 colours) in the same places
-    tol = 2e-6 if not fp64 else 1e-13
-    np.testing.assert_allclose(g["pn"][:, 0], w["pn"][:, 0], rtol=tol, atol=tol * 100)
-    assert np.array_equal(np.isnan(g["c"]), np.isnan(w["c"]))
-    np.testing.assert_allclose(np.nan_to_num(g["pn"]), np.nan_to_num(w["pn"]), rtol=1e-4, atol=1e-4)
+    # field: the same arithmetic in the same order (the oracle takes sqrt(len) too) -> the same bits; NaN (0/0 colours,
+    # normals of nodes without a hit) in the same places
+    assert (w["pn"][:, 0] > 0).sum() > 10000
+    bits_equal(g["pn"], w["pn"], "pn")
+    bits_equal(g["c"], w["c"], "c")
     # count + emit: bit-exact against the oracle's emit stage on the device lattice
     e = o.surface(q, oracle.OracleMc(), lattice=(g["sample"], g["pn"], g["c"]))
     assert len(e["vs"]) == len(g["vs"]) > 3 * 4000
     for k in ("vs", "ns", "cs"):
         assert np.array_equal(g[k], e[k], equal_nan=True), k
-    # the two full pipelines agree on the triangle count (a node within 1e-6 of the isolevel may flip a case)
-    assert abs(len(g["vs"]) - len(w["vs"])) <= 0.005 * len(w["vs"]) + 30
+    # the two full pipelines give the same mesh, triangle count included
+    assert len(g["vs"]) == len(w["vs"])
+    for k in ("vs", "ns", "cs"):
+        assert np.array_equal(g[k], w[k], equal_nan=True), k
     bad, total = mesh_is_closed_and_oriented(g["vs"], 0.05)
     assert bad <= total * 0.002, (bad, total)
 

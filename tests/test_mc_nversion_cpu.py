@@ -47,12 +47,16 @@ def oracle_engine(s, fp64):
 lattice_of, exact_nodes = M.lattice_of, M.exact_nodes
 
 
-def held(name, fp64, mc, mutate=None):
+def held(name, fp64, mc, mutate=None, device_sqrt=False):
     s, o, q, st, cells = oracle_state(name, fp64)
     lat = lattice_of(s, mc, fp64)
     fluid = st["type"] != NM.OBSTACLE
     assert (cells[fluid] >= 0).all() and (cells[fluid] < lat.extent).all(), "a particle outside the grid"
-    w = o.surface(q, O.OracleMc(*mc))
+    o.set_device_sqrt(device_sqrt)
+    try:
+        w = o.surface(q, O.OracleMc(*mc))
+    finally:
+        o.set_device_sqrt(False)
     assert list(w["sample"]) == list(lat.sample)
     rep = NM.compare(w["pn"], w["c"], st["pos"], st["colour"], st["type"], cells, lat, mc[2], mc[3], o.dtype,
                      mutate=mutate, exact_nodes=exact_nodes(name, lat, mc))
@@ -96,6 +100,65 @@ def test_oracle_field_within_derived_bound(name, mc, fp64):
             blk = [lat.index(x, y, z) for x in range(*M.BLOCK[0]) for y in range(*M.BLOCK[1]) for z in range(*M.BLOCK[2])]
             rest = [j for j in blk if j != i]
             assert (rep["plain"][rest] | rep["empty"][rest]).all()
+
+
+HALF = [(n, mc, fp64) for n, mc, fp64 in CASES if mc[3] == 0.5]
+OTHER = [(n, mc, fp64) for n, mc, fp64 in CASES if mc[3] != 0.5]
+case_id = lambda c: f"{c[0]}-{c[1][0]}-{c[1][3]}-{'f64' if c[2] else 'f32'}"
+
+
+def surfaces(name, fp64, mc):
+    """-> the oracle's surface with std::pow and with the second substitution (sqrt for influence 0.5)."""
+    _, o, q, _, _ = oracle_state(name, fp64)
+    a = o.surface(q, O.OracleMc(*mc))
+    o.set_device_sqrt(True)
+    try:
+        b = o.surface(q, O.OracleMc(*mc))
+    finally:
+        o.set_device_sqrt(False)
+    return a, b
+
+
+@pytest.mark.parametrize("name,mc,fp64", HALF, ids=[case_id(c) for c in HALF])
+def test_oracle_sqrt_field_within_derived_bound(name, mc, fp64):
+    """The second documented substitution — sqrt(len) for pow(len, 0.5) — leaves the oracle's field inside the
+    unchanged bounds of tests/nversion_mc.py: every scene x influence-0.5 set x precision."""
+    assert len(HALF) == 2 * 2 * len(M.NAMES)
+    rep = held(name, fp64, mc, device_sqrt=True)
+    print("sqrt", name, mc, "f64" if fp64 else "f32", NM.summary(rep))
+    assert rep["pattern_bad"] == 0
+    assert rep["worst"] <= 1, NM.summary(rep)
+    assert rep["left_out"] <= 0.01 * rep["with_hits"], NM.summary(rep)
+    if fp64:
+        assert rep["rv_bar"] <= 1, "fp64 must also meet 1e-12 of the sum of |terms|"
+    assert rep["with_hits"] > 40 and len(rep["mesh"]["vs"]) >= 3 * 80
+
+
+@pytest.mark.parametrize("name,mc,fp64", OTHER, ids=[case_id(c) for c in OTHER])
+def test_sqrt_switch_changes_no_bit_off_influence_half(name, mc, fp64):
+    a, b = surfaces(name, fp64, mc)
+    for k in ("sample", "pn", "c", "vs", "ns", "cs"):
+        assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+
+
+@pytest.mark.parametrize("name,mc,fp64", HALF, ids=[case_id(c) for c in HALF])
+def test_sqrt_and_pow_fields_agree_within_the_old_tolerance(name, mc, fp64):
+    """How far the libm pow(len, 0.5) is from the correctly rounded root, seen through the field: printed (information),
+    and held to the tolerance tests/test_mc.py::test_surface_gpu_vs_oracle used while it compared across the two."""
+    a, b = surfaces(name, fp64, mc)
+    va, vb = a["pn"][:, 0], b["pn"][:, 0]
+    fin = np.isfinite(va) & np.isfinite(vb)
+    it = np.int64 if fp64 else np.int32
+    ulps = np.abs(va[fin].view(it).astype(np.int64) - vb[fin].view(it).astype(np.int64))   # (v >= 0: same sign)
+    whole = (a["pn"].view(it) != b["pn"].view(it)).any(axis=1) & ~np.isnan(a["pn"]).any(axis=1)
+    print(f"POW-VS-SQRT {name} {mc} {'f64' if fp64 else 'f32'}: v differs on {int((ulps > 0).sum())} of {int(fin.sum())} "
+          f"finite nodes, by at most {int(ulps.max())} ulp; pn differs on {int(whole.sum())} nodes; triangles "
+          f"{len(a['vs']) // 3} vs {len(b['vs']) // 3}")
+    assert np.array_equal(np.isfinite(va), np.isfinite(vb))
+    tol = 2e-6 if not fp64 else 1e-13
+    np.testing.assert_allclose(va, vb, rtol=tol, atol=tol * 100)
+    assert np.array_equal(np.isnan(a["c"]), np.isnan(b["c"]))
+    np.testing.assert_allclose(np.nan_to_num(a["pn"]), np.nan_to_num(b["pn"]), rtol=1e-4, atol=1e-4)
 
 
 def test_faces_scene_reaches_the_folds_and_the_nodes_outside_the_grid():
