@@ -90,7 +90,8 @@ int pbf_abi_version(void);
  * everything in Morton order), "nbr_chunks" (size of the pool of 120-slot overflow chunks of the two-tier neighbour lists;
  * 0 = sized from the particle count), "row_diffuse" (DEFAULT 1, with row_major: the colour diffusion walks the row-major copy, one
  * wave per segment of 64 x cells, runs staged by LDS-DMA, sums applied in place; 0 = per-cell sums on the Morton order, beside
- * the iterations), "diffuse_cap" (diagnostic: records in that kernel's LDS tile, 0 = default 640).  Every setting of these
+ * the iterations), "diffuse_cap" (diagnostic: records in that kernel's LDS tile, 0 = default 640), "sdf_cull" (pbf_sdf_from_mesh / pbf_set_collider_mesh only: 1 = a wave skips the
+ * triangles whose bounding sphere is out of its brick's reach; DEFAULT 1, 0 = every pair).  Every setting of these
  * is bit-identical.  Unknown names return PBF_ERR_INVALID. */
 int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value);
 
@@ -145,7 +146,8 @@ int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion);
  * gives the same bytes; "coop" 2 / 4 / 8 differs at rounding level as it does without a collider.
  * Limitations: there is no friction or restitution term — finalise derives the velocity from the projected position, as it
  * does for the box.  Whitewater's diffuse particles and the observers (surface, sampling, diagnostics, anisotropy) do not
- * see the collider.  One static collider per ctx; mesh-to-SDF conversion is the caller's.
+ * see the collider.  One static collider per ctx.  A triangle mesh becomes a lattice through pbf_sdf_from_mesh /
+ * pbf_set_collider_mesh below.
  *
  * pbf_collider_sample is the window onto that device function, for debugging an uploaded collider: its own synchronising
  * call, never part of a step.  For each point: round to N, q = point / scale in N, then exactly the function above with
@@ -164,6 +166,82 @@ typedef struct pbf_collider_sdf {
 int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf);   /* NULL clears and frees the lattice */
 int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const double *points /* 3n, world */,
                         void *phi /* N[n] */, void *moved /* N[3n], solver frame */, uint8_t *hit /* [n] */);
+
+/* Mesh colliders: the signed-distance lattice of a closed triangle mesh, built on the device (no reference counterpart).
+ * Opt-in; neither call is part of a step and both synchronise.  Without a call to them every launch of a step is unchanged.
+ *
+ * pbf_mesh_records is plain host code (csrc/pbf_mesh_records.hpp: no ctx, no GPU).  It checks the mesh, fills `info` and
+ * writes the records the kernel reads, 30 values of N (fp64 ? double : float) per triangle; records == NULL checks only.
+ * It accepts a closed, consistently oriented 2-manifold only: every index < n_vertices; no triangle of zero area in double;
+ * every undirected edge used by exactly two triangles, in opposite directions.  Anything else returns PBF_ERR_INVALID, the
+ * message in pbf_last_error(NULL), `records` untouched, and `info` (when not NULL) holding:
+ *   mesh, vertices or triangles NULL; a count zero or >= 2^31; a vertex that is not finite:   every field zero
+ *   an index >= n_vertices:                                                                   aabb_min / aabb_max, the rest zero
+ *   a degenerate triangle, a boundary, non-manifold or misoriented edge:                      every field
+ * n_edges counts the undirected edges; an edge used once is a boundary edge, more than twice a non-manifold edge, twice
+ * in the same direction a misoriented edge.  The edge table is built by sorting: O(nt log nt).  A negative volume is legal:
+ * the mesh is inside out, which gives the field of the same mesh with PBF_MESH_NEGATE.
+ * The record of triangle k (vertices a, b, c), formed in double in the order written and then rounded to N:
+ *   [0..8]   a, b, c
+ *   [9..11]  fu = n / sqrt(n . n),  n = (b - a) x (c - a)                     (u . v = (u_x v_x + u_y v_y) + u_z v_z)
+ *   [12..20] the edge pseudonormals of ab, bc, ca: fu_k + fu_k' of the two triangles on that edge
+ *   [21..29] the vertex pseudonormals of a, b, c: the sum, over the triangles around the vertex in ascending triangle index
+ *            and starting from 0, of angle * fu, angle = atan2(|e1 x e2|, e1 . e2) of that triangle's two edges leaving the vertex
+ * Pseudonormals are not normalised.  They are the angle-weighted pseudonormals of Baerentzen & Aanaes 2005 ("Signed distance
+ * computation using the angle weighted pseudonormal", IEEE TVCG 11(3)): the choice for which the sign below is right at
+ * edges and vertices too.
+ *
+ * The field.  Everything is in N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it; divides and
+ * the square root are IEEE.  Node (i, j, k) is at p_a = N(origin_a) + N(i_a) * N(spacing), as pbf_sample_lattice forms its
+ * points.  For a node p and a triangle the closest point q follows the seven regions of Ericson, Real-Time Collision
+ * Detection 5.1.5:
+ *   ab = b - a   ac = c - a   ap = p - a   bp = p - b   cp = p - c   cb = c - b
+ *   d1 = ab . ap   d2 = ac . ap   d3 = ab . bp   d4 = ac . bp   d5 = ab . cp   d6 = ac . cp
+ *   vc = d1 d4 - d3 d2     vb = d5 d2 - d1 d6     va = d3 d6 - d5 d4     e = d4 - d3     f = d5 - d6
+ *   the first region that holds, in this order, gives q and the normal n of that feature:
+ *     vertex a   d1 <= 0 && d2 <= 0                q = a                                   n = [21..23]
+ *     vertex b   d3 >= 0 && d4 <= d3               q = b                                   n = [24..26]
+ *     edge ab    vc <= 0 && d1 >= 0 && d3 <= 0     t = d1 / (d1 - d3)     q = a + t ab     n = [12..14]
+ *     vertex c   d6 >= 0 && d5 <= d6               q = c                                   n = [27..29]
+ *     edge ca    vb <= 0 && d2 >= 0 && d6 <= 0     t = d2 / (d2 - d6)     q = a + t ac     n = [18..20]
+ *     edge bc    va <= 0 && e >= 0 && f >= 0       t = e / (e + f)        q = b + t cb     n = [15..17]
+ *     face       otherwise    den = (va + vb) + vc   v = vb / den   w = vc / den   q = (a + v ab) + w ac   n = [9..11]
+ *   r = p - q     d2 = r . r     s = r . n     neg = s < 0
+ * Every candidate is computed and the result selected: no lane branches, and the 0 / 0 of a region that did not hold is
+ * dropped by the select.  The fold runs over the triangles in ascending index from best = +inf, neg = false; a triangle
+ * replaces {best, neg} only when d2 < best, strictly, so the lowest index among ties wins and a NaN never replaces.
+ *   phi = (neg != negate) ? -sqrt(best) : sqrt(best)            negate = flags & PBF_MESH_NEGATE
+ * A node on the mesh has best == 0 and s == 0, so neg is false: phi is +0 without PBF_MESH_NEGATE and -0 with it (zero
+ * either way: such a node is on the solid's surface).
+ *
+ * pbf_sdf_from_mesh fills the lattice of `lattice` (dims, origin, spacing; its phi and margin are ignored) and copies it
+ * to the host array phi, N[dims product] in pbf_set_collider's order.  pbf_set_collider_mesh computes the same lattice and
+ * installs it as the ctx's collider with lattice->margin, without leaving the device: it ends in pbf_set_collider's
+ * install path (a captured step's key changes, captured graphs are dropped), and every later step and pbf_collider_sample
+ * gives the bytes they give after pbf_set_collider with the array pbf_sdf_from_mesh returned.  The lattice arguments are
+ * checked by the code that checks pbf_set_collider's (margin by the installing call only); a refused mesh is
+ * PBF_ERR_INVALID with pbf_mesh_records' message in pbf_last_error(ctx); so are lattice == NULL, phi == NULL and unknown
+ * flag bits.  The slab refusals are pbf_set_collider's (PBF_ERR_STATE).  A refusal leaves the ctx, its collider and phi
+ * untouched.  stats (may be NULL): pairs_total = nodes x triangles, pairs_tested = the pairs the kernel evaluated — equal
+ * with "sdf_cull" 0, fewer with 1 (the default); the field's bytes are the same either way.  The work is split over launches of at most
+ * 2^33 lane-triangle pairs so that no single kernel runs for seconds. */
+typedef struct pbf_mesh {
+  uint64_t n_vertices, n_triangles;
+  const double *vertices;      /* 3 per vertex, world units */
+  const uint32_t *triangles;   /* 3 vertex indices per triangle, counter-clockwise seen from outside */
+} pbf_mesh;
+typedef struct pbf_mesh_info { /* filled on success AND on a mesh that is refused (see above) */
+  uint64_t n_edges, boundary_edges, nonmanifold_edges, misoriented_edges, degenerate_triangles;
+  double volume;               /* signed: sum a.(b x c) / 6 over the triangles in ascending index; negative = inside out */
+  double aabb_min[3], aabb_max[3];
+} pbf_mesh_info;
+typedef struct pbf_mesh_sdf_stats { uint64_t pairs_total /* nodes x triangles */, pairs_tested; } pbf_mesh_sdf_stats;
+enum { PBF_MESH_NEGATE = 1u << 0 };  /* solid OUTSIDE the mesh: a cavity the fluid lives in */
+int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records /* N[30 n_triangles] */, pbf_mesh_info *info);
+int pbf_sdf_from_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
+                      void *phi /* N[dims product] */, pbf_mesh_sdf_stats *stats /* may be NULL */);
+int pbf_set_collider_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
+                          pbf_mesh_sdf_stats *stats /* may be NULL */);
 
 /* ---- particle state (replaces the std::vector<Particle>& in/out argument, src/sph.hpp:124) */
 int pbf_upload(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type, const void *mass, const void *pos,

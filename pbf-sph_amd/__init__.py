@@ -22,6 +22,10 @@ from .capi import (  # noqa: F401
     FLAG_NO_LDS,
     FLAG_STAGE_TIMING,
     LIB_PATH,
+    MESH_NEGATE,
+    Mesh,
+    MeshInfo,
+    MeshSdfStats,
     McParams,
     Params,
     PbfError,
@@ -39,6 +43,8 @@ from .capi import (  # noqa: F401
     build,
     default_params,
     lib,
+    mesh_records,
+    mesh_struct,
     scene_cubes,
     scene_dambreak,
     sdf_box,

@@ -23,6 +23,8 @@ BUF_WHITEWATER = 7
 WW_SPRAY, WW_FOAM, WW_BUBBLE = 0, 1, 2
 DIAG_DENSITY = 1 << 0
 SAMPLE_VELOCITY, SAMPLE_COLOUR = 1 << 0, 1 << 1
+MESH_NEGATE = 1 << 0
+MESH_RECORD = 30
 
 
 class PbfError(RuntimeError):
@@ -160,6 +162,28 @@ class ColliderSdf(C.Structure):
                 ("phi", C.c_void_p)]
 
 
+class Mesh(C.Structure):
+    """pbf_mesh (include/pbf_hip.h)"""
+    _fields_ = [("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
+
+
+class MeshInfo(C.Structure):
+    """pbf_mesh_info (include/pbf_hip.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges",
+                                          "degenerate_triangles")] + \
+               [("volume", C.c_double), ("aabb_min", C.c_double * 3), ("aabb_max", C.c_double * 3)]
+
+    def as_dict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_[:5]}
+        d.update(volume=float(self.volume), aabb_min=tuple(self.aabb_min), aabb_max=tuple(self.aabb_max))
+        return d
+
+
+class MeshSdfStats(C.Structure):
+    """pbf_mesh_sdf_stats (include/pbf_hip.h)"""
+    _fields_ = [("pairs_total", C.c_uint64), ("pairs_tested", C.c_uint64)]
+
+
 class AosLayout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("stride", "off_id", "off_type", "off_mass", "off_pos", "off_vel",
                                           "off_colour")]
@@ -182,6 +206,9 @@ _SIGS = {
     "pbf_set_surface_tension": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "pbf_set_collider": (C.c_int, [C.c_void_p, C.POINTER(ColliderSdf)]),
     "pbf_collider_sample": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbf_mesh_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
+    "pbf_sdf_from_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.c_void_p, C.POINTER(MeshSdfStats)]),
+    "pbf_set_collider_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
     "pbf_create": (C.c_int, [C.POINTER(Desc), C.POINTER(C.c_void_p)]),
     "pbf_destroy": (None, [C.c_void_p]),
     "pbf_last_error": (C.c_char_p, [C.c_void_p]),
@@ -385,6 +412,35 @@ def sdf_lattice(fn, origin, spacing, dims):
     return np.ascontiguousarray(np.asarray(fn(x), np.float64).reshape([int(v) for v in dims]))
 
 
+def mesh_struct(vertices, triangles):
+    """(vertices (nv, 3) float64, triangles (nt, 3) uint32) -> (Mesh, the arrays it points into: keep them alive)"""
+    v = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    return Mesh(len(v), len(t), v.ctypes.data, t.ctypes.data), (v, t)
+
+
+def mesh_records(vertices, triangles, fp64=False):
+    """pbf_mesh_records (host only, no GPU): the kernel's per-triangle records -> (records (nt, 30) of N, info dict).  A mesh
+    that is refused raises PbfError; its .info holds the counts."""
+    m, keep = mesh_struct(vertices, triangles)
+    rec = np.zeros((len(keep[1]), MESH_RECORD), np.float64 if fp64 else np.float32)
+    info = MeshInfo()
+    rc = lib().pbf_mesh_records(C.byref(m), int(bool(fp64)), _vp(rec), C.byref(info))
+    if rc < 0:
+        e = PbfError(f"pbf_mesh_records failed ({rc}): {lib().pbf_last_error(None).decode()}")
+        e.info = info.as_dict()
+        raise e
+    return rec, info.as_dict()
+
+
+def _lattice_struct(origin, spacing, dims, margin=0.0):
+    sdf = ColliderSdf()
+    sdf.dims[:] = [int(v) for v in dims]
+    sdf.origin[:] = [float(v) for v in origin]
+    sdf.spacing, sdf.margin, sdf.phi = float(spacing), float(margin), None
+    return sdf
+
+
 class Solver:
     """Mirror of sph::hip_impl::Solver<T,N> (host/hipsph.hpp) over the C ABI: ctor takes h like
     omp_impl::Solver(N h) (ompsph.hpp:83); state is device-resident between steps."""
@@ -474,6 +530,28 @@ class Solver:
         sdf.spacing, sdf.margin, sdf.phi = float(spacing), float(margin), a.ctypes.data
         self._chk(self.L.pbf_set_collider(self.ctx, C.byref(sdf)), "pbf_set_collider")
         return self
+
+    def sdf_from_mesh(self, vertices, triangles, origin, spacing, dims, negate=False):
+        """pbf_sdf_from_mesh: the signed distance to a closed triangle mesh (counter-clockwise from outside) on the lattice
+        origin + (i, j, k) * spacing, computed on the device -> (phi of shape dims, negative inside the mesh; negate: outside),
+        dict(pairs_total, pairs_tested))"""
+        m, keep = mesh_struct(vertices, triangles)
+        sdf = _lattice_struct(origin, spacing, dims)
+        phi = np.zeros([int(v) for v in dims], self.dtype)
+        st = MeshSdfStats()
+        self._chk(self.L.pbf_sdf_from_mesh(self.ctx, C.byref(m), C.byref(sdf), MESH_NEGATE if negate else 0, _vp(phi), C.byref(st)),
+                  "pbf_sdf_from_mesh")
+        return phi, dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
+
+    def set_collider_mesh(self, vertices, triangles, origin, spacing, dims, margin=0.0, negate=False):
+        """pbf_set_collider_mesh: the lattice of sdf_from_mesh computed and installed as the collider without leaving the
+        device -> dict(pairs_total, pairs_tested)"""
+        m, keep = mesh_struct(vertices, triangles)
+        sdf = _lattice_struct(origin, spacing, dims, margin)
+        st = MeshSdfStats()
+        self._chk(self.L.pbf_set_collider_mesh(self.ctx, C.byref(m), C.byref(sdf), MESH_NEGATE if negate else 0, C.byref(st)),
+                  "pbf_set_collider_mesh")
+        return dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
 
     def collider_sample(self, p, points):
         """The collider's device function at world points (pbf_collider_sample) -> dict(phi (n,) interpolated distance, +inf

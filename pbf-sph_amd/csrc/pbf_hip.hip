@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <initializer_list>
+#include <limits>
 #include <map>
 #include <string>
 #include <utility>
@@ -25,6 +26,7 @@
 #include "pbf_whitewater.hpp"
 #include "pbf_anisotropy.hpp"
 #include "pbf_aniso_field.hpp"
+#include "pbf_mesh_sdf.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 
@@ -220,6 +222,8 @@ struct pbf_ctx {
   uint32_t colliderDims[3] = {0, 0, 0};
   double colliderOrigin[3] = {0, 0, 0}, colliderSpacing = 0, colliderMargin = 0;
   uint64_t colliderGen = 0;
+  // "sdf_cull": pbf_sdf_from_mesh / pbf_set_collider_mesh skip the triangles out of a brick's reach (same bytes, 5 - 7 x faster)
+  bool sdfCull = true;
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
   // the compaction's per-tile counts and total, the pinned words of the drained count's read-back {total, sequence number}
   std::vector<pbf_source> sources;
@@ -1467,6 +1471,7 @@ int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value) {
     if (value < 0 || value > 4096) return fail(ctx, PBF_ERR_INVALID, "diffuse_cap: 0 (default) .. 4096 records");
     ctx->diffuseCap = uint32_t(value);
   }
+  else if (n == "sdf_cull") ctx->sdfCull = value != 0;
   else if (n == "nbr_chunks") {  // diagnostic: size of the lists' second tier (before the first upload; 0 = capacity / 8 + 1024)
     if (ctx->cap) return fail(ctx, PBF_ERR_STATE, "nbr_chunks must be set before the first upload");
     ctx->nbrChunksOpt = uint32_t(value);
@@ -2360,6 +2365,87 @@ template <typename N> int set_collider_impl(pbf_ctx *ctx, const pbf_collider_sdf
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (phi is the caller's)
   return PBF_OK;
 }
+// what pbf_set_collider, pbf_sdf_from_mesh and pbf_set_collider_mesh refuse about a lattice, in one place and one order;
+// margin and phi are the installing / uploading call's business.  *nodes receives the dims product.
+int collider_lattice_check(pbf_ctx *ctx, const char *who, const pbf_collider_sdf *sdf, bool margin, bool phi, size_t *nodes) {
+  const std::string w = std::string(who) + ": ";
+  size_t n = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (sdf->dims[a] < 2) return fail(ctx, PBF_ERR_INVALID, w + "every dim must be >= 2");
+    if ((n *= sdf->dims[a]) >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, w + "2^31 nodes or more");
+    if (!std::isfinite(sdf->origin[a])) return fail(ctx, PBF_ERR_INVALID, w + "origin must be finite");
+  }
+  if (!std::isfinite(sdf->spacing) || !(sdf->spacing > 0)) return fail(ctx, PBF_ERR_INVALID, w + "spacing must be finite and > 0");
+  if (margin && (!std::isfinite(sdf->margin) || sdf->margin < 0)) return fail(ctx, PBF_ERR_INVALID, w + "margin must be finite and >= 0");
+  if (phi && !sdf->phi) return fail(ctx, PBF_ERR_INVALID, w + "phi == NULL");
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  *nodes = n;
+  return PBF_OK;
+}
+
+// the one install path: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's collider
+int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
+  // the steps captured so far hold the old lattice's address and can never be asked for again (colliderGen): drop them
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (auto &g : ctx->graphs)
+    if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
+  ctx->graphs.clear();
+  ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
+  ctx->colliderGen++;
+  for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
+  ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
+  return PBF_OK;
+}
+
+// pbf_sdf_from_mesh / pbf_set_collider_mesh: the records on the host, then the fold on the device (csrc/pbf_mesh_sdf.hpp,
+// launch_fold: bounded launches over triangle ranges) into `fresh` (N[nodes], an allocation of its own like pbf_set_collider's).
+template <typename N>
+int mesh_sdf_impl(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lat, uint32_t flags, size_t nodes, DevBuf &fresh,
+                  pbf_mesh_sdf_stats *stats) {
+  const size_t nt = size_t(mesh->n_triangles);
+  std::vector<N> rec(size_t(meshsdf::RECORD) * nt), bnd(4 * nt);
+  const char *why = nullptr;
+  if (meshsdf::build_records(mesh, sizeof(N) == 8, rec.data(), nullptr, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  meshsdf::SdfLattice<N> L;
+  N slack;
+  meshsdf::prepare<N>(lat->dims, lat->origin, lat->spacing, rec.data(), nt, &L, bnd.data(), &slack);
+  const size_t bricks = meshsdf::brick_count(L);  // (< 2^31: at most the node count)
+
+  DevBuf dRec, dBnd, dSign, dTested;
+  HIPCHK(ctx, hipMalloc(&fresh.p, nodes * sizeof(N)));
+  fresh.cap = nodes * sizeof(N);
+  HIPCHK(ctx, hipMalloc(&dRec.p, rec.size() * sizeof(N)));
+  HIPCHK(ctx, hipMalloc(&dBnd.p, bnd.size() * sizeof(N)));
+  HIPCHK(ctx, hipMalloc(&dSign.p, nodes));
+  HIPCHK(ctx, hipMalloc(&dTested.p, bricks * sizeof(uint64_t)));
+  ctx->allocEpoch++;
+  HIPCHK(ctx, hipMemcpyAsync(dRec.p, rec.data(), rec.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(dBnd.p, bnd.data(), bnd.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, meshsdf::launch_fold<N>(ctx->stream, L, dRec.as<const N>(), dBnd.as<const N>(), nt, ctx->sdfCull, (flags & PBF_MESH_NEGATE) != 0,
+                                      slack, fresh.as<N>(), dSign.as<uint8_t>(), dTested.as<unsigned long long>()));
+  std::vector<uint64_t> slots(stats ? bricks : 0);
+  if (stats) HIPCHK(ctx, hipMemcpyAsync(slots.data(), dTested.p, bricks * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (rec, bnd and the scratch buffers are locals)
+  if (stats) {
+    stats->pairs_total = uint64_t(nodes) * nt, stats->pairs_tested = 0;
+    for (uint64_t v : slots) stats->pairs_tested += v;
+  }
+  return PBF_OK;
+}
+// the checks the two entry points share, then the fold
+int mesh_sdf_run(pbf_ctx *ctx, const char *who, const pbf_mesh *mesh, const pbf_collider_sdf *lat, uint32_t flags, bool install,
+                 DevBuf &fresh, size_t *nodes, pbf_mesh_sdf_stats *stats) {
+  if (!lat) return fail(ctx, PBF_ERR_INVALID, std::string(who) + ": lattice == NULL");
+  if (flags & ~uint32_t(PBF_MESH_NEGATE)) return fail(ctx, PBF_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  if (int rc = collider_lattice_check(ctx, who, lat, install, false, nodes)) return rc;
+  {  // the mesh, before anything is allocated (mesh_sdf_impl builds the records of the ctx's type)
+    const char *why = nullptr;
+    if (meshsdf::build_records(mesh, 0, nullptr, nullptr, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->fp64 ? mesh_sdf_impl<double>(ctx, mesh, lat, flags, *nodes, fresh, stats)
+                   : mesh_sdf_impl<float>(ctx, mesh, lat, flags, *nodes, fresh, stats);
+}
 template <typename N>
 int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, N *phi, N *moved, uint8_t *hit) {
   std::vector<N> pts(3 * n);
@@ -2389,30 +2475,45 @@ extern "C" {
 int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
   if (!ctx) return PBF_ERR_INVALID;
   size_t nodes = 1;
-  if (sdf) {
-    for (int a = 0; a < 3; ++a) {
-      if (sdf->dims[a] < 2) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: every dim must be >= 2");
-      if ((nodes *= sdf->dims[a]) >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: 2^31 nodes or more");
-      if (!std::isfinite(sdf->origin[a])) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: origin must be finite");
-    }
-    if (!std::isfinite(sdf->spacing) || !(sdf->spacing > 0)) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: spacing must be finite and > 0");
-    if (!std::isfinite(sdf->margin) || sdf->margin < 0) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: margin must be finite and >= 0");
-    if (!sdf->phi) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: phi == NULL");
-    if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
-  }
+  if (sdf)
+    if (int rc = collider_lattice_check(ctx, "pbf_set_collider", sdf, true, true, &nodes)) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   DevBuf fresh;
   if (sdf)
     if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, sdf, nodes, fresh) : set_collider_impl<float>(ctx, sdf, nodes, fresh)) return rc;
-  // the steps captured so far hold the old lattice's address and can never be asked for again (colliderGen): drop them
+  return collider_install(ctx, sdf, fresh);
+}
+
+int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records, pbf_mesh_info *info) {
+  const char *why = nullptr;
+  const int rc = meshsdf::build_records(mesh, fp64, records, info, &why);
+  if (rc != PBF_OK) g_create_error = why;  // (no ctx: read with pbf_last_error(NULL))
+  return rc;
+}
+
+int pbf_sdf_from_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags, void *phi,
+                      pbf_mesh_sdf_stats *stats) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!phi) return fail(ctx, PBF_ERR_INVALID, "pbf_sdf_from_mesh: phi == NULL");
+  DevBuf fresh;
+  size_t nodes = 0;
+  pbf_mesh_sdf_stats st{};
+  if (int rc = mesh_sdf_run(ctx, "pbf_sdf_from_mesh", mesh, lattice, flags, false, fresh, &nodes, &st)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(phi, fresh.p, nodes * (ctx->fp64 ? sizeof(double) : sizeof(float)), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  for (auto &g : ctx->graphs)
-    if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-  ctx->graphs.clear();
-  ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
-  ctx->colliderGen++;
-  for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
-  ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
+  if (stats) *stats = st;
+  return PBF_OK;
+}
+
+int pbf_set_collider_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
+                          pbf_mesh_sdf_stats *stats) {
+  if (!ctx) return PBF_ERR_INVALID;
+  DevBuf fresh;
+  size_t nodes = 0;
+  pbf_mesh_sdf_stats st{};
+  if (int rc = mesh_sdf_run(ctx, "pbf_set_collider_mesh", mesh, lattice, flags, true, fresh, &nodes, &st)) return rc;
+  if (int rc = collider_install(ctx, lattice, fresh)) return rc;
+  if (stats) *stats = st;
   return PBF_OK;
 }
 

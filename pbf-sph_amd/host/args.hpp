@@ -36,7 +36,10 @@ struct Args {
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
   // --collider=sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]] with --resident: opt-in static SDF collider
+  // --collider=mesh:FILE.obj[,margin[,spacing[,negate]]]: the same collider, its lattice built on the device from a closed mesh
   std::string colliderShape;              // "" = off
+  std::string colliderMesh;               // shape "mesh": the OBJ file
+  bool colliderNegate = false;            // shape "mesh": the solid is outside the mesh
   double colliderCfg[4] = {0, 0, 0, 0};
   double colliderMargin = 13.5;           // half the rest spacing of 27 world units
   double colliderSpacing = 0;             // 0 = h * scale / 2
@@ -103,6 +106,9 @@ struct Args {
           "                                        plane:nx,ny,nz,d (solid where n.x < d, n normalised). The fluid stays\n"
           "                                        `margin` world units off the solid (default 13.5); lattice spacing in\n"
           "                                        world units (default h * scale / 2). Single device only\n"
+          "      --collider=mesh:[FILE.obj[,margin[,spacing[,negate]]]]  The same, from a closed triangle mesh (v and triangular\n"
+          "                                        f lines, counter-clockwise from outside): the lattice is computed on the\n"
+          "                                        device. negate = 1: the solid is OUTSIDE the mesh (a cavity)\n"
           "      --whitewater=[k_ta,k_wc[,capacity]]  With --resident: spray, foam and air bubbles after Ihmsen et al. 2012,\n"
           "                                        one whitewater step after every frame at these rates; the tau ranges are\n"
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
@@ -222,6 +228,18 @@ struct Args {
         else if (value(i, a, "", "--collider", v)) {
           const size_t colon = v.find(':');
           const std::string shape = v.substr(0, colon);
+          if (colon != std::string::npos && shape == "mesh") {
+            const size_t comma = v.find(',', colon);
+            colliderMesh = v.substr(colon + 1, comma == std::string::npos ? std::string::npos : comma - colon - 1);
+            const auto f = comma == std::string::npos ? std::vector<double>{} : numbers(v.substr(comma + 1));
+            if (colliderMesh.empty() || f.size() > 3) throw std::runtime_error("--collider: expected mesh:FILE.obj[,margin[,spacing[,negate]]]");
+            colliderShape = shape;
+            if (f.size() > 0) colliderMargin = f[0];
+            if (f.size() > 1) colliderSpacing = f[1];
+            if (f.size() > 2) colliderNegate = f[2] != 0;
+            if (!(colliderMargin >= 0) || !(colliderSpacing >= 0)) throw std::runtime_error("--collider: margin and spacing must be >= 0");
+            continue;
+          }
           if (colon == std::string::npos || (shape != "sphere" && shape != "bowl" && shape != "plane"))
             throw std::runtime_error("--collider: expected sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]]");
           const auto f = numbers(v.substr(colon + 1));

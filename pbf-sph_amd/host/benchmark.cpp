@@ -22,6 +22,7 @@
 
 #include "args.hpp"
 #include "hipsph.hpp"
+#include "obj_mesh.hpp"
 
 using duration_millis = std::chrono::duration<double, std::milli>;
 using hrc = std::chrono::high_resolution_clock;
@@ -181,6 +182,23 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       origin[size_t(a)] = lo[a] - spacing;
       dims[size_t(a)] = uint32_t(std::ceil((hi[a] - lo[a]) / spacing)) + 3u;
     }
+    if (args.colliderShape == "mesh") {
+      const objmesh::Mesh mesh = objmesh::read(args.colliderMesh);
+      pbf_mesh view{mesh.vertices.size() / 3, mesh.triangles.size() / 3, mesh.vertices.data(), mesh.triangles.data()};
+      pbf_mesh_info info{};
+      if (pbf_mesh_records(&view, 0, nullptr, &info) != PBF_OK) {
+        std::cerr << args.colliderMesh << ": " << pbf_last_error(nullptr) << " (edges " << info.n_edges << ", boundary " << info.boundary_edges
+                  << ", non-manifold " << info.nonmanifold_edges << ", misoriented " << info.misoriented_edges << ", degenerate triangles "
+                  << info.degenerate_triangles << ")" << std::endl;
+        return 1;
+      }
+      pbf_mesh_sdf_stats stats{};
+      solver.setColliderMesh(mesh.vertices, mesh.triangles, dims, origin, spacing, args.colliderMargin, args.colliderNegate, &stats);
+      std::cout << "Collider             : mesh " << args.colliderMesh << (args.colliderNegate ? " (negated)" : "") << ", " << view.n_triangles
+                << " triangles, volume " << info.volume << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2] << ", spacing "
+                << spacing << ", margin " << args.colliderMargin << ", pairs tested " << stats.pairs_tested << " / " << stats.pairs_total
+                << std::endl;
+    } else {
     const double *g = args.colliderCfg;
     const double nl = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
     std::vector<N> phi(size_t(dims[0]) * dims[1] * dims[2]);
@@ -196,6 +214,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     solver.setCollider(dims, origin, spacing, args.colliderMargin, phi.data());
     std::cout << "Collider             : " << args.colliderShape << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2]
               << ", spacing " << spacing << ", margin " << args.colliderMargin << std::endl;
+    }
   }
   if (args.indexedMesh) solver.indexedMesh(true);
   sph::hip_impl::IndexedMesh<N, sph::vec> indexed;  // --indexed-mesh --resident: the last frame's mesh

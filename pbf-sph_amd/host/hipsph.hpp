@@ -432,6 +432,23 @@ public:
     check(pbf_set_collider(ctx_, &sdf), "pbf_set_collider");
     return *this;
   }
+  // The same collider from a closed triangle mesh (pbf_set_collider_mesh; no reference counterpart): vertices = 3 doubles per
+  // vertex in world units, triangles = 3 indices per triangle, counter-clockwise seen from outside.  The lattice of `dims`
+  // nodes at origin + (i, j, k) * spacing is filled with the signed distance on the device (negative inside the mesh; negate:
+  // the solid is OUTSIDE, a cavity the fluid lives in) and installed.  A single-device feature, like setCollider.
+  Solver &setColliderMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
+                          const std::array<double, 3> &origin, double spacing, double margin, bool negate = false,
+                          pbf_mesh_sdf_stats *stats = nullptr) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_mesh mesh{};
+    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
+    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
+    pbf_collider_sdf sdf{};
+    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
+    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = nullptr;
+    check(pbf_set_collider_mesh(ctx_, &mesh, &sdf, negate ? uint32_t(PBF_MESH_NEGATE) : 0u, stats), "pbf_set_collider_mesh");
+    return *this;
+  }
   Solver &clearCollider() {
     if (!multi()) check(pbf_set_collider(ctx_, nullptr), "pbf_set_collider");
     return *this;
