@@ -107,7 +107,8 @@ struct SceneRecord {  // k_drain_scan's host[0] and host[1]
   uint32_t kept, seq;
 };
 
-constexpr uint32_t kTickets = 254;  // (kTickets + 2 words = 1024 bytes: ONE fill kernel per step; 1028 bytes took two)
+constexpr uint32_t kTickets = 252;  // (kTickets + 4 control words = 256: one pass of k_scan_sums' workgroup zeroes them all)
+constexpr uint32_t kCtlWords = kTickets + 4;
 constexpr int kBrickZ = 4;
 
 enum Stage { ST_PREDICT = 0, ST_SORT, ST_DIFFUSE, ST_LAMBDA, ST_DELTA, ST_FINALISE, ST_BUILD, ST_COUNT };
@@ -166,6 +167,7 @@ struct pbf_ctx {
   DevBuf pos4[2], vel4[2], col4[2], id[2], type[2], key[2];
   DevBuf pstar[3];       // [0],[1]: sort ping-pong partner of set 0/1 ; [2]: Jacobi partner
   DevBuf count, table, blockSums, permTmp, wells, staging;
+  DevBuf cellSlot;  // per particle: its slot among its bucket's members, handed out by the histogram's atomics (k_scatter_slots)
   // slab decomposition (pbf_slab_*): bookkeeping of what was sent / received this step
   DevBuf slotOf, selCounts, selTotals, ghostSrcL, ghostSrcR, colHist;
   bool slabActive = false, realObstacles = false;
@@ -205,7 +207,7 @@ struct pbf_ctx {
   DevBuf nbrList, nbrCount;  // neighbour lists handed from the lambda launch to the delta launch: NBR_ROWS slots per particle
   // option "row_major": the iterations' working set also laid out cell-row-major (csrc/pbf_kernels.hpp RowArrays)
   int rowMajor = 1;           // default ON since round 3: -3 % per step at 1 M, -10 % at 4 M (profiles/r03_matrix.txt)
-  DevBuf rowPstar[2], rowMass, rowQpos, rowXYZ, rowType, rowSlotOf, linCount, linTable, linSums;
+  DevBuf rowPstar[2], rowMass, rowQpos, rowXYZ, rowType, rowSlotOf, linTable, linSums;
   DevBuf rowCol, rowMortonOf, rowSegs;  // k_diffuse_rows: the colours in row order, slot -> Morton index, non-empty segments
   uint32_t rowSegShift = 0;
   uint32_t diffuseCap = 0;   // option "diffuse_cap" (diagnostic): records in k_diffuse_rows' tile, 0 = default
@@ -313,7 +315,8 @@ struct pbf_ctx {
                              // (bit-identical; measured 2 % SLOWER at 1 M — the colour loads stall the filter loop — so off)
   // pbf_steps' request to the step it starts: the NEXT step's predict rides on this step's finalise (k_finalise_predict)
   bool fuseNextPredict = false;
-  DevBuf bricks, brickCtl;  // non-empty brick list; brickCtl = {nActive, ticket[kTickets], nBigCells}
+  // non-empty brick list; brickCtl = {nActive, ticket[kTickets], nBigCells, row tail allocator, number of row segments}
+  DevBuf bricks, brickCtl;
   DevBuf bigCells;          // cells with more than BIG_CELL members this step (k_sort_big_cells)
   uint32_t gatherSeq = 0;   // which ticket word the next persistent gather launch uses
   int numCUs = 256;
@@ -389,6 +392,7 @@ int ensure_particles(pbf_ctx *ctx, size_t n) {
   for (int s = 0; s < 3; ++s)
     if (int rc = ensure(ctx, ctx->pstar[s], n * v)) return rc;
   if (int rc = ensure(ctx, ctx->permTmp, n * 4)) return rc;
+  if (int rc = ensure(ctx, ctx->cellSlot, n * 4)) return rc;
   if (int rc = ensure(ctx, ctx->slotOf, n * 4)) return rc;
   if (int rc = ensure(ctx, ctx->qpos, (n + QPOS_PAD) * 8)) return rc;
   if (int rc = ensure(ctx, ctx->nbrCount, n * 4)) return rc;
@@ -485,7 +489,8 @@ int drop_histogram(pbf_ctx *ctx) {
 int ensure_table(pbf_ctx *ctx, uint32_t tableN) {
   const size_t entries = size_t(tableN) + 2;  // buckets 0..tableN (+1 overflow) and the closing total
   if (ctx->tableCap >= entries) return PBF_OK;
-  // count must start (and, by the atomicSub in k_scatter_slots, always returns to) all-zero
+  // count must start (and always returns to) all-zero: k_scatter_slots stores 0 over every bucket the producers raised (the
+  // member that holds slot 0 does), and a histogram that never reaches a scatter is cleared by drop_histogram
   if (ctx->count.p) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, ctx->count.reset());
@@ -495,7 +500,7 @@ int ensure_table(pbf_ctx *ctx, uint32_t tableN) {
   const size_t nb = (entries + SCAN_TILE - 1) / SCAN_TILE + 1;
   if (int rc = ensure(ctx, ctx->blockSums, nb * 4)) return rc;
   if (int rc = ensure(ctx, ctx->bricks, (entries / Brick<kBrickZ>::HOME + 2) * 4)) return rc;
-  if (int rc = ensure(ctx, ctx->brickCtl, (kTickets + 2) * 4)) return rc;
+  if (int rc = ensure(ctx, ctx->brickCtl, kCtlWords * 4)) return rc;
   ctx->tableCap = ctx->count.cap / 4 - SCAN_TILE;
   return PBF_OK;
 }
@@ -617,7 +622,7 @@ template <typename N> int stage_predict(pbf_ctx *ctx, const pbf_params *p) {
   hipLaunchKernelGGL((k_predict<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c,
                      ctx->pos4[s].as<const vec4<N>>(), ctx->vel4[s].as<vec4<N>>(), ctx->type[s].as<const uint8_t>(),
                      ctx->wells.as<const N>(), ctx->pstar[s].as<vec4<N>>(), ctx->key[s].as<uint32_t>(),
-                     ctx->count.as<uint32_t>());
+                     ctx->count.as<uint32_t>(), ctx->cellSlot.as<uint32_t>());
   LAUNCH_CHECK(ctx);
   ctx->st.predicted(c.tableN, /*ahead=*/false);
   return PBF_OK;
@@ -650,7 +655,8 @@ ScanJobs scan_job(const uint32_t *count, uint32_t len, uint32_t *sums, uint32_t 
 }
 
 template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
-  // the scatter consumes the histogram k_predict built (atomicSub back to zero): never run it twice
+  // the scatter consumes the histogram k_predict built (it stores the buckets back to zero, and the slots in cellSlot belong
+  // to that histogram): never run it twice
   if (!ctx->st.counted) return fail(ctx, PBF_ERR_STATE, "pbf_stage_sort needs pbf_stage_predict first");
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
@@ -662,6 +668,7 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   ScanJobs jobs = scan_job(count, len, sums, table);
   int njobs = 1;
   const int s = ctx->st.cur, d = 1 - s;
+  uint32_t *ctl = ctx->brickCtl.as<uint32_t>();
   // option "row_major": the box cells' populations in cell-row-major order and their scan (the row table), read off the
   // Morton table; k_rank_move below then writes the iterations' row-major copy on its way
   RowArrays<N> row{};
@@ -673,7 +680,6 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
     const size_t ncells = size_t(1) << (3 * pshift), llen = ncells + 1;
     const uint32_t lnb = uint32_t((llen + SCAN_TILE - 1) / SCAN_TILE);
     const size_t v = sizeof(vec4<N>);
-    if (int rc = ensure(ctx, ctx->linCount, (ncells + 2 + SCAN_TILE) * 4)) return rc;
     if (int rc = ensure(ctx, ctx->linTable, (ncells + 2 + SCAN_TILE) * 4)) return rc;
     if (int rc = ensure(ctx, ctx->linSums, (size_t(lnb) + 2) * 4)) return rc;
     for (int k = 0; k < 2; ++k)
@@ -690,28 +696,28 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
       if (int rc = ensure(ctx, ctx->rowMortonOf, ctx->cap * 4)) return rc;
       if (int rc = ensure(ctx, ctx->rowSegs, (std::min(nSegTotal, ctx->cap) + 1) * 4)) return rc;
     }
-    // the cells' populations in row order straight from the histogram, so that both tables' scans share their launches
-    hipLaunchKernelGGL(k_lin_count, grid_for(ncells + 1), dim3(BLOCK), 0, ctx->stream, c.tableN, pshift, count,
-                       ctx->linCount.as<uint32_t>());
-    jobs.count[1] = ctx->linCount.as<const uint32_t>(), jobs.sums[1] = ctx->linSums.as<uint32_t>(), jobs.table[1] = ctx->linTable.as<uint32_t>();
+    // the row table's scan has no input array: it gathers the cells' populations from the histogram itself (row_populations),
+    // in the launches of the Morton table's scan
+    jobs.count[1] = nullptr, jobs.rowShift = pshift, jobs.tableN = c.tableN;
+    jobs.sums[1] = ctx->linSums.as<uint32_t>(), jobs.table[1] = ctx->linTable.as<uint32_t>();
     jobs.len[1] = uint32_t(llen), jobs.nb[1] = lnb;
     njobs = 2;
-    // (brickCtl = {nActive bricks, tickets[kTickets], number of big cells}: zeroed once per step, by k_scan_sums on its way)
-    launch_scans(ctx, jobs, njobs, ctx->brickCtl.as<uint32_t>(), kTickets + 2);
-    if (rowDiffuse)  // the x-segments that hold a particle (at most one per particle), for k_diffuse_rows
-      hipLaunchKernelGGL(k_row_segments, grid_for(nSegTotal), dim3(BLOCK), 0, ctx->stream, pshift, segShift,
-                         ctx->linTable.as<const uint32_t>(), ctx->rowSegs.as<uint32_t>(), ctx->linCount.as<uint32_t>() + ncells + 2);
+    if (rowDiffuse)  // the apply pass lists the x-segments that hold a particle (at most one per particle), for k_diffuse_rows
+      jobs.segs = ctx->rowSegs.as<uint32_t>(), jobs.nSegs = ctl + kTickets + 3, jobs.segShift = segShift;
+    // (brickCtl: zeroed once per step, by k_scan_sums on its way — before the apply pass counts segments in it)
+    launch_scans(ctx, jobs, njobs, ctl, kCtlWords);
     row = RowArrays<N>{ctx->rowPstar[0].as<vec4<N>>(), ctx->rowMass.as<N>(), ctx->rowQpos.as<uint2>(), ctx->rowXYZ.as<uint32_t>(),
                        ctx->rowType.as<uint8_t>(), ctx->rowSlotOf.as<uint32_t>(),
                        rowDiffuse ? ctx->rowCol.as<vec4<N>>() : nullptr, rowDiffuse ? ctx->rowMortonOf.as<uint32_t>() : nullptr,
-                       ctx->linTable.as<const uint32_t>(), ctx->linCount.as<uint32_t>() + ncells + 1, pshift};
+                       ctx->linTable.as<const uint32_t>(), ctl + kTickets + 2, pshift};
     ctx->rowShift = pshift, ctx->rowSegShift = segShift;
   }
-  if (njobs == 1) launch_scans(ctx, jobs, 1, ctx->brickCtl.as<uint32_t>(), kTickets + 2);  // (Morton order only)
-  uint32_t *nBig = ctx->brickCtl.as<uint32_t>() + kTickets + 1;
+  if (njobs == 1) launch_scans(ctx, jobs, 1, ctl, kCtlWords);  // (Morton order only)
+  uint32_t *nBig = ctl + kTickets + 1;
   if (int rc = ensure(ctx, ctx->bigCells, (ctx->cap / BIG_CELL + 2) * 4)) return rc;
   hipLaunchKernelGGL(k_scatter_slots, grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c.n, c.tableN,
-                     ctx->key[s].as<const uint32_t>(), table, count, ctx->permTmp.as<uint32_t>(),
+                     ctx->key[s].as<const uint32_t>(), table, ctx->cellSlot.as<const uint32_t>(), count,
+                     ctx->permTmp.as<uint32_t>(),
                      ctx->bigCells.as<uint32_t>(), nBig);
   // pile-ups only: cells with more than BIG_CELL members get their segment sorted (exits at once when there are none)
   hipLaunchKernelGGL(k_sort_big_cells, dim3(64), dim3(BLOCK), 0, ctx->stream, table, c.tableN,
@@ -961,7 +967,6 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
   if (ctx->cellDiffuse && ctx->st.diffuse_on_rows() && ctx->rowDiffuse) {
     // the row-major copy: one wave per segment of 64 x cells, runs staged through LDS, sums applied in place (k_diffuse_rows).
     // On the solver's own stream: the launch is short, nothing is gained by hiding it
-    const uint32_t ncells = 1u << (3u * ctx->rowShift);
     // records of one row's run in the LDS tile (66 cells; the settled dam-break's are ~460): a longer run walks from memory.
     // A small tile matters more than a roomy one: 13 single-wave workgroups per CU at 640 records (fp32), and the launch time
     // is inversely proportional to that number (measured: 1 024 records 68 us, 768 61 us, 640 51 us, 576 51 us)
@@ -973,7 +978,7 @@ template <typename N> int stage_diffuse(pbf_ctx *ctx, const pbf_params *p, bool 
     hipLaunchKernelGGL((k_diffuse_rows<N>), dim3(blocks), dim3(DIFFUSE_ROW_THREADS), lds, ctx->stream, c,
                        row_walk<N>(ctx), ctx->rowCol.as<const vec4<N>>(), ctx->rowType.as<const uint8_t>(),
                        ctx->rowMortonOf.as<const uint32_t>(), ctx->rowSegs.as<const uint32_t>(),
-                       ctx->linCount.as<const uint32_t>() + ncells + 2, ctx->rowSegShift, args.colOut, cap, uint32_t(ctx->n));
+                       ctx->brickCtl.as<const uint32_t>() + kTickets + 3, ctx->rowSegShift, args.colOut, cap, uint32_t(ctx->n));
     LAUNCH_CHECK(ctx);
   } else if (ctx->cellDiffuse && !(ctx->desc.flags & PBF_FLAG_NO_LDS)) {
     brick_list(ctx, c.tableN);
@@ -1226,7 +1231,7 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
     hipLaunchKernelGGL((k_finalise_predict<N>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c,
                        ctx->type[s].as<const uint8_t>(), ctx->pstar[s].as<vec4<N>>(), ctx->pos4[s].as<vec4<N>>(),
                        ctx->vel4[s].as<vec4<N>>(), ctx->wells.as<const N>(), ctx->key[s].as<uint32_t>(),
-                       ctx->count.as<uint32_t>(), ctx->rowPstar[ctx->st.rcur].as<const vec4<N>>(),
+                       ctx->count.as<uint32_t>(), ctx->cellSlot.as<uint32_t>(), ctx->rowPstar[ctx->st.rcur].as<const vec4<N>>(),
                        ctx->st.pstarInRows ? ctx->rowSlotOf.as<const uint32_t>() : nullptr);
     ctx->st.predicted(c.tableN, /*ahead=*/true);
     LAUNCH_CHECK(ctx);
@@ -2916,7 +2921,7 @@ template <typename N> int slab_add_ghosts(pbf_ctx *ctx, const void *rL, uint32_t
   // histogram of the re-assembled set (owned + copies) for the sort
   if (ctx->n)
     hipLaunchKernelGGL(k_count_keys, grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n), ctx->tableN,
-                       ctx->key[ctx->st.cur].as<const uint32_t>(), ctx->count.as<uint32_t>());
+                       ctx->key[ctx->st.cur].as<const uint32_t>(), ctx->count.as<uint32_t>(), ctx->cellSlot.as<uint32_t>());
   LAUNCH_CHECK(ctx);
   ctx->st.histogram_current(ctx->tableN);
   ctx->slabActive = true;
@@ -3233,7 +3238,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
     hipLaunchKernelGGL((k_append_migrants_h<N>), grid_for(arrived), dim3(BLOCK), 0, ctx->stream, nPrev,
                        reinterpret_cast<const MigrantRec<N> *>(rL + WIRE_HDR), got[0],
                        reinterpret_cast<const MigrantRec<N> *>(rR + WIRE_HDR), got[1], ctx->shiftL, ctx->shiftR,
-                       arrays<N>(ctx, a, ctx->st.pcur), c.tableN, ctx->count.as<uint32_t>());
+                       arrays<N>(ctx, a, ctx->st.pcur), c.tableN, ctx->count.as<uint32_t>(), ctx->cellSlot.as<uint32_t>());
     hipLaunchKernelGGL((k_slab_arrival_ghosts<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, nPrev, arrived, sc,
                        arrays<N>(ctx, a, ctx->st.pcur), tot, reinterpret_cast<GhostRec<N> *>(gL + WIRE_HDR),
                        reinterpret_cast<GhostRec<N> *>(gR + WIRE_HDR), reinterpret_cast<uint32_t *>(gL),
@@ -3250,7 +3255,7 @@ template <typename N> int slab_step_impl(pbf_ctx *ctx, const pbf_params *p) {
     hipLaunchKernelGGL((k_append_ghosts_h<N>), grid_for(copies), dim3(BLOCK), 0, ctx->stream, ctx->ghostAt,
                        reinterpret_cast<const GhostRec<N> *>(rL + WIRE_HDR), got[0],
                        reinterpret_cast<const GhostRec<N> *>(rR + WIRE_HDR), got[1], ctx->shiftL, ctx->shiftR,
-                       arrays<N>(ctx, a, ctx->st.pcur), c.tableN, ctx->count.as<uint32_t>());
+                       arrays<N>(ctx, a, ctx->st.pcur), c.tableN, ctx->count.as<uint32_t>(), ctx->cellSlot.as<uint32_t>());
     LAUNCH_CHECK(ctx);
     ctx->hasObstacles = true;  // "special" particles exist: the kernels must look at type[]
   }

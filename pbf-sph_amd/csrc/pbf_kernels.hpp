@@ -26,8 +26,9 @@ template <typename N> __device__ inline int64_t cell_coord(N v) {
 
 // One atomic per distinct bucket per WAVE instead of one per lane: the particles arrive in the previous step's Z order,
 // so the 64 lanes of a wave fall into ~10 cells.  Every lane gets the value the bucket held before the wave's add and its
-// rank among the wave's lanes of the same bucket (the histogram only needs the side effect; the scatter turns the two
-// into its slot).  The loop runs once per distinct bucket of the wave and every lane leaves it.
+// rank among the wave's lanes of the same bucket: before + rank is a slot of its own among the bucket's m members, in
+// [0, m) — the histogram's producers keep it (`cellSlot`) and the scatter places the particle by it.  The loop runs once per
+// distinct bucket of the wave and every lane leaves it.
 template <typename F> __device__ inline void wave_bucket_atomic(uint32_t bucket, F &&leader_op, uint32_t &before, uint32_t &rank) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t below = (1ull << lane) - 1ull;
@@ -99,7 +100,8 @@ template <typename N>
 __global__ __launch_bounds__(BLOCK) void k_predict(StepConsts<N> c, const vec4<N> *__restrict__ pos4,
                                                    vec4<N> *__restrict__ vel4, const uint8_t *__restrict__ type,
                                                    const N *__restrict__ wells, vec4<N> *__restrict__ pstar,
-                                                   uint32_t *__restrict__ key, uint32_t *__restrict__ count) {
+                                                   uint32_t *__restrict__ key, uint32_t *__restrict__ count,
+                                                   uint32_t *__restrict__ cellSlot) {
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= c.n) return;
   const uint8_t ty = c.hasObstacles ? type[i] : uint8_t(0);
@@ -117,6 +119,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(StepConsts<N> c, const vec4<N
   // bucket tableN collects particles outside the table: they are "in no cell" (sph.hpp:206)
   uint32_t before, rank;
   wave_bucket_atomic(min(k, c.tableN), [&](uint32_t b, uint32_t cnt) { return atomicAdd(&count[b], cnt); }, before, rank);
+  cellSlot[i] = before + rank;  // its slot among the bucket's members (k_scatter_slots)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -179,19 +182,53 @@ template <int THREADS = BLOCK> __device__ inline uint32_t block_excl_scan(uint32
 
 // Up to two independent scans per launch (the Morton grid table and, with the row-major working set, the row table): job 0
 // takes the first nb[0] workgroups, job 1 the rest.
+// rowShift != 0: job 1 is the row table of the cube [0, 1 << rowShift)^3 and has no input array of its own — the population
+// of cell (z P + y) P + x is the histogram bin of the cell's Morton code, gathered from count[0] (row_populations).
+// segs != NULL: job 1's apply also lists the non-empty x-segments of 1 << segShift cells for k_diffuse_rows.
 struct ScanJobs {
   const uint32_t *count[2];
   uint32_t *sums[2];
   uint32_t *table[2];
   uint32_t len[2], nb[2];
+  uint32_t rowShift, tableN;
+  uint32_t *segs, *nSegs;
+  uint32_t segShift;
 };
+// SCAN_ITEMS consecutive cells of the cube in row order, from `base` (a multiple of SCAN_ITEMS): a cell the table does not
+// know (code >= tableN - 1, sph.hpp:206-208) and everything behind the cube — the scan's closing entry — count 0
+__device__ inline void row_populations(const ScanJobs &jobs, uint32_t base, uint32_t v[SCAN_ITEMS]) {
+  static_assert(SCAN_ITEMS == 8, "the x bits of eight consecutive cells");
+  const uint32_t *__restrict__ count = jobs.count[0];
+  const uint32_t ps = jobs.rowShift, mask = (1u << ps) - 1u;
+  if (ps >= 3) {  // one row: y, z and the high bits of x are the thread's, the low three x bits count 0..7
+    const uint32_t z = base >> (2u * ps);
+    const uint32_t c0 = morton_encode(base & mask, (base >> ps) & mask, z);
+#pragma unroll
+    for (uint32_t k = 0; k < SCAN_ITEMS; ++k) {
+      const uint32_t code = c0 + ((k & 1u) | ((k & 2u) << 2) | ((k & 4u) << 4));
+      v[k] = (z <= mask && code + 1u < jobs.tableN) ? count[code] : 0u;
+    }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < SCAN_ITEMS; ++k) {
+      const uint32_t lin = base + k, z = lin >> (2u * ps);
+      const uint32_t code = morton_encode(lin & mask, (lin >> ps) & mask, z);
+      v[k] = (z <= mask && code + 1u < jobs.tableN) ? count[code] : 0u;
+    }
+  }
+}
 __global__ __launch_bounds__(BLOCK) void k_scan_block_sums(ScanJobs jobs) {
   const uint32_t j = blockIdx.x >= jobs.nb[0] ? 1u : 0u, blk = blockIdx.x - (j ? jobs.nb[0] : 0u);
   const uint32_t *__restrict__ count = jobs.count[j];
   const uint32_t len = jobs.len[j];
   const uint32_t base = blk * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
   uint32_t s = 0;
-  if (base + SCAN_ITEMS <= len) {
+  if (j && jobs.rowShift) {
+    uint32_t v[SCAN_ITEMS];
+    row_populations(jobs, base, v);
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) s += v[k];
+  } else if (base + SCAN_ITEMS <= len) {
     const uint4 a = *reinterpret_cast<const uint4 *>(count + base);
     const uint4 b = *reinterpret_cast<const uint4 *>(count + base + 4);
     s = a.x + a.y + a.z + a.w + b.x + b.y + b.z + b.w;
@@ -230,10 +267,56 @@ __global__ __launch_bounds__(BLOCK) void k_scan_apply(ScanJobs jobs) {
   const uint32_t base = blk * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
   uint32_t v[SCAN_ITEMS];
   uint32_t s = 0;
+  if (j && jobs.rowShift) {
+    row_populations(jobs, base, v);
 #pragma unroll
-  for (int k = 0; k < SCAN_ITEMS; ++k) {
-    v[k] = (base + k < len) ? count[base + k] : 0u;
-    s += v[k];
+    for (int k = 0; k < SCAN_ITEMS; ++k) s += v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) {
+      v[k] = (base + k < len) ? count[base + k] : 0u;
+      s += v[k];
+    }
+  }
+  // The x-segments that hold a particle (at most one per particle), for k_diffuse_rows: a segment is 1 << segShift <= 64
+  // aligned cells, so it lies inside one wave's 512 cells and is non-empty exactly when its populations do not sum to zero —
+  // lintab[c0 + X] != lintab[c0] without the table.  (Any order: segments are independent.  Cells behind the cube count 0.)
+  if (j && jobs.segs) {
+    const uint32_t sh = jobs.segShift;
+    if (sh >= 3) {  // 1 << (sh - 3) aligned lanes share a segment
+      const uint32_t lanes = 1u << (sh - 3u);
+      uint32_t t = s;
+      for (uint32_t d = 1; d < lanes; d <<= 1) t += __shfl_xor(t, int(d), 64);
+      // one atomic per WORKGROUP: the counter is one word for the whole device, and same-address atomics are served one
+      // after the other (one per wave: 4 096 of them, and this launch takes 30 us instead of 20)
+      __shared__ uint32_t segCount[BLOCK / 64], segAt;
+      const bool mine = t != 0u && (threadIdx.x & (lanes - 1u)) == 0u;
+      const uint64_t listed = __ballot(mine);
+      const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+      if (lane == 0) segCount[wave] = uint32_t(__builtin_popcountll(listed));
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        uint32_t n = 0;
+        for (int w = 0; w < BLOCK / 64; ++w) n += segCount[w];
+        segAt = n ? atomicAdd(jobs.nSegs, n) : 0u;
+      }
+      __syncthreads();
+      if (mine) {
+        uint32_t at = segAt + uint32_t(__builtin_popcountll(listed & ((1ull << lane) - 1ull)));
+        for (uint32_t w = 0; w < wave; ++w) at += segCount[w];
+        jobs.segs[at] = base >> sh;
+      }
+    } else {  // the small cubes (P = 2, 4): a lane holds several segments
+      uint32_t acc = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < SCAN_ITEMS; ++k) {
+        acc += v[k];
+        if (((k + 1u) & ((1u << sh) - 1u)) == 0u) {
+          if (acc != 0u) jobs.segs[atomicAdd(jobs.nSegs, 1u)] = (base + k) >> sh;
+          acc = 0;
+        }
+      }
+    }
   }
   uint32_t total;
   uint32_t run = block_excl_scan(s, &total) + jobs.sums[j][blk];
@@ -293,8 +376,10 @@ struct QuantFilter {
 
 // ------------------------------------------------------------------------------------------------
 // Counting-sort scatter, made deterministic                      (reference: ompsph.hpp:157-159)
-//   pass A: slot inside the cell from an atomic (arbitrary order), records the source index;
-//           atomicSub returns the histogram to zero for the next step (no memset);
+//   pass A: the slot inside the cell is the one the histogram's own atomic handed out (cellSlot, arbitrary order: written by
+//           k_predict, k_finalise_predict, the slab assembly); records the source index there.  The member with slot 0
+//           stores 0 over its bucket: the histogram is all-zero again for the next step (no memset, no second round of
+//           atomics — the histogram's readers, the scans, ran in earlier launches);
 //   pass B: each particle's final rank inside its cell = number of cell-mates with a smaller
 //           source index, i.e. a STABLE sort by key — run-to-run reproducible — then the whole
 //           record moves to its sorted slot (writes stay inside one cell's short range).
@@ -307,6 +392,7 @@ constexpr uint32_t BIG_CELL = 2048;
 
 __global__ __launch_bounds__(BLOCK) void k_scatter_slots(uint32_t n, uint32_t tableN, const uint32_t *__restrict__ key,
                                                          const uint32_t *__restrict__ table,
+                                                         const uint32_t *__restrict__ cellSlot,
                                                          uint32_t *__restrict__ count,
                                                          uint32_t *__restrict__ permTmp,
                                                          uint32_t *__restrict__ bigCells,
@@ -316,10 +402,9 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_slots(uint32_t n, uint32_t ta
   const uint32_t k = key[i];
   if (k == DEAD_KEY) return;  // pbf_slab_step: a slot whose particle has left takes no place in the sorted array
   const uint32_t b = min(k, tableN);
-  uint32_t before, rank;
-  wave_bucket_atomic(b, [&](uint32_t bb, uint32_t cnt) { return atomicSub(&count[bb], cnt); }, before, rank);
-  const uint32_t r = before - 1u - rank;  // r runs m - 1 .. 0 over the cell's m members (which member gets which: arbitrary)
+  const uint32_t r = cellSlot[i];  // r runs 0 .. m - 1 over the cell's m members (which member gets which: arbitrary)
   permTmp[table[b] + r] = i;
+  if (r == 0u) count[b] = 0u;  // one plain store per occupied bucket
   if (r == BIG_CELL) bigCells[atomicAdd(nBig, 1u)] = b;  // exactly one member of a cell with m > BIG_CELL sees this
 }
 
@@ -408,21 +493,6 @@ __host__ __device__ inline bool row_cell_of(uint32_t key, uint32_t tableN, uint3
   const uint32_t x = compact10(key), y = compact10(key >> 1), z = compact10(key >> 2);
   *lin = (((z << pshift) | y) << pshift) | x;
   return key + 1u < tableN;  // (a key >= tableN - 1 is "in no cell" for its neighbours, sph.hpp:206-208; below it, x, y, z < P)
-}
-
-// per cell of the cube: its population, read off the cell histogram k_predict built (one lane per Morton code) — BEFORE the
-// scans, so that the Morton table's and the row table's run in the same launches
-// (over every code of the cube — a bijection onto its cells, so no memset: a cell the table does not know is written 0)
-__global__ __launch_bounds__(BLOCK) void k_lin_count(uint32_t tableN, uint32_t pshift, const uint32_t *__restrict__ count,
-                                                     uint32_t *__restrict__ linCount) {
-  const uint32_t code = blockIdx.x * BLOCK + threadIdx.x;
-  if (code >= (1u << (3u * pshift))) {
-    if (code == (1u << (3u * pshift))) linCount[code] = 0u, linCount[code + 1u] = 0u, linCount[code + 2u] = 0u;  // scan sentinel, tail allocator, segment counter
-    return;
-  }
-  uint32_t lin;
-  const bool known = row_cell_of(code, tableN, pshift, &lin);
-  linCount[lin] = known ? count[code] : 0u;  // (known: code < tableN - 1 — its histogram bin holds exactly the particles with that key)
 }
 
 template <typename N>
@@ -1868,7 +1938,7 @@ template <typename F> __device__ inline void row_for_each_candidate(const RowWal
 // the colour copy — cells x0 - 1 .. x0 + 64 — which the wave copies into LDS with fully coalesced loads (a few records per
 // lane) and each lane then folds its own three-cell sub-run out of it, in the reference's order.  The wave finally applies the
 // sums to the segment's own particles (again a contiguous run) and writes the new colours to their Morton-sorted places:
-// no per-cell sums in memory, no second pass, no halo gather.  k_row_segments lists the segments that hold a particle
+// no per-cell sums in memory, no second pass, no halo gather.  The row table's k_scan_apply lists the segments that hold a particle
 // (persistent workgroups stride over that list).  Cells whose walkers take the Morton table (P = 1024 faces) and the
 // particles in no cell walk serially, as they do in the iteration kernels.
 constexpr int DIFFUSE_ROW_THREADS = 64;
@@ -1878,13 +1948,6 @@ __device__ inline void lds_dma16(const void *src, void *ldsBase) {
   using G = const __attribute__((address_space(1))) void *;
   using L = __attribute__((address_space(3))) void *;
   __builtin_amdgcn_global_load_lds((G)(uintptr_t)src, (L)(uint32_t)(uintptr_t)ldsBase, 16, 0, 0);
-}
-__global__ __launch_bounds__(BLOCK) void k_row_segments(uint32_t pshift, uint32_t segShift, const uint32_t *__restrict__ lintab,
-                                                        uint32_t *__restrict__ segs, uint32_t *__restrict__ nSegs) {
-  const uint32_t sg = blockIdx.x * BLOCK + threadIdx.x;
-  if (sg >= (1u << (3u * pshift - segShift))) return;
-  const uint32_t c0 = sg << segShift;
-  if (lintab[c0 + (1u << segShift)] != lintab[c0]) segs[atomicAdd(nSegs, 1u)] = sg;  // (any order: segments are independent)
 }
 
 template <typename N>
@@ -2452,6 +2515,7 @@ __global__ __launch_bounds__(BLOCK) void k_finalise_predict(StepConsts<N> c, con
                                                             vec4<N> *__restrict__ pstar, vec4<N> *__restrict__ pos4,
                                                             vec4<N> *__restrict__ vel4, const N *__restrict__ wells,
                                                             uint32_t *__restrict__ key, uint32_t *__restrict__ count,
+                                                            uint32_t *__restrict__ cellSlot,
                                                             const vec4<N> *__restrict__ rowPstar,
                                                             const uint32_t *__restrict__ rowSlotOf) {
   const uint32_t a = blockIdx.x * BLOCK + threadIdx.x;
@@ -2473,6 +2537,7 @@ __global__ __launch_bounds__(BLOCK) void k_finalise_predict(StepConsts<N> c, con
   if (!slab_stays(c, k)) return;
   uint32_t before, rank;
   wave_bucket_atomic(min(k, c.tableN), [&](uint32_t b, uint32_t cnt) { return atomicAdd(&count[b], cnt); }, before, rank);
+  cellSlot[a] = before + rank;  // (see k_predict)
 }
 
 // the iterations' row-major {pStar, lambda} back into the Morton-sorted array (stage-level read-backs, the opt-in extras)

@@ -226,11 +226,12 @@ __global__ __launch_bounds__(BLOCK) void k_append_ghosts(uint32_t at, const Ghos
 }
 
 __global__ __launch_bounds__(BLOCK) void k_count_keys(uint32_t n, uint32_t tableN, const uint32_t *__restrict__ key,
-                                                      uint32_t *__restrict__ count) {
+                                                      uint32_t *__restrict__ count, uint32_t *__restrict__ cellSlot) {
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   uint32_t before, rank;  // one atomic per distinct cell per wave (the keeps are still in Z order)
   wave_bucket_atomic(min(key[i], tableN), [&](uint32_t b, uint32_t cnt) { return atomicAdd(&count[b], cnt); }, before, rank);
+  cellSlot[i] = before + rank;  // its slot among the bucket's members (k_scatter_slots)
 }
 
 // owned particles per GLOBAL grid column (1024 bins, LDS-privatised): the load-balance input of the slab driver
@@ -428,20 +429,21 @@ __global__ void k_slab_counts(const uint32_t *__restrict__ totals, uint32_t *__r
   }
 }
 
-// arrivals: appended behind everything the arrays hold, re-keyed into this rank's frame, added to the histogram
+// arrivals: appended behind everything the arrays hold, re-keyed into this rank's frame, added to the histogram (the value
+// the bucket held before is the arrival's slot in it: k_predict's stayers took the slots below)
 template <typename N>
 __global__ __launch_bounds__(BLOCK) void k_append_migrants_h(uint32_t at, const MigrantRec<N> *__restrict__ recvL,
                                                              uint32_t nL, const MigrantRec<N> *__restrict__ recvR,
                                                              uint32_t nR, int32_t shiftL, int32_t shiftR,
                                                              ParticleArrays<N> dst, uint32_t tableN,
-                                                             uint32_t *__restrict__ count) {
+                                                             uint32_t *__restrict__ count, uint32_t *__restrict__ cellSlot) {
   const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
   if (j >= nL + nR) return;
   const MigrantRec<N> r = j < nL ? recvL[j] : recvR[j - nL];
   const uint32_t d = at + j, k = shift_key_x(r.key, j < nL ? shiftL : shiftR);
   dst.pos4[d] = r.pos4, dst.vel4[d] = r.vel4, dst.col4[d] = r.col4, dst.pstar[d] = r.pstar;
   dst.id[d] = r.id, dst.type[d] = uint8_t(r.type), dst.key[d] = k;
-  atomicAdd(&count[min(k, tableN)], 1u);
+  cellSlot[d] = atomicAdd(&count[min(k, tableN)], 1u);
 }
 
 // copies of the arrivals that landed in a boundary column, appended to the ghost wire behind the stayers' copies in
@@ -479,7 +481,7 @@ __global__ __launch_bounds__(BLOCK) void k_append_ghosts_h(uint32_t at, const Gh
                                                            uint32_t nL, const GhostRec<N> *__restrict__ recvR,
                                                            uint32_t nR, int32_t shiftL, int32_t shiftR,
                                                            ParticleArrays<N> dst, uint32_t tableN,
-                                                           uint32_t *__restrict__ count) {
+                                                           uint32_t *__restrict__ count, uint32_t *__restrict__ cellSlot) {
   const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
   if (j >= nL + nR) return;
   const GhostRec<N> r = j < nL ? recvL[j] : recvR[j - nL];
@@ -487,7 +489,7 @@ __global__ __launch_bounds__(BLOCK) void k_append_ghosts_h(uint32_t at, const Gh
   const vec4<N> zero = make_vec4<N>(N(0), N(0), N(0), N(0));
   dst.pos4[d] = zero, dst.vel4[d] = zero, dst.col4[d] = r.col4, dst.pstar[d] = r.pstar;
   dst.id[d] = ~uint64_t(0), dst.type[d] = uint8_t(r.type), dst.key[d] = k;
-  atomicAdd(&count[min(k, tableN)], 1u);
+  cellSlot[d] = atomicAdd(&count[min(k, tableN)], 1u);
 }
 
 }  // namespace pbf
