@@ -54,6 +54,12 @@ class OracleEngine:
         self.got = [0, 0]
         self.slot_of = None
         self.xoff, self.shift = 0, [0, 0]
+        # trace: None, or a list that gets one dict of counters per step (slab_worker --trace; tests/trip_scenes.py reads
+        # them).  top_* = largest index, in THIS engine's array, of a class the selects pick (-1: none) — the staged API
+        # sees the same array.  slot_* = the same in pbf_slab_step's array, which is not compacted between the steps: it
+        # holds last step's sorted set with the copies still in it (slot_at: where each owned particle sits there).
+        self.trace = None
+        self.slot_at, self.n_slots = None, 0
 
     # -- plumbing ----------------------------------------------------------------------------------
     def alloc(self, nbytes):
@@ -73,6 +79,7 @@ class OracleEngine:
     def upload(self, **sc):
         self.o.set_particles(**sc)
         self.n_owned_ = len(sc["id"])
+        self.slot_at, self.n_slots = None, self.n_owned_
 
     def sync(self):
         pass
@@ -126,6 +133,13 @@ class OracleEngine:
         to_l = (~ghost) & has_l & (cx < xlo)
         to_r = (~ghost) & has_r & (cx >= xhi) & ~to_l
         keep = (~ghost) & ~to_l & ~to_r
+        if self.trace is not None:
+            at = np.arange(len(cx)) if self.slot_at is None else self.slot_at
+            top = lambda mask, idx: int(idx[mask].max()) if mask.any() else -1  # noqa: E731
+            self._kept, self._at = np.flatnonzero(keep), at
+            self.trace.append(dict(slots=self.n_slots, n_migrate=len(cx), top_left=top(to_l, np.arange(len(cx))),
+                                   top_right=top(to_r, np.arange(len(cx))), top_keep=top(keep, np.arange(len(cx))),
+                                   slot_left=top(to_l, at), slot_right=top(to_r, at)))
         for mask, buf in ((to_l, send_l), (to_r, send_r)):
             sub = self._take(st, np.flatnonzero(mask))
             rec = np.zeros(len(sub["id"]), self.mig_dt)
@@ -161,6 +175,15 @@ class OracleEngine:
             assert len(rec) <= cap
             self._write(buf, rec)
         self.src = sel
+        if self.trace is not None:  # the array is [stayers, arrivals from the left, arrivals from the right]
+            t, nk = self.trace[-1], len(self._kept)
+            t["n_ghosts"], t["arrivals"] = len(cx), len(cx) - nk
+            for name, idx in (("left", sel[0]), ("right", sel[1])):
+                stay = idx[idx < nk]
+                t["top_copy_" + name] = int(idx.max()) if len(idx) else -1
+                t["slot_copy_" + name] = int(self._at[self._kept[stay]].max()) if len(stay) else -1
+            late = np.concatenate(sel)
+            t["top_arrival_copy"] = int(late.max()) - nk if len(late) and late.max() >= nk else -1
         return len(sel[0]), len(sel[1])
 
     def add_ghosts(self, recv_l, n_l, recv_r, n_r):
@@ -228,6 +251,7 @@ class OracleEngine:
     def finish(self):
         st = self._state()
         keep = np.flatnonzero((st["type"] & GHOST) == 0)
+        self.slot_at, self.n_slots = keep, len(st["id"])
         self._set(self._take(st, keep))
         self.n_owned_ = len(keep)
 

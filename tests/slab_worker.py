@@ -12,7 +12,10 @@ Writes the rank's final owned particles to <out>/rank<r>.npz.
                       and repeatable while the copies are pending — stored as surf<i>_{sample,pn,c,vs,ns,cs,rounds}
                       (rounds = what the call added to pbf_comm_rounds); a set marked "!" is expected to be refused:
                       surf<i>_{rc,rounds}.  After the final download both surface calls once more: after_rc = their codes.
-  --peek-at S         download the owned particles after step S (peek_*), then go on stepping"""
+  --peek-at S         download the owned particles after step S (peek_*), then go on stepping
+  --scene boxN        the moving box of tests/trip_scenes.py
+  --trace             (oracle) per step, where in the arrays the selects' classes sit: trace_<counter>[step], the counters of
+                      OracleEngine.trace"""
 import argparse
 import ctypes as C
 import os
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--vorticity", type=int, default=0)
     ap.add_argument("--surface", default="")
     ap.add_argument("--peek-at", type=int, default=0)
+    ap.add_argument("--trace", action="store_true")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
@@ -58,6 +62,9 @@ def main():
     else:
         if a.scene.startswith("cubes"):
             sc, side = pkg.scene_cubes(int(a.scene[5:]), a.fp64), 1000.0
+        elif a.scene.startswith("box"):
+            import trip_scenes
+            sc, side = trip_scenes.box_scene(int(a.scene[3:]), a.fp64)
         else:
             sc, side = pkg.scene_dambreak(int(a.scene[3:]), a.fp64)
         p = pkg.default_params(a.iteration, side)
@@ -78,6 +85,8 @@ def main():
         from slab_engines import OracleEngine
         eng = OracleEngine(a.fp64, device_pow=True)
         eng.upload(**part)
+        if a.trace:
+            eng.trace = []
         get = eng.download
         stage = False
     else:
@@ -122,6 +131,8 @@ def main():
                      recuts=drv.stats["recuts"])
         cuts = drv.cuts
     out = get()
+    if a.trace and a.engine == "oracle":
+        extra.update({"trace_" + k: np.array([t[k] for t in eng.trace], np.int64) for k in eng.trace[0]})
     if a.surface:  # the download dropped the copies: both calls are refused, and neither exchanges anything
         mc, nv, nt, r0 = pkg.McParams(), C.c_uint64(), C.c_uint64(), drv.rounds
         extra["after_rc"] = np.array([s.L.pbf_surface(s.ctx, C.byref(p), C.byref(mc), C.byref(nt)),

@@ -8,6 +8,7 @@ std::stable_sort's — the oracle's (JACOBI, SORT_STABLE), bit for bit:
   * one cell of exactly BIG_CELL, BIG_CELL + 1 and BIG_CELL + 2 members: the pile-up is announced by the member whose
     slot equals BIG_CELL;
   * the overflow bucket (particles outside the grid, several keys): ordered by (key, source index);
+  * 66 such cells, and 66 with the overflow bucket as the 67th: k_sort_big_cells has 64 workgroups and strides over the list;
   * each with option row_major 1 (two tables, the row table's populations gathered from the histogram) and 0.
 
 The scenes run with K = 0 solver iterations: 20 000 particles at random in 10^3 cells are far from a fluid at rest, and
@@ -15,6 +16,7 @@ nothing of this stage depends on what the iterations do (tests/test_hip_parity.p
 import numpy as np
 import pytest
 
+import trip_scenes as T
 from slab_engines import spread10
 
 pytestmark = pytest.mark.gpu
@@ -202,3 +204,48 @@ def test_overflow_bucket(pkg, oracle, row_major):
     o.finalise(q)
     o.step(q)
     assert_state_equal(s.download(), o.get_particles(), "step after the overflow sort")
+
+
+_PILES = {}
+
+
+def piles_reference(pkg, oracle, overflow):
+    """the oracle's keys, table and ids after each of two rounds of predict + sort, and its state after a whole step behind
+    them (computed once per scene)"""
+    if overflow not in _PILES:
+        sc = T.piles_scene(overflow)
+        q = oracle.make_params(iteration=0, force=(0.0, 0.0, 0.0), max_bound=(T.PILE_SIDE,) * 3, mode=oracle.JACOBI,
+                               sort=oracle.SORT_STABLE)
+        o = oracle.Oracle(False, device_pow=True)
+        o.set_particles(**sc)
+        rounds = []
+        for _ in range(2):
+            o.predict(q)
+            T.check_pile_trips(o.keys(), overflow)  # more listed cells than k_sort_big_cells has workgroups, in both rounds
+            o.sort(q).grid_table(q)
+            rounds.append((o.keys(), o.table(), o.get_particles()["id"]))
+        o.finalise(q)
+        o.step(q)
+        _PILES[overflow] = sc, rounds, o.get_particles()
+    return _PILES[overflow]
+
+
+@pytest.mark.parametrize("row_major", [1, 0])
+@pytest.mark.parametrize("overflow", [False, True], ids=["piles", "piles+overflow"])
+def test_more_big_cells_than_sort_workgroups(pkg, oracle, overflow, row_major):
+    """k_sort_big_cells runs 64 workgroups, one listed cell each and then the cell 64 further on: 66 cells of BIG_CELL + 1
+    members (and, with the overflow bucket over BIG_CELL as well, 67 — that one ordered by (key, source)) put two (three)
+    cells into the second trip.  At rest, K = 0; the second round starts from the histogram the first one left."""
+    sc, rounds, final = piles_reference(pkg, oracle, overflow)
+    p = pkg.default_params(0, T.PILE_SIDE)
+    p.constant_force[:] = (0.0, 0.0, 0.0)
+    s = solver(pkg, sc, row_major)
+    for rnd, (keys, table, ids) in enumerate(rounds):
+        s.stage("predict", p)
+        s.stage("sort", p)
+        assert np.array_equal(s.keys().astype(np.uint64), keys), rnd
+        assert np.array_equal(s.table().astype(np.uint64), table), rnd
+        assert np.array_equal(s.download()["id"], ids), rnd
+    s.stage("finalise", p)
+    s.step(p)
+    assert_state_equal(s.download(), final, "step after the piles")
