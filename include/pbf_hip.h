@@ -167,6 +167,86 @@ int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf);   /* NULL clear
 int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const double *points /* 3n, world */,
                         void *phi /* N[n] */, void *moved /* N[3n], solver frame */, uint8_t *hit /* [n] */);
 
+/* Moving colliders: a rigid pose for the installed lattice (no reference counterpart).  Opt-in: until the first call the
+ * collider is the static one above, kernels and arguments included.
+ *
+ * With a pose the lattice is read in a body frame: a world point is w = R b + t.  The shape does not change, only its
+ * placement, so a paddle, a piston or a gate moves with one call per frame instead of a lattice upload.  The pose persists
+ * until it is changed and applies to every later pbf_stage_delta, pbf_step and pbf_steps (hipGraph replays included) and
+ * to pbf_collider_sample, which stays the window onto the very function delta-p runs.  Within one pbf_steps(count) call
+ * the pose is constant.  pose == NULL returns to the static collider.  pbf_set_collider and pbf_set_collider_mesh,
+ * clearing included, reset the pose to "none".
+ *
+ * The call does not synchronise and uploads no lattice: the ctx keeps one record {N(R), N(t)} on the device, and the call
+ * writes it with a one-lane kernel on the ctx's stream, in stream order with the steps already queued and those to come.
+ * The posed kernels read the record through a pointer, so a new pose changes no argument of a captured step: an update
+ * drops no graph and causes no recapture.  Going between "none" and a pose selects other kernels, so it changes a captured
+ * step's key and drops the captured graphs as pbf_set_collider does (and synchronises, once).
+ *
+ * Refusals, all of which leave the pose and the state unchanged.  PBF_ERR_INVALID: pose != NULL with a non-finite entry;
+ * max |R^T R - I| > 1e-5 evaluated in double (a stated condition of the interface, loose enough for a matrix composed in
+ * float); det R < 0 (a reflection).  PBF_ERR_STATE: no collider is installed; the slab cases pbf_set_collider refuses.  The
+ * library does not re-orthonormalise: it uses N(R) and N(t) as given.  The check is plain host code
+ * (csrc/pbf_collider_pose.hpp).
+ *
+ * The contract with a pose (csrc/pbf_collider.hpp).  Everything is in N, in the order written, not contracted;
+ * PBF_FLAG_FAST_MATH does not reach it.  q is the input of the static contract above.
+ *   w_a  = q_a * scale                         d_a = w_a - t_a
+ *   b_a  = (R[0][a] d_0 + R[1][a] d_1) + R[2][a] d_2                 (R^T d)
+ *   u_a  = (b_a - origin_a) * inv
+ *   ... inside, i, f, the eight nodes, phi, g, len, hit, s: exactly the static contract, on u ...
+ *   b'_a = b_a + s * g_a
+ *   w'_a = ((R[a][0] b'_0 + R[a][1] b'_1) + R[a][2] b'_2) + t_a
+ *   q'_a = hit ? min(maxB_a / scale, max(minB_a / scale, w'_a / scale)) : q_a
+ * A particle that does not hit keeps its bits; outside the lattice, NaN included, nothing is loaded.  The margin and the
+ * spacing are lengths, so a rotation leaves them alone.  The box is the world's: the second clamp is not rotated.
+ * Limitations: the wall is free-slip and pushes through positions; there is no contact velocity, friction or restitution,
+ * and finalise derives the velocity from the projected position with the reference's damping.  There is no swept
+ * collision: a body that moves further per step than its own thickness can pass through fluid.  One collider per ctx; no
+ * pose across slabs; whitewater and the observers do not see the collider. */
+typedef struct pbf_collider_pose {
+  double rot[9];     /* row-major R, body -> world */
+  double trans[3];   /* t, world */
+} pbf_collider_pose;
+int pbf_set_collider_pose(pbf_ctx *ctx, const pbf_collider_pose *pose);   /* NULL: back to the static collider */
+
+/* The reaction: what the collider did to the fluid in the last step, per particle and summed — the other half of a coupling
+ * to a rigid-body solver (no reference counterpart).  Opt-in: pbf_set_collider_reaction(ctx, 1) allocates two vec4 of N per
+ * particle at the ctx's capacity (regrown by an upload that grows it; nothing is allocated inside a step) and selects the
+ * delta-p kernels that keep the records; 0 returns to the kernels without them.  Either change alters a captured step's key
+ * and drops the captured graphs, as pbf_set_collider does.  PBF_ERR_STATE in slab mode.
+ *
+ * Per particle.  With the reaction on, delta-p runs the posed contract above (the identity pose while none is set: the
+ * state then compares equal to the static collider's, a zero may change its sign) and a lane that HITS updates the record
+ * of its particle, in N, after q':
+ *   delta_a = (q'_a - q_a) * scale                r_a = q'_a * scale - t_a
+ *   A_a += delta_a                                hits += 1          (kept as N)
+ *   B_x += r_y * delta_z - r_z * delta_y          (y, z cyclic; each product rounded, one subtraction, one add)
+ * A lane that does not hit stores nothing.  The records are cleared once per step by the sort stage (pbf_stage_sort,
+ * pbf_step, every step of pbf_steps; the clear is captured with the step), when the device order they are indexed by is
+ * established; every delta-p launch until the next sort accumulates into them.  PBF_BUF_COLLIDER_PUSH reads them back
+ * through pbf_read_buffer: N[8n] = {A.xyz, hits, B.xyz, 0} per particle in the device (Morton) order of PBF_BUF_PSTAR,
+ * whichever gather path ran.  PBF_ERR_STATE while the records do not describe the current arrays.
+ *
+ * The sum.  pbf_collider_reaction is an observer call of its own between steps (it synchronises; it is not part of a step
+ * or a captured graph and changes nothing a step reads): P = sum_i m_i A_i and L = sum_i m_i B_i, raw sums as the sampling
+ * calls return them, with L taken about the pose's t (about the world origin without a pose).  The body received -P and
+ * -L; dividing by dt^2 to get a force is the caller's business.  Finalise derives the velocity from the projected position
+ * with the reference's damping, and the figure is the usual position-based estimate, not a pressure integral.  The
+ * reduction has the diagnostics' fixed shape (no atomics, particles taken in the Morton order, terms formed in double):
+ * the same state gives the same bytes on every gather path and in every run.  PBF_ERR_STATE: the reaction is not enabled;
+ * no collider is set; no step has run since enabling (or the arrays have changed since the last one); slab mode. */
+int pbf_set_collider_reaction(pbf_ctx *ctx, int on);
+typedef struct pbf_collider_wrench {
+  double impulse[3];      /* P = sum_i m_i A_i   (mass x world displacement the collider gave the fluid) */
+  double angular[3];      /* L = sum_i m_i B_i   (about the pose's t; about the world origin without a pose) */
+  double abs_impulse[3], abs_angular[3];   /* sums of |term|: what the rounding of P and L scales with */
+  uint64_t hits;          /* projections, summed over particles and iterations */
+  uint64_t particles;     /* particles with at least one */
+  uint64_t step;          /* serial of the step the record belongs to: steps run since the reaction was enabled */
+} pbf_collider_wrench;
+int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);
+
 /* Mesh colliders: the signed-distance lattice of a closed triangle mesh, built on the device (no reference counterpart).
  * Opt-in; neither call is part of a step and both synchronise.  Without a call to them every launch of a step is unchanged.
  *
@@ -354,6 +434,7 @@ enum pbf_buffer {
 };
 /* read through pbf_read_buffer like the values above (enum pbf_buffer itself is closed: its PBF_BUF_COUNT_ stays 7) */
 enum {
+  PBF_BUF_COLLIDER_PUSH = 8, /* N[8n]: {A.xyz, hits, B.xyz, 0} of pbf_set_collider_reaction, the order of PBF_BUF_PSTAR */
   PBF_BUF_WHITEWATER = 7, /* N[4n]: {I_ta, I_wc, E_k, n_d} of the last pbf_whitewater_step, device order; zero for obstacles;
                              PBF_ERR_STATE when there is none, or once the arrays have changed since */
 };

@@ -13,9 +13,12 @@ from .capi import (  # noqa: F401
     AnisoSurface,
     Anisotropy,
     AnisotropyOut,
+    BUF_COLLIDER_PUSH,
     BUF_DENSITY,
     BUF_WHITEWATER,
+    ColliderPose,
     ColliderSdf,
+    ColliderWrench,
     DIAG_DENSITY,
     Diag,
     FLAG_FAST_MATH,

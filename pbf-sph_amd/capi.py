@@ -20,6 +20,7 @@ BUF_OMEGA = 4
 BUF_SURFACE = 5
 BUF_DENSITY = 6
 BUF_WHITEWATER = 7
+BUF_COLLIDER_PUSH = 8
 WW_SPRAY, WW_FOAM, WW_BUBBLE = 0, 1, 2
 DIAG_DENSITY = 1 << 0
 SAMPLE_VELOCITY, SAMPLE_COLOUR = 1 << 0, 1 << 1
@@ -162,6 +163,22 @@ class ColliderSdf(C.Structure):
                 ("phi", C.c_void_p)]
 
 
+class ColliderPose(C.Structure):
+    """pbf_collider_pose (include/pbf_hip.h)"""
+    _fields_ = [("rot", C.c_double * 9), ("trans", C.c_double * 3)]
+
+
+class ColliderWrench(C.Structure):
+    """pbf_collider_wrench (include/pbf_hip.h)"""
+    _fields_ = [("impulse", C.c_double * 3), ("angular", C.c_double * 3), ("abs_impulse", C.c_double * 3),
+                ("abs_angular", C.c_double * 3), ("hits", C.c_uint64), ("particles", C.c_uint64), ("step", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: np.array(getattr(self, k)) for k in ("impulse", "angular", "abs_impulse", "abs_angular")}
+        d.update(hits=int(self.hits), particles=int(self.particles), step=int(self.step))
+        return d
+
+
 class Mesh(C.Structure):
     """pbf_mesh (include/pbf_hip.h)"""
     _fields_ = [("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
@@ -206,6 +223,9 @@ _SIGS = {
     "pbf_set_surface_tension": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "pbf_set_collider": (C.c_int, [C.c_void_p, C.POINTER(ColliderSdf)]),
     "pbf_collider_sample": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbf_set_collider_pose": (C.c_int, [C.c_void_p, C.POINTER(ColliderPose)]),
+    "pbf_set_collider_reaction": (C.c_int, [C.c_void_p, C.c_int]),
+    "pbf_collider_reaction": (C.c_int, [C.c_void_p, C.POINTER(ColliderWrench)]),
     "pbf_mesh_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
     "pbf_sdf_from_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.c_void_p, C.POINTER(MeshSdfStats)]),
     "pbf_set_collider_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
@@ -530,6 +550,39 @@ class Solver:
         sdf.spacing, sdf.margin, sdf.phi = float(spacing), float(margin), a.ctypes.data
         self._chk(self.L.pbf_set_collider(self.ctx, C.byref(sdf)), "pbf_set_collider")
         return self
+
+    def set_collider_pose(self, rot, trans=(0.0, 0.0, 0.0)):
+        """A rigid pose for the installed collider (pbf_set_collider_pose, include/pbf_hip.h): the lattice is read in a body
+        frame, a world point being w = rot @ b + trans.  rot: (3, 3) rotation, body -> world; rot=None returns to the static
+        collider.  No upload, no synchronisation and no recapture per call; persists until it is changed."""
+        if rot is None:
+            self._chk(self.L.pbf_set_collider_pose(self.ctx, None), "pbf_set_collider_pose")
+            return self
+        pose = ColliderPose()
+        pose.rot[:] = [float(v) for v in np.asarray(rot, np.float64).reshape(9)]
+        pose.trans[:] = [float(v) for v in np.asarray(trans, np.float64).reshape(3)]
+        self._chk(self.L.pbf_set_collider_pose(self.ctx, C.byref(pose)), "pbf_set_collider_pose")
+        return self
+
+    def set_collider_reaction(self, on=True):
+        """Opt-in records of what the collider did to the fluid (pbf_set_collider_reaction): per particle through
+        collider_push(), summed through collider_reaction()."""
+        self._chk(self.L.pbf_set_collider_reaction(self.ctx, 1 if on else 0), "pbf_set_collider_reaction")
+        return self
+
+    def collider_reaction(self, raw=False):
+        """The impulse and angular impulse the collider gave the fluid in the last step (pbf_collider_reaction) -> dict(impulse
+        (3,), angular (3,), abs_impulse, abs_angular, hits, particles, step); raw: the ColliderWrench itself.  The body
+        received the negatives."""
+        w = ColliderWrench()
+        self._chk(self.L.pbf_collider_reaction(self.ctx, C.byref(w)), "pbf_collider_reaction")
+        return w if raw else w.as_dict()
+
+    def collider_push(self):
+        """(n, 8): {A.xyz, hits, B.xyz, 0} per particle, the order of pstar() (PBF_BUF_COLLIDER_PUSH)"""
+        a = np.empty((self.n, 8), self.dtype)
+        self._chk(self.L.pbf_read_buffer(self.ctx, BUF_COLLIDER_PUSH, _vp(a), a.nbytes), "read collider push records")
+        return a
 
     def sdf_from_mesh(self, vertices, triangles, origin, spacing, dims, negate=False):
         """pbf_sdf_from_mesh: the signed distance to a closed triangle mesh (counter-clockwise from outside) on the lattice

@@ -29,6 +29,7 @@
 #include "pbf_mesh_sdf.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
+#include "pbf_collider_pose.hpp"
 
 using namespace pbf;
 
@@ -224,6 +225,19 @@ struct pbf_ctx {
   uint32_t colliderDims[3] = {0, 0, 0};
   double colliderOrigin[3] = {0, 0, 0}, colliderSpacing = 0, colliderMargin = 0;
   uint64_t colliderGen = 0;
+  // pbf_set_collider_pose: the one ColliderPose<N> record the posed kernels read through a pointer (allocated by the first
+  // call), and whether a pose is set.  A pose update changes neither; none <-> posed bumps colliderGen (other kernels).
+  DevBuf colliderPose;
+  bool colliderPosed = false;
+  // pbf_set_collider_reaction: the records {A, hits}, {B, 0} of DeltaOp<.., COLLIDE_REACT> (2 vec4<N> per particle, sized to
+  // the capacity), the step counter its clear bumps, the partial sums of pbf_collider_reaction and its pinned record.
+  // pushAt: the order epoch of the sort that cleared the records (0: no sort since enabling), believed like diagRhoAt.
+  // pushRows: the delta-p launches since that sort indexed them by row slot (-1: none has run yet).
+  bool reactionOn = false;
+  DevBuf pushRec, pushCtl, pushPartials, pushOut;
+  Mailbox<WrenchRecord> hostWrench;
+  uint64_t pushAt = 0;
+  int pushRows = -1;
   // "sdf_cull": pbf_sdf_from_mesh / pbf_set_collider_mesh skip the triangles out of a brick's reach (same bytes, 5 - 7 x faster)
   bool sdfCull = true;
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
@@ -654,6 +668,7 @@ ScanJobs scan_job(const uint32_t *count, uint32_t len, uint32_t *sums, uint32_t 
   return j;
 }
 
+int ensure_reaction(pbf_ctx *ctx);
 template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   // the scatter consumes the histogram k_predict built (it stores the buckets back to zero, and the slots in cellSlot belong
   // to that histogram): never run it twice
@@ -734,6 +749,14 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   ctx->gatherSeq = 0;  // (fresh tickets)
   ctx->st.sorted_now(rows, rowDiffuse);
   ctx->orderEpoch++;  // (a new order: what the observers left describes the old one)
+  if (ctx->reactionOn) {  // the reaction records are indexed by the order just established: cleared once per step, here
+    if (int rc = ensure_reaction(ctx)) return rc;  // (allocates only if the capacity grew without an upload)
+    const uint32_t n2 = 2u * uint32_t(ctx->n);
+    hipLaunchKernelGGL((k_push_clear<N>), grid_for(std::max<size_t>(n2, 1)), dim3(BLOCK), 0, ctx->stream, n2, ctx->pushRec.as<vec4<N>>(),
+                       ctx->pushCtl.as<unsigned long long>());
+    LAUNCH_CHECK(ctx);
+    ctx->pushAt = ctx->orderEpoch, ctx->pushRows = -1;
+  }
   if (!rowDiffuse) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
   return PBF_OK;
 }
@@ -1089,15 +1112,25 @@ template <typename N> ColliderSdf<N> collider_args(const pbf_ctx *ctx) {
 }
 constexpr const char *kColliderSlabError = "a collider is not supported in slab mode (pbf_set_collider(ctx, NULL) clears it)";
 
-template <typename N, bool FAST, bool COLLIDE> int delta_run(pbf_ctx *ctx, const pbf_params *p) {
+template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const pbf_params *p) {
   using Op = DeltaOp<N, FAST, COLLIDE>;
-  // (with COLLIDE the lattice follows the stock arguments)
+  // (with a collider the lattice follows the stock arguments, and with a pose the pointer to its record follows the lattice)
   auto args = [&](const typename Op::ArgsPlain &plain) {
-    if constexpr (COLLIDE) return typename Op::Args{plain, collider_args<N>(ctx)};
+    if constexpr (COLLIDE == COLLIDE_REACT)
+      return typename Op::Args{{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()};
+    else if constexpr (COLLIDE == COLLIDE_POSED) return typename Op::Args{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()};
+    else if constexpr (COLLIDE == COLLIDE_STATIC) return typename Op::Args{plain, collider_args<N>(ctx)};
     else return plain;
   };
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
+  if constexpr (COLLIDE == COLLIDE_REACT) {  // the records follow the index of the launch: one kind of index per step
+    const int rows = ctx->st.delta_on_rows() ? 1 : 0;
+    if (!record_current(ctx, ctx->pushAt)) return fail(ctx, PBF_ERR_STATE, "the collider reaction needs a sort since it was enabled");
+    if (ctx->pushRows >= 0 && ctx->pushRows != rows)
+      return fail(ctx, PBF_ERR_STATE, "the gather path changed between two delta-p launches of a step with the collider reaction on");
+    ctx->pushRows = rows;
+  }
   StageTimer t(ctx, ST_DELTA);
   const int s = ctx->st.cur;
   if (ctx->st.delta_on_rows()) {  // list-driven delta-p on the row-major copy
@@ -1119,7 +1152,10 @@ template <typename N, bool FAST, bool COLLIDE> int delta_run(pbf_ctx *ctx, const
   return rc;
 }
 template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
-  return collider_on(ctx) ? delta_run<N, FAST, true>(ctx, p) : delta_run<N, FAST, false>(ctx, p);
+  // the one place that picks the mode
+  if (!collider_on(ctx)) return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
+  if (ctx->reactionOn) return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);  // (the identity pose while none is set)
+  return ctx->colliderPosed ? delta_run<N, FAST, COLLIDE_POSED>(ctx, p) : delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
 }
 template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
   if (collider_on(ctx) && (ctx->comm || ctx->slabActive || ctx->slabConfigured)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
@@ -1137,6 +1173,15 @@ int ensure_surface(pbf_ctx *ctx) {
   const size_t bytes = ctx->cap * (ctx->fp64 ? sizeof(double4) : sizeof(float4));
   if (int rc = ensure(ctx, ctx->surfA, bytes)) return rc;
   return ensure(ctx, ctx->surfB, bytes);
+}
+
+// pbf_set_collider_reaction's buffers, sized to the particle capacity: made when the feature is enabled and regrown when an
+// upload grows the capacity, so that no step allocates
+int ensure_reaction(pbf_ctx *ctx) {
+  if (!ctx->reactionOn) return PBF_OK;
+  const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4);
+  if (int rc = ensure(ctx, ctx->pushRec, std::max<size_t>(ctx->cap, 1) * 2 * v)) return rc;
+  return ensure(ctx, ctx->pushPartials, (ctx->cap / DIAG_TILE + 2) * sizeof(WrenchPartial));
 }
 
 // pbf_diagnostics' buffers, sized to the particle capacity: allocated by the first call that needs them (`first`) and, once
@@ -1373,6 +1418,7 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
+  if (int rc = ensure_reaction(ctx)) return rc;
   if (ctx->wwOn)
     if (int rc = ensure_whitewater_fields(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
@@ -1637,6 +1683,7 @@ int pbf_upload_aos(pbf_ctx *ctx, size_t n, const void *particles, const pbf_aos_
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
+  if (int rc = ensure_reaction(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
   ctx->st.arrays_replaced(0);
   ctx->n = n, ctx->uploaded = n;
@@ -1756,6 +1803,7 @@ void restore(pbf_ctx *ctx, const StepState &s) {
   ctx->st = s.st, ctx->hasObstacles = s.hasObstacles;  // (all of the derived state, not only what the key compares)
   ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
   ctx->orderEpoch++;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
+  if (ctx->reactionOn) ctx->pushAt = ctx->orderEpoch, ctx->pushRows = 0;  // (its clear ran with it; a graphed step has no row-major launches)
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
@@ -2389,14 +2437,30 @@ int collider_lattice_check(pbf_ctx *ctx, const char *who, const pbf_collider_sdf
 }
 
 // the one install path: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's collider
-int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
-  // the steps captured so far hold the old lattice's address and can never be asked for again (colliderGen): drop them
+// With the reaction on and no pose set the kernels run the identity pose: keep the record at it.
+template <typename N> int collider_pose_store(pbf_ctx *ctx, const pbf_collider_pose *pose);
+int collider_pose_identity(pbf_ctx *ctx) {
+  if (!ctx->reactionOn || ctx->colliderPosed) return PBF_OK;
+  pbf_collider_pose id{};
+  id.rot[0] = id.rot[4] = id.rot[8] = 1.0;
+  if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
+  return ctx->fp64 ? collider_pose_store<double>(ctx, &id) : collider_pose_store<float>(ctx, &id);
+}
+// the steps captured so far can never be asked for again once colliderGen moves on: drop them
+int collider_drop_graphs(pbf_ctx *ctx) {
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (auto &g : ctx->graphs)
     if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
   ctx->graphs.clear();
-  ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
   ctx->colliderGen++;
+  return PBF_OK;
+}
+int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
+  // (they hold the old lattice's address)
+  if (int rc = collider_drop_graphs(ctx)) return rc;
+  ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
+  ctx->colliderPosed = false;           // (a new solid starts without a pose)
+  if (int rc = collider_pose_identity(ctx)) return rc;
   for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
   ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
   return PBF_OK;
@@ -2451,6 +2515,33 @@ int mesh_sdf_run(pbf_ctx *ctx, const char *who, const pbf_mesh *mesh, const pbf_
   return ctx->fp64 ? mesh_sdf_impl<double>(ctx, mesh, lat, flags, *nodes, fresh, stats)
                    : mesh_sdf_impl<float>(ctx, mesh, lat, flags, *nodes, fresh, stats);
 }
+// pbf_collider_reaction: the two launches of the sum and the polled read-back, as diagnostics_impl
+static_assert(sizeof(pbf_collider_wrench) == 15 * 8 && offsetof(WrenchRecord, seq) == sizeof(pbf_collider_wrench) &&
+                  offsetof(pbf_collider_wrench, hits) == offsetof(WrenchRecord, hits) &&
+                  offsetof(pbf_collider_wrench, step) == offsetof(WrenchRecord, step),
+              "WrenchRecord (pbf_kernels.hpp) is pbf_collider_wrench followed by the polled word");
+template <typename N> int collider_reaction_impl(pbf_ctx *ctx, pbf_collider_wrench *out) {
+  uint32_t seq;
+  HIPCHK(ctx, ctx->hostWrench.arm(seq));
+  const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
+  if (nb)
+    hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(),
+                       ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[ctx->st.cur].as<const vec4<N>>(),
+                       ctx->pushPartials.as<WrenchPartial>());
+  hipLaunchKernelGGL(k_wrench_final, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->pushPartials.as<const WrenchPartial>(),
+                     ctx->pushCtl.as<const unsigned long long>(), ctx->hostWrench.rec.p, seq);
+  LAUNCH_CHECK(ctx);
+  return receive(ctx, ctx->hostWrench, "collider reaction read-back", *out);
+}
+// pbf_set_collider_pose: N(R), N(t) into the ctx's record by a one-lane kernel on the stream; no synchronisation
+template <typename N> int collider_pose_store(pbf_ctx *ctx, const pbf_collider_pose *pose) {
+  ColliderPose<N> v;
+  for (int k = 0; k < 9; ++k) v.rot[k] = N(pose->rot[k]);
+  for (int k = 0; k < 3; ++k) v.trans[k] = N(pose->trans[k]);
+  hipLaunchKernelGGL((k_collider_pose_store<N>), dim3(1), dim3(1), 0, ctx->stream, v, ctx->colliderPose.as<ColliderPose<N>>());
+  LAUNCH_CHECK(ctx);
+  return PBF_OK;
+}
 template <typename N>
 int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, N *phi, N *moved, uint8_t *hit) {
   std::vector<N> pts(3 * n);
@@ -2463,7 +2554,8 @@ int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const doub
   f.scale = N(p->scale);
   for (int a = 0; a < 3; ++a) f.minB[a] = N(p->min_bound[a]), f.maxB[a] = N(p->max_bound[a]);
   HIPCHK(ctx, hipMemcpyAsync(ctx->samplePoints.p, pts.data(), 3 * e, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL((k_collider_sample<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, collider_args<N>(ctx), f, uint32_t(n),
+  hipLaunchKernelGGL((k_collider_sample<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, collider_args<N>(ctx),
+                     ctx->colliderPosed ? ctx->colliderPose.as<const ColliderPose<N>>() : nullptr, f, uint32_t(n),
                      ctx->samplePoints.as<const N>(), reinterpret_cast<N *>(out), reinterpret_cast<N *>(out + e),
                      reinterpret_cast<uint8_t *>(out + 4 * e));
   LAUNCH_CHECK(ctx);
@@ -2487,6 +2579,66 @@ int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
   if (sdf)
     if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, sdf, nodes, fresh) : set_collider_impl<float>(ctx, sdf, nodes, fresh)) return rc;
   return collider_install(ctx, sdf, fresh);
+}
+
+int pbf_set_collider_pose(pbf_ctx *ctx, const pbf_collider_pose *pose) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (pose) {
+    const char *why = nullptr;
+    if (colliderpose::check(pose, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  }
+  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_pose: no collider set (pbf_set_collider)");
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!pose) {  // back to the static kernels
+    if (!ctx->colliderPosed) return PBF_OK;
+    if (int rc = collider_drop_graphs(ctx)) return rc;
+    ctx->colliderPosed = false;
+    return collider_pose_identity(ctx);
+  }
+  if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
+  if (int rc = ctx->fp64 ? collider_pose_store<double>(ctx, pose) : collider_pose_store<float>(ctx, pose)) return rc;
+  if (!ctx->colliderPosed) {  // none -> posed selects other kernels; an update changes no key and drops no graph
+    if (int rc = collider_drop_graphs(ctx)) return rc;
+    ctx->colliderPosed = true;
+  }
+  return PBF_OK;
+}
+
+int pbf_set_collider_reaction(pbf_ctx *ctx, int on) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured)
+    return fail(ctx, PBF_ERR_STATE, "the collider reaction is not supported in slab mode");
+  const bool want = on != 0;
+  if (want == ctx->reactionOn) return PBF_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (want) {
+    ctx->reactionOn = true;
+    int rc = ensure_reaction(ctx);
+    if (!rc) rc = ensure(ctx, ctx->pushCtl, 8);
+    if (!rc) rc = collider_pose_identity(ctx);
+    if (!rc && hipMemsetAsync(ctx->pushCtl.p, 0, 8, ctx->stream) != hipSuccess) rc = fail(ctx, PBF_ERR_HIP, "pbf_set_collider_reaction: hipMemsetAsync failed");
+    if (rc) {
+      ctx->reactionOn = false;
+      return rc;
+    }
+  }
+  if (int rc = collider_drop_graphs(ctx)) return rc;  // (other delta-p kernels, and the sort's clear comes or goes)
+  ctx->reactionOn = want;
+  ctx->pushAt = 0, ctx->pushRows = -1;
+  return PBF_OK;
+}
+
+int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_reaction: out == NULL");
+  if (!ctx->reactionOn) return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: not enabled (pbf_set_collider_reaction)");
+  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: no collider set (pbf_set_collider)");
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (!record_current(ctx, ctx->pushAt))
+    return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: no step since the reaction was enabled or the arrays last changed");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->fp64 ? collider_reaction_impl<double>(ctx, out) : collider_reaction_impl<float>(ctx, out);
 }
 
 int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records, pbf_mesh_info *info) {
@@ -2734,6 +2886,24 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
       if (!record_current(ctx, ctx->wwPotAt))
         return fail(ctx, PBF_ERR_STATE, "no whitewater step since the arrays last changed (pbf_whitewater_step)");
       src = ctx->wwPot.p, avail = std::min(ctx->n * v, ctx->wwPot.cap);
+      break;
+    case PBF_BUF_COLLIDER_PUSH:
+      if (!ctx->reactionOn || !record_current(ctx, ctx->pushAt))
+        return fail(ctx, PBF_ERR_STATE, "no sort since the collider reaction was enabled or the arrays last changed (pbf_set_collider_reaction)");
+      if (ctx->pushRows > 0) {  // the records are in row order: into the Morton order, as PBF_BUF_PSTAR's are
+        if (int rc = ensure(ctx, ctx->pushOut, std::max<size_t>(ctx->cap, 1) * 2 * v)) return rc;
+        if (ctx->fp64)
+          hipLaunchKernelGGL((k_push_to_morton<double>), grid_for(std::max<size_t>(ctx->n, 1)), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
+                             ctx->pushRec.as<const vec4<double>>(), ctx->rowSlotOf.as<const uint32_t>(), ctx->pushOut.as<vec4<double>>());
+        else
+          hipLaunchKernelGGL((k_push_to_morton<float>), grid_for(std::max<size_t>(ctx->n, 1)), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
+                             ctx->pushRec.as<const vec4<float>>(), ctx->rowSlotOf.as<const uint32_t>(), ctx->pushOut.as<vec4<float>>());
+        LAUNCH_CHECK(ctx);
+        src = ctx->pushOut.p;
+      } else {
+        src = ctx->pushRec.p;
+      }
+      avail = ctx->n * 2 * v;
       break;
     case PBF_BUF_DENSITY:
       if (!record_current(ctx, ctx->diagRhoAt))

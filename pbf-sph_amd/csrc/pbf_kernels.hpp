@@ -899,8 +899,21 @@ template <typename N, bool FAST> struct LambdaOp {
 // delta-p + clamp (ompsph.hpp:235-248), Jacobi: reads pstarIn (xyz + lambda), writes pstarOut.
 // COLLIDE: pbf_set_collider's projection after the clamp (csrc/pbf_collider.hpp).  A compile-time switch, so that without a
 // collider the kernels and their arguments are exactly what they are without the feature (measured: a run-time test on a
-// lattice pointer in the arguments cost 0.3 % of a 1 M-particle step, profiles/collider_1m.md).
-template <typename N, bool FAST, bool COLLIDE = false> struct DeltaOp {
+// lattice pointer in the arguments cost 0.3 % of a 1 M-particle step, profiles/collider_1m.md).  A small mode, not a bool:
+// off (no collider: not one kernel or argument differs from a build without the feature), static (a collider and no pose
+// ever set: the lattice follows the stock arguments) and posed (pbf_set_collider_pose: a pointer to the ctx's pose record
+// follows the lattice) and posed with the reaction record (pbf_set_collider_reaction: the per-particle records follow the
+// pose; without a pose it runs the identity pose, so that only two new instantiations exist).  Every gather kernel gets
+// the modes through this op.
+//
+// The reaction record of particle i, two vec4<N> at push[2 i] and push[2 i + 1], updated by a lane that HITS (any other
+// lane stores nothing), in N after q':
+//   delta_a = (q'_a - q_a) * scale                r_a = q'_a * scale - t_a
+//   A_a += delta_a                                hits += 1          (kept in A.w as N)
+//   B_x += r_y * delta_z - r_z * delta_y          (y, z cyclic; each product rounded, one subtraction, one add)
+// The sort stage clears the records once per step; every delta-p launch until the next sort accumulates into them.
+enum ColliderMode : int { COLLIDE_OFF = 0, COLLIDE_STATIC = 1, COLLIDE_POSED = 2, COLLIDE_REACT = 3 };
+template <typename N, bool FAST, int COLLIDE = COLLIDE_OFF> struct DeltaOp {
   using Src = vec4<N>;
   struct ArgsPlain {
     const vec4<N> *pstarIn;
@@ -911,7 +924,14 @@ template <typename N, bool FAST, bool COLLIDE = false> struct DeltaOp {
   struct ArgsSdf : ArgsPlain {
     ColliderSdf<N> sdf;  // the lattice, sdf.phi != NULL
   };
-  using Args = std::conditional_t<COLLIDE, ArgsSdf, ArgsPlain>;
+  struct ArgsPosed : ArgsSdf {
+    const ColliderPose<N> *pose;  // the ctx's record, written by k_collider_pose_store between steps
+  };
+  struct ArgsReact : ArgsPosed {
+    vec4<N> *push;  // {A.xyz, hits}, {B.xyz, 0} per particle, indexed like pstarOut
+  };
+  using Args = std::conditional_t<COLLIDE == COLLIDE_REACT, ArgsReact,
+                                  std::conditional_t<COLLIDE == COLLIDE_POSED, ArgsPosed, std::conditional_t<COLLIDE == COLLIDE_STATIC, ArgsSdf, ArgsPlain>>>;
   static constexpr bool kNeedsCandidateType = false;
   static constexpr bool kFilter = true;
   static constexpr bool kTileable = true;
@@ -972,7 +992,19 @@ template <typename N, bool FAST, bool COLLIDE = false> struct DeltaOp {
     y = min(c.maxB[1], max(c.minB[1], y));
     z = min(c.maxB[2], max(c.minB[2], z));
     x = x / c.scale, y = y / c.scale, z = z / c.scale;
-    if constexpr (COLLIDE) collider_project<N>(a.sdf, c.scale, c.minB, c.maxB, x, y, z, nullptr);
+    if constexpr (COLLIDE == COLLIDE_STATIC) collider_project<N>(a.sdf, c.scale, c.minB, c.maxB, x, y, z, nullptr);
+    if constexpr (COLLIDE == COLLIDE_POSED) collider_project_posed<N>(a.sdf, a.pose, c.scale, c.minB, c.maxB, x, y, z, nullptr);
+    if constexpr (COLLIDE == COLLIDE_REACT) {
+      const N qx = x, qy = y, qz = z;
+      if (collider_project_posed<N>(a.sdf, a.pose, c.scale, c.minB, c.maxB, x, y, z, nullptr)) {
+        const N dx = (x - qx) * c.scale, dy = (y - qy) * c.scale, dz = (z - qz) * c.scale;
+        const N rx = x * c.scale - a.pose->trans[0], ry = y * c.scale - a.pose->trans[1], rz = z * c.scale - a.pose->trans[2];
+        vec4<N> A = a.push[2u * i], B = a.push[2u * i + 1u];
+        A.x += dx, A.y += dy, A.z += dz, A.w += N(1);
+        B.x += ry * dz - rz * dy, B.y += rz * dx - rx * dz, B.z += rx * dy - ry * dx;
+        a.push[2u * i] = A, a.push[2u * i + 1u] = B;
+      }
+    }
     const vec4<N> out = make_vec4<N>(x, y, z, pa.w);
     a.pstarOut[i] = out;
     if (a.qpos) {
@@ -3240,6 +3272,110 @@ __global__ __launch_bounds__(BLOCK) void k_diag_partial(uint32_t n, const vec4<N
   }
   diag_block_fold(a, waves);
   if (threadIdx.x == 0) partials[blockIdx.x] = a;
+}
+
+// ---- pbf_set_collider_reaction / pbf_collider_reaction: the per-particle records of DeltaOp<.., COLLIDE_REACT> and their sum --
+// the sort stage's clear, captured with the step: 2 n records to zero, and the count of the steps that have run since the
+// reaction was enabled (ctl[0], one lane, a plain load and store: launches of one stream do not overlap)
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_push_clear(uint32_t n2, vec4<N> *__restrict__ push, unsigned long long *__restrict__ ctl) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < n2) push[i] = make_vec4<N>(N(0), N(0), N(0), N(0));
+  if (i == 0) ctl[0] = ctl[0] + 1ull;
+}
+// PBF_BUF_COLLIDER_PUSH after delta-p ran on the row-major copy: the records into the Morton order, as k_rows_to_morton does
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_push_to_morton(uint32_t n, const vec4<N> *__restrict__ push, const uint32_t *__restrict__ rowSlotOf,
+                                                          vec4<N> *__restrict__ out) {
+  const uint32_t a = blockIdx.x * BLOCK + threadIdx.x;
+  if (a >= n) return;
+  const uint32_t r = rowSlotOf[a];
+  out[2u * a] = push[2u * r], out[2u * a + 1u] = push[2u * r + 1u];
+}
+
+// The sum: the diagnostics' reduction with another record — two launches of a fixed shape, no atomics.  Workgroup b owns the
+// particles [DIAG_TILE b, DIAG_TILE (b + 1)) OF THE MORTON ORDER whichever path ran (slotOf: Morton index -> row slot, NULL
+// when the records are in Morton order), so the same state gives the same bytes on every gather path.  Terms are formed in
+// double from the stored N values (double(m) * double(A_a)), not contracted.
+struct WrenchPartial {
+  double sum[12];             // P.xyz, L.xyz, sum |P term|.xyz, sum |L term|.xyz
+  unsigned long long cnt[2];  // hits, particles with at least one
+};
+__device__ inline void wrench_identity(WrenchPartial &p) {
+  for (int k = 0; k < 12; ++k) p.sum[k] = 0.0;
+  p.cnt[0] = p.cnt[1] = 0ull;
+}
+__device__ inline void wrench_fold(WrenchPartial &a, const WrenchPartial &b) {
+  for (int k = 0; k < 12; ++k) a.sum[k] += b.sum[k];
+  a.cnt[0] += b.cnt[0], a.cnt[1] += b.cnt[1];
+}
+// the wave's lanes by an xor butterfly, the wave records through LDS in wave order: thread 0 alone holds the result
+__device__ inline void wrench_block_fold(WrenchPartial &p, WrenchPartial *waves) {
+#pragma unroll 1
+  for (int m = 1; m < 64; m <<= 1) {
+    WrenchPartial o;
+    for (int k = 0; k < 12; ++k) o.sum[k] = __shfl_xor(p.sum[k], m);
+    for (int k = 0; k < 2; ++k) o.cnt[k] = __shfl_xor(p.cnt[k], m);
+    wrench_fold(p, o);
+  }
+  if ((threadIdx.x & 63u) == 0) waves[threadIdx.x >> 6] = p;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (uint32_t w = 1; w < BLOCK / 64; ++w) wrench_fold(p, waves[w]);
+  __syncthreads();  // (the next round overwrites `waves`)
+}
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_wrench_partial(uint32_t n, const vec4<N> *__restrict__ push, const uint32_t *__restrict__ slotOf,
+                                                          const vec4<N> *__restrict__ pos4, WrenchPartial *__restrict__ partials) {
+  __shared__ WrenchPartial waves[BLOCK / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t waveBase = blockIdx.x * DIAG_TILE + wave * 64u * DIAG_ITEMS;
+  WrenchPartial a;
+  wrench_identity(a);
+#pragma unroll 1
+  for (int j = 0; j < DIAG_ITEMS; ++j) {
+    const uint32_t i = waveBase + j * 64u + lane;
+    if (i >= n) continue;
+    const uint32_t r = slotOf ? slotOf[i] : i;
+    const vec4<N> A = push[2u * r], B = push[2u * r + 1u];
+    if (!(A.w > N(0))) continue;  // (never hit: its record is zero)
+    const double m = double(pos4[i].w);
+    const double t[6] = {m * double(A.x), m * double(A.y), m * double(A.z), m * double(B.x), m * double(B.y), m * double(B.z)};
+    for (int k = 0; k < 6; ++k) a.sum[k] += t[k], a.sum[6 + k] += fabs(t[k]);
+    a.cnt[0] += static_cast<unsigned long long>(A.w), a.cnt[1] += 1ull;
+  }
+  wrench_block_fold(a, waves);
+  if (threadIdx.x == 0) partials[blockIdx.x] = a;
+}
+// the device's image of pbf_collider_wrench (include/pbf_hip.h; pbf_hip.hip asserts that the two agree) + the polled word
+struct WrenchRecord {
+  double impulse[3], angular[3], abs_impulse[3], abs_angular[3];
+  unsigned long long hits, particles, step;
+  uint32_t seq;
+};
+__global__ __launch_bounds__(BLOCK) void k_wrench_final(uint32_t nb, const WrenchPartial *__restrict__ partials,
+                                                        const unsigned long long *__restrict__ ctl, volatile WrenchRecord *__restrict__ host,
+                                                        uint32_t seq) {
+  __shared__ WrenchPartial waves[BLOCK / 64];
+  WrenchPartial t;
+  wrench_identity(t);
+  for (uint32_t base = 0; base < nb; base += BLOCK) {  // BLOCK records at a time in index order
+    const uint32_t i = base + threadIdx.x;
+    WrenchPartial p;
+    if (i < nb) p = partials[i];
+    else wrench_identity(p);
+    wrench_block_fold(p, waves);
+    wrench_fold(t, p);  // (thread 0's is the one that counts)
+  }
+  if (threadIdx.x != 0) return;
+  for (int k = 0; k < 3; ++k) {
+    host->impulse[k] = t.sum[k], host->angular[k] = t.sum[3 + k];
+    host->abs_impulse[k] = t.sum[6 + k], host->abs_angular[k] = t.sum[9 + k];
+  }
+  host->hits = t.cnt[0], host->particles = t.cnt[1], host->step = ctl[0];
+  __threadfence_system();
+  host->seq = seq;
+  __threadfence_system();
 }
 
 // the device's image of pbf_diag (include/pbf_hip.h; pbf_hip.hip asserts that the two agree) + the polled word

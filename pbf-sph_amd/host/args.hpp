@@ -43,6 +43,11 @@ struct Args {
   double colliderCfg[4] = {0, 0, 0, 0};
   double colliderMargin = 13.5;           // half the rest spacing of 27 world units
   double colliderSpacing = 0;             // 0 = h * scale / 2
+  // --collider-motion=vx,vy,vz[,wx,wy,wz[,px,py,pz]] with --resident and --collider: the solid moves rigidly — a linear velocity
+  // and an angular velocity (rad / s) about a pivot, world units per second; --collider-reaction[=every] prints the wrench
+  bool colliderMoves = false;
+  double colliderMotion[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  size_t colliderReaction = 0;            // 0 = off
   double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
   size_t wwCapacity = 0;                  // 0 = off
   bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
@@ -109,6 +114,13 @@ struct Args {
           "      --collider=mesh:[FILE.obj[,margin[,spacing[,negate]]]]  The same, from a closed triangle mesh (v and triangular\n"
           "                                        f lines, counter-clockwise from outside): the lattice is computed on the\n"
           "                                        device. negate = 1: the solid is OUTSIDE the mesh (a cavity)\n"
+          "      --collider-motion=[vx,vy,vz[,wx,wy,wz[,px,py,pz]]]  With --resident and --collider: the solid moves rigidly, with\n"
+          "                                        a linear velocity and an angular velocity (rad / s) about the pivot p, in\n"
+          "                                        world units per second: the pose of a frame is set before it is stepped\n"
+          "                                        (no lattice upload, no recapture). A body that moves further per frame\n"
+          "                                        than its thickness can pass through fluid\n"
+          "      --collider-reaction[=every]       With --resident and --collider: one JSON line per `every` frames with the impulse\n"
+          "                                        and angular impulse the collider gave the fluid in that frame\n"
           "      --whitewater=[k_ta,k_wc[,capacity]]  With --resident: spray, foam and air bubbles after Ihmsen et al. 2012,\n"
           "                                        one whitewater step after every frame at these rates; the tau ranges are\n"
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
@@ -224,6 +236,19 @@ struct Args {
           wwTa = f[0], wwWc = f[1];
           wwCapacity = f.size() == 3 ? size_t(f[2]) : size_t(262144);
           if (!(wwTa >= 0 && wwWc >= 0) || wwCapacity == 0) throw std::runtime_error("--whitewater: rates must be >= 0, capacity >= 1");
+        }
+        else if (value(i, a, "", "--collider-motion", v)) {
+          const auto f = numbers(v);
+          if (f.size() != 3 && f.size() != 6 && f.size() != 9) throw std::runtime_error("--collider-motion: expected vx,vy,vz[,wx,wy,wz[,px,py,pz]]");
+          for (double x : f)
+            if (!std::isfinite(x)) throw std::runtime_error("--collider-motion: the values must be finite");
+          colliderMoves = true;
+          for (size_t k = 0; k < f.size(); ++k) colliderMotion[k] = f[k];
+        }
+        else if (a == "--collider-reaction") colliderReaction = 1;
+        else if (a.rfind("--collider-reaction=", 0) == 0) {
+          colliderReaction = std::stoull(a.substr(20));
+          if (colliderReaction == 0) throw std::runtime_error("--collider-reaction: every must be >= 1");
         }
         else if (value(i, a, "", "--collider", v)) {
           const size_t colon = v.find(':');

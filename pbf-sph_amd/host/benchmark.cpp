@@ -119,6 +119,15 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   if (collider && !args.resident) std::cout << "--collider takes effect with --resident: ignored" << std::endl;
+  if ((args.colliderMoves || args.colliderReaction) && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--collider-motion / --collider-reaction are single-device features: they cannot be combined with --slabs / --all-devices"
+              << std::endl;
+    return 1;
+  }
+  if ((args.colliderMoves || args.colliderReaction) && !(collider && args.resident))
+    std::cout << "--collider-motion / --collider-reaction take effect with --resident and --collider: ignored" << std::endl;
+  const bool colliderMoves = args.colliderMoves && collider && args.resident;
+  const size_t colliderReaction = collider && args.resident ? args.colliderReaction : 0;
   if (args.diagnostics && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--diagnostics is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -216,6 +225,25 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
               << ", spacing " << spacing << ", margin " << args.colliderMargin << std::endl;
     }
   }
+  if (colliderReaction) solver.enableColliderReaction();
+  // --collider-motion: the pose of the frame numbered f (warm-up frames included), at time f * dt — a rotation by |w| f dt about
+  // the axis w through the pivot p (Rodrigues), then the translation v f dt: w = R (b - p) + p + v f dt
+  size_t poseFrame = 0;
+  auto colliderPoseOf = [&](size_t f, std::array<double, 9> &rot, std::array<double, 3> &trans) {
+    const double *m = args.colliderMotion, tau = double(f) * double(param.dt);
+    const double wl = std::sqrt((m[3] * m[3] + m[4] * m[4]) + m[5] * m[5]), angle = wl * tau;
+    const double k[3] = {wl > 0 ? m[3] / wl : 0.0, wl > 0 ? m[4] / wl : 0.0, wl > 0 ? m[5] / wl : 0.0};
+    const double K[9] = {0, -k[2], k[1], k[2], 0, -k[0], -k[1], k[0], 0}, s = std::sin(angle), c1 = 1.0 - std::cos(angle);
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        const double kk = (K[3 * a] * K[b] + K[3 * a + 1] * K[3 + b]) + K[3 * a + 2] * K[6 + b];
+        rot[size_t(3 * a + b)] = ((a == b ? 1.0 : 0.0) + s * K[3 * a + b]) + c1 * kk;
+      }
+    for (int a = 0; a < 3; ++a) {
+      const double rp = (rot[size_t(3 * a)] * m[6] + rot[size_t(3 * a + 1)] * m[7]) + rot[size_t(3 * a + 2)] * m[8];
+      trans[size_t(a)] = (m[6 + a] - rp) + m[a] * tau;
+    }
+  };
   if (args.indexedMesh) solver.indexedMesh(true);
   sph::hip_impl::IndexedMesh<N, sph::vec> indexed;  // --indexed-mesh --resident: the last frame's mesh
   // the resident arrays grow by what the inlets emit: room for every frame of the run
@@ -238,6 +266,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   }
   auto one = [&](size_t frame) {
     if (args.resident) {
+      if (colliderMoves) {  // the pose of this frame, before it is stepped
+        std::array<double, 9> rot;
+        std::array<double, 3> trans;
+        colliderPoseOf(poseFrame++, rot, trans);
+        solver.setColliderPose(rot, trans);
+      }
       solver.step(frameParam(frame), scene);
       if (whitewater && solver.count()) {
         solver.whitewaterStep(frameParam(frame));
@@ -309,6 +343,21 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cout << "]}" << std::endl;
     diagMillis += duration_millis(hrc::now() - d0).count();
   };
+  // --collider-reaction: one JSON line per report; its time is kept out like the diagnostics'
+  auto wrench = [&](size_t frame) {
+    const auto d0 = hrc::now();
+    const pbf_collider_wrench w = solver.colliderReaction();
+    auto num = [](double x) {
+      char buf[40];
+      std::snprintf(buf, sizeof buf, "%.17g", x);
+      return std::isfinite(x) ? std::string(buf) : std::string("null");
+    };
+    auto vec3 = [&](const double *v) { return "[" + num(v[0]) + "," + num(v[1]) + "," + num(v[2]) + "]"; };
+    std::cout << "{\"frame\":" << frame << ",\"wrench\":{\"impulse\":" << vec3(w.impulse) << ",\"angular\":" << vec3(w.angular)
+              << ",\"abs_impulse\":" << vec3(w.abs_impulse) << ",\"abs_angular\":" << vec3(w.abs_angular) << ",\"hits\":" << w.hits
+              << ",\"particles\":" << w.particles << ",\"step\":" << w.step << "}}" << std::endl;
+    diagMillis += duration_millis(hrc::now() - d0).count();
+  };
   const bool probing = args.resident && !args.probes.empty();
   start = hrc::now();
   for (size_t frame = 0; frame < args.iterations; ++frame) {
@@ -321,6 +370,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     }
     frameTime.push_back(duration_millis(hrc::now() - f0).count());
     if (args.resident && args.diagnostics && (frame + 1) % args.diagnostics == 0) report(frame);
+    if (colliderReaction && solver.count() && (frame + 1) % colliderReaction == 0) wrench(frame);
     if (probing && (args.probeEvery ? (frame + 1) % args.probeEvery == 0 : frame + 1 == args.iterations)) probe(frame);
   }
   end = hrc::now();

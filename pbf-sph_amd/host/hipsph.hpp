@@ -453,6 +453,35 @@ public:
     if (!multi()) check(pbf_set_collider(ctx_, nullptr), "pbf_set_collider");
     return *this;
   }
+  // Moving colliders (pbf_set_collider_pose; no reference counterpart): the installed lattice is read in a body frame, a world
+  // point being w = rot b + trans (rot row-major, body -> world).  No upload, no synchronisation and no recapture per call;
+  // persists until it is changed, clearColliderPose() or a new collider.  A single-device feature, like setCollider.
+  Solver &setColliderPose(const std::array<double, 9> &rot, const std::array<double, 3> &trans) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_collider_pose pose{};
+    for (size_t k = 0; k < 9; ++k) pose.rot[k] = rot[k];
+    for (size_t k = 0; k < 3; ++k) pose.trans[k] = trans[k];
+    check(pbf_set_collider_pose(ctx_, &pose), "pbf_set_collider_pose");
+    return *this;
+  }
+  Solver &clearColliderPose() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_pose(ctx_, nullptr), "pbf_set_collider_pose");
+    return *this;
+  }
+  // The reaction (pbf_set_collider_reaction / pbf_collider_reaction): what the collider gave the fluid in the last step, raw
+  // sums — the body received the negatives.
+  Solver &enableColliderReaction(bool on = true) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_reaction(ctx_, on ? 1 : 0), "pbf_set_collider_reaction");
+    return *this;
+  }
+  pbf_collider_wrench colliderReaction() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_collider_wrench w{};
+    check(pbf_collider_reaction(ctx_, &w), "pbf_collider_reaction");
+    return w;
+  }
 
   // ---- device-resident path -------------------------------------------------------------------
   // Several devices: `config` places the cuts (its bounds and scale define the grid columns); the slabs start with
