@@ -174,7 +174,8 @@ int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const 
  * placement, so a paddle, a piston or a gate moves with one call per frame instead of a lattice upload.  The pose persists
  * until it is changed and applies to every later pbf_stage_delta, pbf_step and pbf_steps (hipGraph replays included) and
  * to pbf_collider_sample, which stays the window onto the very function delta-p runs.  Within one pbf_steps(count) call
- * the pose is constant.  pose == NULL returns to the static collider.  pbf_set_collider and pbf_set_collider_mesh,
+ * the pose is constant, unless a body is on (pbf_set_collider_body below): then every step ends by writing the pose of the
+ * next.  pose == NULL returns to the static collider.  pbf_set_collider and pbf_set_collider_mesh,
  * clearing included, reset the pose to "none".
  *
  * The call does not synchronise and uploads no lattice: the ctx keeps one record {N(R), N(t)} on the device, and the call
@@ -246,6 +247,80 @@ typedef struct pbf_collider_wrench {
   uint64_t step;          /* serial of the step the record belongs to: steps run since the reaction was enabled */
 } pbf_collider_wrench;
 int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);
+
+/* Floating bodies: the collider's rigid body integrated on the device (no reference counterpart) — the first half of the
+ * coupling whose other half is the reaction above.  Opt-in: a ctx that never calls pbf_set_collider_body launches what it
+ * always did.
+ *
+ * With a body on, every step (pbf_step, every step of pbf_steps, hipGraph replays included) runs one more stage after its
+ * delta-p iterations and before finalise: the reaction records are summed by the reduction of pbf_collider_reaction (the
+ * same partial kernel and the same fold, so the sums are the bytes that call would return for the step), and one workgroup
+ * advances the body and writes the pose record the posed delta-p kernels read through a pointer.  There is no host
+ * read-back in a step and no new kernel argument that changes per step: the step is captured once and replayed, and
+ * pbf_steps(ctx, p, 200) runs 200 two-way coupled steps.  With iteration == 0 the records are the sort's zeros and the
+ * body moves under accel alone.  A step that returns early because the particles are depleted does not advance the body.
+ *
+ * The contract (csrc/pbf_collider_body.hpp, plain C++ shared by the kernel and a stand-alone host program).  Everything is
+ * in double whatever the ctx's N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it.  State: x
+ * (centre of mass, world units; the pose's t — the body frame's origin is the centre of mass), q (unit quaternion w, x, y,
+ * z, body -> world), v (world units per time), w (angular velocity, world frame, rad per time).  The body's principal axes
+ * are the lattice's axes.  One advance takes dt = pbf_params.dt and the step's raw sums P, L (pbf_collider_wrench.impulse
+ * and .angular; L about the t the step's delta-p launches read):
+ *   R      = R(q)                     (each entry written out in csrc/pbf_collider_body.hpp)
+ *   J_a    = -(gain * P_a) / dt       H_a = -(gain * L_a) / dt
+ *            one non-finite J or H: all six count as zero for this step and `rejected` goes up by one
+ *   v'_a   = ((v_a + dt * accel_a) + J_a / mass) * linear_factor_a / (1 + dt * linear_damping)
+ *   h      = R^T H ;  k_b = h_b / inertia_b ;  w'_a = ((w_a + (R k)_a) * angular_factor_a) / (1 + dt * angular_damping)
+ *   x'_a   = x_a + dt * v'_a ;  x'_a < centre_min_a or > centre_max_a: x'_a = that bound, v'_a = 0
+ *   q'     = (q + (dt / 2) * (0, w') (x) q) / |q + (dt / 2) * (0, w') (x) q|
+ *   pose   = { N(R(q')), N(x') }      steps += 1
+ * gain is the caller's: finalise gives a particle displaced by delta the velocity change 0.49 * delta / dt (the reference's
+ * damping of the position-derived velocity), so with gain = 0.49 the body receives exactly the momentum the fluid was
+ * given; gain = 1 is the plain position-based estimate.  The factors are 0 or 1 per world axis (a hinge, a slider, a body
+ * that only heaves); the centre bounds may be +-inf.
+ *
+ * pbf_set_collider_body needs an installed collider (PBF_ERR_STATE otherwise, and in the slab cases pbf_set_collider
+ * refuses).  It turns the reaction records on if they are off (the allocation of pbf_set_collider_reaction(ctx, 1); nothing
+ * is allocated inside a step) and writes parameters, state and start pose into one small device record with a one-lane
+ * kernel on the ctx's stream that receives them by value: the call itself does not synchronise.  The start pose is kept as
+ * given, so the first step reads what pbf_set_collider_pose would have left.  Going off -> on or on -> off selects another
+ * launch sequence and drops the captured graphs, as pbf_set_collider does; a call while a body is on re-places the body or
+ * changes its parameters (the counters start again), changes no key and drops no graph.  body == NULL turns the body off:
+ * the solid stays where it is, as an ordinary pose, and the reaction stays on.  While a body is on, pbf_set_collider_pose
+ * and pbf_set_collider_reaction(ctx, 0) return PBF_ERR_STATE (re-place the body through this call); pbf_set_collider and
+ * pbf_set_collider_mesh, clearing included, turn the body off, since they reset the pose.
+ *
+ * PBF_ERR_INVALID, each with its reason, leaving everything unchanged: a non-finite parameter or start velocity (the centre
+ * bounds may be infinite); mass <= 0; an inertia <= 0; gain < 0; a damping < 0; a factor other than 0 or 1; centre_min >
+ * centre_max; a start pose pbf_set_collider_pose would refuse.
+ *
+ * Limitations: one body per ctx; no contact of the body with the box or with obstacles beyond the centre bounds; no swept
+ * collision (a body that moves further per step than its own thickness can pass through fluid); no friction; no gyroscopic
+ * term (a spinning asymmetric body does not precess); not in slab mode; whitewater and the observers still do not see the
+ * solid. */
+typedef struct pbf_collider_body {
+  double mass, inertia[3];                 /* principal moments about the centre of mass, along the lattice's axes */
+  double gain;                             /* 0.49: the momentum finalise gave the fluid; 1: the position-based estimate */
+  double linear_damping, angular_damping;  /* >= 0, per time */
+  double accel[3];                         /* world units per time squared (gravity) */
+  double linear_factor[3], angular_factor[3];   /* 0 or 1 per world axis */
+  double centre_min[3], centre_max[3];     /* bounds of the centre of mass, world; may be -inf / +inf */
+  pbf_collider_pose pose;                  /* the start pose; trans is the centre of mass */
+  double velocity[3], angular_velocity[3];
+} pbf_collider_body;
+/* (the struct shares its name with the call that fills it, so it has no typedef: write `struct pbf_collider_body_state`) */
+struct pbf_collider_body_state {
+  pbf_collider_pose pose;                  /* R(q) and x in double; the kernels read it rounded to N */
+  double quat[4], velocity[3], angular_velocity[3];
+  double impulse[3], angular[3];           /* the sums the last advance consumed: P and L of that step */
+  uint64_t hits;                           /* and its hit count */
+  uint64_t steps;                          /* advances since the body was set */
+  uint64_t rejected;                       /* of which ignored their sums (a non-finite impulse) */
+};
+int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body);   /* NULL: off */
+/* an observer between steps, like pbf_collider_reaction: it synchronises (a polled mailbox), is part of no step and changes
+ * nothing a step reads.  PBF_ERR_STATE without a body. */
+int pbf_collider_body_state(pbf_ctx *ctx, struct pbf_collider_body_state *out);
 
 /* Mesh colliders: the signed-distance lattice of a closed triangle mesh, built on the device (no reference counterpart).
  * Opt-in; neither call is part of a step and both synchronise.  Without a call to them every launch of a step is unchanged.
@@ -371,6 +446,9 @@ int pbf_stage_diffuse(pbf_ctx *ctx, const pbf_params *params);  /* ompsph.hpp:18
 int pbf_stage_lambda(pbf_ctx *ctx, const pbf_params *params);   /* ompsph.hpp:217-232 */
 int pbf_stage_delta(pbf_ctx *ctx, const pbf_params *params);    /* ompsph.hpp:235-248 */
 int pbf_stage_finalise(pbf_ctx *ctx, const pbf_params *params); /* ompsph.hpp:256-264 */
+/* with a body on (pbf_set_collider_body): the body's advance alone, which pbf_step runs after its delta-p iterations and
+ * before finalise.  PBF_ERR_STATE without a body, or without a sort since the reaction records were enabled. */
+int pbf_stage_body(pbf_ctx *ctx, const pbf_params *params);
 
 /* ---- sources, drains and cell queries on resident state (the rest of sph::Scene, src/sph.hpp:56-79) -----------
  * What the reference does on the host at the top of advance() (src/omp/ompsph.hpp:93-118) runs here on the device,

@@ -16,6 +16,8 @@ from .capi import (  # noqa: F401
     BUF_COLLIDER_PUSH,
     BUF_DENSITY,
     BUF_WHITEWATER,
+    ColliderBody,
+    ColliderBodyState,
     ColliderPose,
     ColliderSdf,
     ColliderWrench,
@@ -43,6 +45,7 @@ from .capi import (  # noqa: F401
     Whitewater,
     WhitewaterStats,
     apply_motion,
+    collider_body,
     build,
     default_params,
     lib,

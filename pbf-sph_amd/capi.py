@@ -179,6 +179,41 @@ class ColliderWrench(C.Structure):
         return d
 
 
+class ColliderBody(C.Structure):
+    """pbf_collider_body (include/pbf_hip.h)"""
+    _fields_ = [("mass", C.c_double), ("inertia", C.c_double * 3), ("gain", C.c_double), ("linear_damping", C.c_double),
+                ("angular_damping", C.c_double), ("accel", C.c_double * 3), ("linear_factor", C.c_double * 3),
+                ("angular_factor", C.c_double * 3), ("centre_min", C.c_double * 3), ("centre_max", C.c_double * 3),
+                ("pose", ColliderPose), ("velocity", C.c_double * 3), ("angular_velocity", C.c_double * 3)]
+
+
+class ColliderBodyState(C.Structure):
+    """struct pbf_collider_body_state (include/pbf_hip.h)"""
+    _fields_ = [("pose", ColliderPose), ("quat", C.c_double * 4), ("velocity", C.c_double * 3), ("angular_velocity", C.c_double * 3),
+                ("impulse", C.c_double * 3), ("angular", C.c_double * 3), ("hits", C.c_uint64), ("steps", C.c_uint64),
+                ("rejected", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: np.array(getattr(self, k)) for k in ("quat", "velocity", "angular_velocity", "impulse", "angular")}
+        d.update(rot=np.array(self.pose.rot).reshape(3, 3), centre=np.array(self.pose.trans), hits=int(self.hits),
+                 steps=int(self.steps), rejected=int(self.rejected))
+        return d
+
+
+def collider_body(mass, inertia=(1.0, 1.0, 1.0), rot=np.eye(3), centre=(0.0, 0.0, 0.0), velocity=(0.0, 0.0, 0.0),
+                  angular_velocity=(0.0, 0.0, 0.0), gain=0.49, accel=(0.0, 0.0, 0.0), linear_damping=0.0, angular_damping=0.0,
+                  linear_factor=(1.0, 1.0, 1.0), angular_factor=(1.0, 1.0, 1.0), centre_min=(-np.inf,) * 3, centre_max=(np.inf,) * 3):
+    """-> a filled ColliderBody (the arguments of Solver.set_collider_body)"""
+    b = ColliderBody()
+    b.mass, b.gain, b.linear_damping, b.angular_damping = float(mass), float(gain), float(linear_damping), float(angular_damping)
+    for name, v in (("inertia", inertia), ("accel", accel), ("linear_factor", linear_factor), ("angular_factor", angular_factor),
+                    ("centre_min", centre_min), ("centre_max", centre_max), ("velocity", velocity), ("angular_velocity", angular_velocity)):
+        getattr(b, name)[:] = [float(x) for x in np.asarray(v, np.float64).reshape(3)]
+    b.pose.rot[:] = [float(x) for x in np.asarray(rot, np.float64).reshape(9)]
+    b.pose.trans[:] = [float(x) for x in np.asarray(centre, np.float64).reshape(3)]
+    return b
+
+
 class Mesh(C.Structure):
     """pbf_mesh (include/pbf_hip.h)"""
     _fields_ = [("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
@@ -226,6 +261,9 @@ _SIGS = {
     "pbf_set_collider_pose": (C.c_int, [C.c_void_p, C.POINTER(ColliderPose)]),
     "pbf_set_collider_reaction": (C.c_int, [C.c_void_p, C.c_int]),
     "pbf_collider_reaction": (C.c_int, [C.c_void_p, C.POINTER(ColliderWrench)]),
+    "pbf_set_collider_body": (C.c_int, [C.c_void_p, C.POINTER(ColliderBody)]),
+    "pbf_collider_body_state": (C.c_int, [C.c_void_p, C.POINTER(ColliderBodyState)]),
+    "pbf_stage_body": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
     "pbf_mesh_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
     "pbf_sdf_from_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.c_void_p, C.POINTER(MeshSdfStats)]),
     "pbf_set_collider_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
@@ -577,6 +615,30 @@ class Solver:
         w = ColliderWrench()
         self._chk(self.L.pbf_collider_reaction(self.ctx, C.byref(w)), "pbf_collider_reaction")
         return w if raw else w.as_dict()
+
+    def set_collider_body(self, mass=None, inertia=(1.0, 1.0, 1.0), rot=np.eye(3), centre=(0.0, 0.0, 0.0), velocity=(0.0, 0.0, 0.0),
+                          angular_velocity=(0.0, 0.0, 0.0), gain=0.49, accel=(0.0, 0.0, 0.0), linear_damping=0.0, angular_damping=0.0,
+                          linear_factor=(1.0, 1.0, 1.0), angular_factor=(1.0, 1.0, 1.0), centre_min=(-np.inf,) * 3, centre_max=(np.inf,) * 3):
+        """The installed collider as a rigid body the fluid moves (pbf_set_collider_body, include/pbf_hip.h): every later step
+        sums the reaction, advances the body and writes the pose of the next step on the device, pbf_steps and graph replays
+        included.  rot / centre: the start pose (the body frame's origin is the centre of mass); inertia: the principal
+        moments along the lattice's axes; gain 0.49 = the momentum finalise gave the fluid.  mass=None turns the body off
+        (the solid stays where it is).  Calling it again re-places the body without a recapture."""
+        if mass is None:
+            self._chk(self.L.pbf_set_collider_body(self.ctx, None), "pbf_set_collider_body")
+            return self
+        self._chk(self.L.pbf_set_collider_body(self.ctx, C.byref(collider_body(
+            mass, inertia, rot, centre, velocity, angular_velocity, gain, accel, linear_damping, angular_damping, linear_factor,
+            angular_factor, centre_min, centre_max))), "pbf_set_collider_body")
+        return self
+
+    def collider_body_state(self, raw=False):
+        """The body's state between steps (pbf_collider_body_state; it synchronises) -> dict(rot (3, 3), centre, quat (w, x, y,
+        z), velocity, angular_velocity, impulse and angular — the sums the last advance consumed —, hits, steps, rejected);
+        raw: the ColliderBodyState itself."""
+        st = ColliderBodyState()
+        self._chk(self.L.pbf_collider_body_state(self.ctx, C.byref(st)), "pbf_collider_body_state")
+        return st if raw else st.as_dict()
 
     def collider_push(self):
         """(n, 8): {A.xyz, hits, B.xyz, 0} per particle, the order of pstar() (PBF_BUF_COLLIDER_PUSH)"""

@@ -238,6 +238,12 @@ struct pbf_ctx {
   Mailbox<WrenchRecord> hostWrench;
   uint64_t pushAt = 0;
   int pushRows = -1;
+  // pbf_set_collider_body: the one colliderbody::Record on the device (parameters and state; allocated by the first call)
+  // and whether a body is on.  On <-> off bumps colliderGen (another launch sequence); re-placing the body changes nothing
+  // here.  A body implies reactionOn and colliderPosed.
+  DevBuf bodyRec;
+  bool bodyOn = false;
+  Mailbox<BodyStateRecord> hostBody;
   // "sdf_cull": pbf_sdf_from_mesh / pbf_set_collider_mesh skip the triangles out of a brick's reach (same bytes, 5 - 7 x faster)
   bool sdfCull = true;
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
@@ -1356,6 +1362,22 @@ template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
   return PBF_OK;
 }
 
+// pbf_set_collider_body's stage, after the delta-p iterations and before finalise: the reaction records summed by the
+// observer's partial kernel (indexed as collider_reaction_impl chooses) and ONE workgroup that folds the partial records,
+// advances the body and writes the pose of the next step.  No read-back, nothing allocated; captured with the step.
+template <typename N> int stage_body(pbf_ctx *ctx, const pbf_params *p) {
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (!record_current(ctx, ctx->pushAt)) return fail(ctx, PBF_ERR_STATE, "the collider body needs a sort since the reaction records were enabled");
+  const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
+  hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(),
+                     ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[ctx->st.cur].as<const vec4<N>>(),
+                     ctx->pushPartials.as<WrenchPartial>());
+  hipLaunchKernelGGL((k_body_advance<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->pushPartials.as<const WrenchPartial>(),
+                     double(p->dt), ctx->bodyRec.as<colliderbody::Record>(), ctx->colliderPose.as<ColliderPose<N>>());
+  LAUNCH_CHECK(ctx);
+  return PBF_OK;
+}
+
 template <typename N> int step_impl(pbf_ctx *ctx, const pbf_params *p) {
   if (scene_on(ctx))  // ompsph.hpp:93-118, before the "depleted" test as there: a source refills an empty state
     if (int rc = stage_scene<N>(ctx, p)) return rc;
@@ -1373,6 +1395,8 @@ template <typename N> int step_impl(pbf_ctx *ctx, const pbf_params *p) {
     if (int rc = stage_lambda<N>(ctx, p, fuse && it == 0)) return rc;
     if (int rc = stage_delta<N>(ctx, p)) return rc;
   }
+  if (ctx->bodyOn)  // (pbf_set_collider_body: the step's reaction moves the solid before the next step reads its pose)
+    if (int rc = stage_body<N>(ctx, p)) return rc;
   if (int rc = stage_finalise<N>(ctx, p)) return rc;
   return join_diffuse(ctx);  // the step is complete on ctx->stream only once the colours are
 }
@@ -1959,6 +1983,12 @@ int pbf_stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = check(ctx, p, true)) return rc;
   return DISPATCH(ctx, stage_finalise, ctx, p);
 }
+int pbf_stage_body(pbf_ctx *ctx, const pbf_params *p) {
+  if (int rc = check(ctx, p, false)) return rc;
+  if (!ctx->bodyOn) return fail(ctx, PBF_ERR_STATE, "pbf_stage_body: no body set (pbf_set_collider_body)");
+  if (ctx->n == 0) return PBF_OK;  // (a depleted step does not advance the body)
+  return DISPATCH(ctx, stage_body, ctx, p);
+}
 int pbf_stage_scene(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = check(ctx, p, false)) return rc;
   if (int rc = drop_ghosts(ctx)) return rc;
@@ -2460,6 +2490,7 @@ int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
   if (int rc = collider_drop_graphs(ctx)) return rc;
   ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
   ctx->colliderPosed = false;           // (a new solid starts without a pose)
+  ctx->bodyOn = false;                  // (and without a body)
   if (int rc = collider_pose_identity(ctx)) return rc;
   for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
   ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
@@ -2516,6 +2547,9 @@ int mesh_sdf_run(pbf_ctx *ctx, const char *who, const pbf_mesh *mesh, const pbf_
                    : mesh_sdf_impl<float>(ctx, mesh, lat, flags, *nodes, fresh, stats);
 }
 // pbf_collider_reaction: the two launches of the sum and the polled read-back, as diagnostics_impl
+static_assert(sizeof(struct pbf_collider_body_state) == 31 * 8 && offsetof(BodyStateRecord, seq) == sizeof(struct pbf_collider_body_state) &&
+                  sizeof(colliderbody::Record) == (22 + 31) * 8,
+              "the body record is doubles and 64-bit counters throughout (k_body_read copies it in 64-bit words)");
 static_assert(sizeof(pbf_collider_wrench) == 15 * 8 && offsetof(WrenchRecord, seq) == sizeof(pbf_collider_wrench) &&
                   offsetof(pbf_collider_wrench, hits) == offsetof(WrenchRecord, hits) &&
                   offsetof(pbf_collider_wrench, step) == offsetof(WrenchRecord, step),
@@ -2589,6 +2623,8 @@ int pbf_set_collider_pose(pbf_ctx *ctx, const pbf_collider_pose *pose) {
   }
   if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_pose: no collider set (pbf_set_collider)");
   if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (ctx->bodyOn)
+    return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_pose: a body is on and owns the pose (re-place it through pbf_set_collider_body)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!pose) {  // back to the static kernels
     if (!ctx->colliderPosed) return PBF_OK;
@@ -2611,6 +2647,8 @@ int pbf_set_collider_reaction(pbf_ctx *ctx, int on) {
     return fail(ctx, PBF_ERR_STATE, "the collider reaction is not supported in slab mode");
   const bool want = on != 0;
   if (want == ctx->reactionOn) return PBF_OK;
+  if (!want && ctx->bodyOn)
+    return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a body is on and needs the records (pbf_set_collider_body(ctx, NULL) first)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (want) {
     ctx->reactionOn = true;
@@ -2639,6 +2677,52 @@ int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out) {
     return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: no step since the reaction was enabled or the arrays last changed");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return ctx->fp64 ? collider_reaction_impl<double>(ctx, out) : collider_reaction_impl<float>(ctx, out);
+}
+
+int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (body) {
+    const char *why = nullptr;
+    if (colliderbody::check(body, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  }
+  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_body: no collider set (pbf_set_collider)");
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!body) {  // off: the solid stays where it is, as an ordinary pose; the reaction stays on
+    if (!ctx->bodyOn) return PBF_OK;
+    if (int rc = collider_drop_graphs(ctx)) return rc;
+    ctx->bodyOn = false;
+    return PBF_OK;
+  }
+  if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;  // (a no-op when it is on already)
+  if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
+  if (int rc = ensure(ctx, ctx->bodyRec, sizeof(colliderbody::Record))) return rc;
+  HIPCHK(ctx, ctx->hostBody.rec.ensure(1));  // (so that the observer allocates nothing either)
+  const colliderbody::Record rec = colliderbody::record_of(*body);
+  if (ctx->fp64)
+    hipLaunchKernelGGL((k_body_store<double>), dim3(1), dim3(1), 0, ctx->stream, rec, ctx->bodyRec.as<colliderbody::Record>(),
+                       ctx->colliderPose.as<ColliderPose<double>>());
+  else
+    hipLaunchKernelGGL((k_body_store<float>), dim3(1), dim3(1), 0, ctx->stream, rec, ctx->bodyRec.as<colliderbody::Record>(),
+                       ctx->colliderPose.as<ColliderPose<float>>());
+  LAUNCH_CHECK(ctx);
+  if (!ctx->bodyOn) {  // off -> on selects another launch sequence; a re-placed body changes no key and drops no graph
+    if (int rc = collider_drop_graphs(ctx)) return rc;
+    ctx->bodyOn = true, ctx->colliderPosed = true;
+  }
+  return PBF_OK;
+}
+
+int pbf_collider_body_state(pbf_ctx *ctx, struct pbf_collider_body_state *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_body_state: out == NULL");
+  if (!ctx->bodyOn) return fail(ctx, PBF_ERR_STATE, "pbf_collider_body_state: no body set (pbf_set_collider_body)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t seq;
+  HIPCHK(ctx, ctx->hostBody.arm(seq));
+  hipLaunchKernelGGL(k_body_read, dim3(1), dim3(1), 0, ctx->stream, ctx->bodyRec.as<const colliderbody::Record>(), ctx->hostBody.rec.p, seq);
+  LAUNCH_CHECK(ctx);
+  return receive(ctx, ctx->hostBody, "collider body read-back", *out);
 }
 
 int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records, pbf_mesh_info *info) {

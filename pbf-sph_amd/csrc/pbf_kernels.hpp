@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "pbf_collider.hpp"
+#include "pbf_collider_body.hpp"
 #include "pbf_common.hpp"
 
 namespace pbf {
@@ -3347,6 +3348,20 @@ __global__ __launch_bounds__(BLOCK) void k_wrench_partial(uint32_t n, const vec4
   wrench_block_fold(a, waves);
   if (threadIdx.x == 0) partials[blockIdx.x] = a;
 }
+// the fold of the partial records by ONE workgroup, shared by the two kernels that end the sum (k_wrench_final for the
+// observer, k_body_advance inside a step): BLOCK records at a time in index order, so both deliver the same bytes.  Thread 0
+// alone holds the result in t.
+__device__ inline void wrench_fold_partials(uint32_t nb, const WrenchPartial *__restrict__ partials, WrenchPartial *waves, WrenchPartial &t) {
+  wrench_identity(t);
+  for (uint32_t base = 0; base < nb; base += BLOCK) {
+    const uint32_t i = base + threadIdx.x;
+    WrenchPartial p;
+    if (i < nb) p = partials[i];
+    else wrench_identity(p);
+    wrench_block_fold(p, waves);
+    wrench_fold(t, p);  // (thread 0's is the one that counts)
+  }
+}
 // the device's image of pbf_collider_wrench (include/pbf_hip.h; pbf_hip.hip asserts that the two agree) + the polled word
 struct WrenchRecord {
   double impulse[3], angular[3], abs_impulse[3], abs_angular[3];
@@ -3358,21 +3373,54 @@ __global__ __launch_bounds__(BLOCK) void k_wrench_final(uint32_t nb, const Wrenc
                                                         uint32_t seq) {
   __shared__ WrenchPartial waves[BLOCK / 64];
   WrenchPartial t;
-  wrench_identity(t);
-  for (uint32_t base = 0; base < nb; base += BLOCK) {  // BLOCK records at a time in index order
-    const uint32_t i = base + threadIdx.x;
-    WrenchPartial p;
-    if (i < nb) p = partials[i];
-    else wrench_identity(p);
-    wrench_block_fold(p, waves);
-    wrench_fold(t, p);  // (thread 0's is the one that counts)
-  }
+  wrench_fold_partials(nb, partials, waves, t);
   if (threadIdx.x != 0) return;
   for (int k = 0; k < 3; ++k) {
     host->impulse[k] = t.sum[k], host->angular[k] = t.sum[3 + k];
     host->abs_impulse[k] = t.sum[6 + k], host->abs_angular[k] = t.sum[9 + k];
   }
   host->hits = t.cnt[0], host->particles = t.cnt[1], host->step = ctl[0];
+  __threadfence_system();
+  host->seq = seq;
+  __threadfence_system();
+}
+
+// ---- pbf_set_collider_body: the collider's rigid body, advanced inside the step (csrc/pbf_collider_body.hpp) -------------
+// pbf_set_collider_body: one lane writes the ctx's body record and the pose record of the first step, in stream order with
+// the steps before and after it.  Both arrive by value, as in k_collider_pose_store.
+template <typename N> __global__ void k_body_store(colliderbody::Record v, colliderbody::Record *dst, ColliderPose<N> *pose) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  *dst = v;
+  for (int k = 0; k < 9; ++k) pose->rot[k] = N(v.st.pose.rot[k]);
+  for (int k = 0; k < 3; ++k) pose->trans[k] = N(v.st.pose.trans[k]);
+}
+// The end of the step's sum and the body's advance: ONE workgroup folds the partial records of k_wrench_partial with the
+// observer's fold, then thread 0 runs colliderbody::advance in double and stores the body record and the pose of the next
+// step with ordinary stores.  The delta-p launches of this step have read the old pose; those of the next come after this
+// kernel in the stream.  dt arrives as an argument: it is part of a captured step's key.
+template <typename N>
+__global__ __launch_bounds__(BLOCK) void k_body_advance(uint32_t nb, const WrenchPartial *__restrict__ partials, double dt,
+                                                        colliderbody::Record *body, ColliderPose<N> *pose) {
+  __shared__ WrenchPartial waves[BLOCK / 64];
+  WrenchPartial t;
+  wrench_fold_partials(nb, partials, waves, t);
+  if (threadIdx.x != 0) return;
+  colliderbody::Record r = *body;
+  colliderbody::advance(r.par, r.st, dt, &t.sum[0], &t.sum[3], t.cnt[0]);
+  body->st = r.st;
+  for (int k = 0; k < 9; ++k) pose->rot[k] = N(r.st.pose.rot[k]);
+  for (int k = 0; k < 3; ++k) pose->trans[k] = N(r.st.pose.trans[k]);
+}
+// struct pbf_collider_body_state: the state into the pinned record the host polls
+struct BodyStateRecord {
+  struct pbf_collider_body_state st;
+  uint32_t seq;
+};
+__global__ void k_body_read(const colliderbody::Record *body, volatile BodyStateRecord *host, uint32_t seq) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const unsigned long long *src = reinterpret_cast<const unsigned long long *>(&body->st);
+  volatile unsigned long long *dst = reinterpret_cast<volatile unsigned long long *>(&host->st);
+  for (uint32_t k = 0; k < sizeof(struct pbf_collider_body_state) / 8; ++k) dst[k] = src[k];
   __threadfence_system();
   host->seq = seq;
   __threadfence_system();

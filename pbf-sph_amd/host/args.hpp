@@ -48,6 +48,11 @@ struct Args {
   bool colliderMoves = false;
   double colliderMotion[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   size_t colliderReaction = 0;            // 0 = off
+  // --collider-body=mass[,Ixx,Iyy,Izz[,gain]] with --resident and --collider=sphere|bowl|plane: the solid is a rigid body the
+  // fluid moves (pbf_set_collider_body); --collider-body-report[=every] prints its state
+  bool colliderBody = false;
+  double colliderBodyCfg[5] = {0, 0, 0, 0, 0.49};   // mass, the principal moments (0 = a solid ball of the collider's radius), gain
+  size_t colliderBodyReport = 0;          // 0 = off
   double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
   size_t wwCapacity = 0;                  // 0 = off
   bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
@@ -121,6 +126,13 @@ struct Args {
           "                                        than its thickness can pass through fluid\n"
           "      --collider-reaction[=every]       With --resident and --collider: one JSON line per `every` frames with the impulse\n"
           "                                        and angular impulse the collider gave the fluid in that frame\n"
+          "      --collider-body=[mass[,Ixx,Iyy,Izz[,gain]]]  With --resident and --collider=sphere|bowl|plane: the solid floats — a\n"
+          "                                        rigid body integrated on the device inside every step from the reaction of\n"
+          "                                        the fluid, starting at rest at the collider's centre (a plane: the box's)\n"
+          "                                        under the fluid's own acceleration, its centre kept inside the box. Moments\n"
+          "                                        about the lattice's axes (default: a solid ball of the sphere's radius);\n"
+          "                                        gain 0.49 (default) returns the momentum the fluid was given\n"
+          "      --collider-body-report[=every]    One JSON line per `every` frames with the body's state\n"
           "      --whitewater=[k_ta,k_wc[,capacity]]  With --resident: spray, foam and air bubbles after Ihmsen et al. 2012,\n"
           "                                        one whitewater step after every frame at these rates; the tau ranges are\n"
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
@@ -244,6 +256,21 @@ struct Args {
             if (!std::isfinite(x)) throw std::runtime_error("--collider-motion: the values must be finite");
           colliderMoves = true;
           for (size_t k = 0; k < f.size(); ++k) colliderMotion[k] = f[k];
+        }
+        else if (a == "--collider-body-report") colliderBodyReport = 1;
+        else if (a.rfind("--collider-body-report=", 0) == 0) {
+          colliderBodyReport = std::stoull(a.substr(23));
+          if (colliderBodyReport == 0) throw std::runtime_error("--collider-body-report: every must be >= 1");
+        }
+        else if (value(i, a, "", "--collider-body", v)) {
+          const auto f = numbers(v);
+          if (f.size() != 1 && f.size() != 4 && f.size() != 5) throw std::runtime_error("--collider-body: expected mass[,Ixx,Iyy,Izz[,gain]]");
+          for (double x : f)
+            if (!std::isfinite(x)) throw std::runtime_error("--collider-body: the values must be finite");
+          if (!(f[0] > 0) || (f.size() >= 4 && !(f[1] > 0 && f[2] > 0 && f[3] > 0)) || (f.size() == 5 && f[4] < 0))
+            throw std::runtime_error("--collider-body: mass and moments must be > 0, gain >= 0");
+          colliderBody = true;
+          for (size_t k = 0; k < f.size(); ++k) colliderBodyCfg[k] = f[k];
         }
         else if (a == "--collider-reaction") colliderReaction = 1;
         else if (a.rfind("--collider-reaction=", 0) == 0) {

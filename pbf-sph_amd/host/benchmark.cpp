@@ -127,6 +127,27 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   if ((args.colliderMoves || args.colliderReaction) && !(collider && args.resident))
     std::cout << "--collider-motion / --collider-reaction take effect with --resident and --collider: ignored" << std::endl;
   const bool colliderMoves = args.colliderMoves && collider && args.resident;
+  if ((args.colliderBody || args.colliderBodyReport) && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--collider-body / --collider-body-report are single-device features: they cannot be combined with --slabs / --all-devices"
+              << std::endl;
+    return 1;
+  }
+  if (args.colliderBody && args.colliderMoves) {
+    std::cerr << "--collider-body and --collider-motion both own the collider's pose: give one of them" << std::endl;
+    return 1;
+  }
+  if (args.colliderBody && collider && args.colliderShape == "mesh") {
+    std::cerr << "--collider-body needs --collider=sphere, bowl or plane (the lattice is built about the body's centre)" << std::endl;
+    return 1;
+  }
+  if (args.colliderBody && collider && args.colliderShape == "plane" && !(args.colliderBodyCfg[1] > 0)) {
+    std::cerr << "--collider-body with a plane needs its moments: mass,Ixx,Iyy,Izz" << std::endl;
+    return 1;
+  }
+  if ((args.colliderBody || args.colliderBodyReport) && !(collider && args.resident))
+    std::cout << "--collider-body / --collider-body-report take effect with --resident and --collider: ignored" << std::endl;
+  const bool colliderBody = args.colliderBody && collider && args.resident;
+  const size_t colliderBodyReport = colliderBody ? args.colliderBodyReport : 0;
   const size_t colliderReaction = collider && args.resident ? args.colliderReaction : 0;
   if (args.diagnostics && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--diagnostics is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
@@ -179,6 +200,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   sph::hip_impl::Solver<T, N> solver(N(0.1), devices, flags);
+  std::array<double, 3> bodyCentre{0, 0, 0}, bodyMin{0, 0, 0}, bodyMax{0, 0, 0};
   if (surfaceTension) solver.surfaceTension(N(args.cohesion), N(args.adhesion));
   if (collider && args.resident) {
     // the analytic distance on a lattice over the box plus one spacing (float64, rounded to N at the end)
@@ -191,6 +213,14 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       origin[size_t(a)] = lo[a] - spacing;
       dims[size_t(a)] = uint32_t(std::ceil((hi[a] - lo[a]) / spacing)) + 3u;
     }
+    // --collider-body: the lattice is the body's own frame, whose origin is the centre of mass — the sphere's centre, for a
+    // plane the box's; the start pose puts it back where the static collider would stand
+    if (colliderBody)
+      for (int a = 0; a < 3; ++a) {
+        bodyCentre[size_t(a)] = args.colliderShape == "plane" ? 0.5 * (lo[a] + hi[a]) : args.colliderCfg[a];
+        origin[size_t(a)] -= bodyCentre[size_t(a)];
+        bodyMin[size_t(a)] = lo[a], bodyMax[size_t(a)] = hi[a];
+      }
     if (args.colliderShape == "mesh") {
       const objmesh::Mesh mesh = objmesh::read(args.colliderMesh);
       pbf_mesh view{mesh.vertices.size() / 3, mesh.triangles.size() / 3, mesh.vertices.data(), mesh.triangles.data()};
@@ -214,7 +244,8 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     for (uint32_t i = 0; i < dims[0]; ++i)
       for (uint32_t j = 0; j < dims[1]; ++j)
         for (uint32_t k = 0; k < dims[2]; ++k) {
-          const double x = origin[0] + i * spacing, y = origin[1] + j * spacing, z = origin[2] + k * spacing;
+          const double x = (origin[0] + i * spacing) + bodyCentre[0], y = (origin[1] + j * spacing) + bodyCentre[1],
+                       z = (origin[2] + k * spacing) + bodyCentre[2];
           double d;
           if (args.colliderShape == "plane") d = (g[0] * x + g[1] * y + g[2] * z) / nl - g[3];
           else d = std::sqrt((x - g[0]) * (x - g[0]) + (y - g[1]) * (y - g[1]) + (z - g[2]) * (z - g[2])) - g[3];
@@ -226,6 +257,24 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     }
   }
   if (colliderReaction) solver.enableColliderReaction();
+  if (colliderBody) {
+    // at rest at the collider's centre under the fluid's own acceleration in world units (a unit mass gains constant_force *
+    // scale per time: predict works in solver units), its centre kept inside the box
+    pbf_collider_body body{};
+    const double *c = args.colliderBodyCfg, r = args.colliderCfg[3];
+    body.mass = c[0], body.gain = c[4];
+    const double force[3] = {double(param.constantForce.x), double(param.constantForce.y), double(param.constantForce.z)};
+    for (int a = 0; a < 3; ++a) {
+      body.inertia[a] = c[1] > 0 ? c[1 + a] : 0.4 * c[0] * r * r;
+      body.accel[a] = force[a] * double(param.scale);
+      body.linear_factor[a] = body.angular_factor[a] = 1.0;
+      body.centre_min[a] = bodyMin[size_t(a)], body.centre_max[a] = bodyMax[size_t(a)];
+      body.pose.rot[4 * a] = 1.0, body.pose.trans[a] = bodyCentre[size_t(a)];
+    }
+    solver.setColliderBody(body);
+    std::cout << "Collider body        : mass " << body.mass << ", moments " << body.inertia[0] << " " << body.inertia[1] << " " << body.inertia[2]
+              << ", gain " << body.gain << ", centre " << bodyCentre[0] << " " << bodyCentre[1] << " " << bodyCentre[2] << std::endl;
+  }
   // --collider-motion: the pose of the frame numbered f (warm-up frames included), at time f * dt — a rotation by |w| f dt about
   // the axis w through the pivot p (Rodrigues), then the translation v f dt: w = R (b - p) + p + v f dt
   size_t poseFrame = 0;
@@ -358,6 +407,26 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
               << ",\"particles\":" << w.particles << ",\"step\":" << w.step << "}}" << std::endl;
     diagMillis += duration_millis(hrc::now() - d0).count();
   };
+  // --collider-body-report: one JSON line per report, kept out of the timed frames like the wrench's
+  auto bodyReport = [&](size_t frame) {
+    const auto d0 = hrc::now();
+    const struct pbf_collider_body_state st = solver.colliderBody();
+    auto num = [](double x) {
+      char buf[40];
+      std::snprintf(buf, sizeof buf, "%.17g", x);
+      return std::isfinite(x) ? std::string(buf) : std::string("null");
+    };
+    auto vecn = [&](const double *v, int n) {
+      std::string out = "[";
+      for (int k = 0; k < n; ++k) out += (k ? "," : "") + num(v[k]);
+      return out + "]";
+    };
+    std::cout << "{\"frame\":" << frame << ",\"body\":{\"rot\":" << vecn(st.pose.rot, 9) << ",\"centre\":" << vecn(st.pose.trans, 3)
+              << ",\"quat\":" << vecn(st.quat, 4) << ",\"velocity\":" << vecn(st.velocity, 3) << ",\"angular_velocity\":"
+              << vecn(st.angular_velocity, 3) << ",\"impulse\":" << vecn(st.impulse, 3) << ",\"angular\":" << vecn(st.angular, 3)
+              << ",\"hits\":" << st.hits << ",\"steps\":" << st.steps << ",\"rejected\":" << st.rejected << "}}" << std::endl;
+    diagMillis += duration_millis(hrc::now() - d0).count();
+  };
   const bool probing = args.resident && !args.probes.empty();
   start = hrc::now();
   for (size_t frame = 0; frame < args.iterations; ++frame) {
@@ -371,6 +440,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     frameTime.push_back(duration_millis(hrc::now() - f0).count());
     if (args.resident && args.diagnostics && (frame + 1) % args.diagnostics == 0) report(frame);
     if (colliderReaction && solver.count() && (frame + 1) % colliderReaction == 0) wrench(frame);
+    if (colliderBodyReport && (frame + 1) % colliderBodyReport == 0) bodyReport(frame);
     if (probing && (args.probeEvery ? (frame + 1) % args.probeEvery == 0 : frame + 1 == args.iterations)) probe(frame);
   }
   end = hrc::now();

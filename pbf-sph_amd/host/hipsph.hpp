@@ -482,6 +482,26 @@ public:
     check(pbf_collider_reaction(ctx_, &w), "pbf_collider_reaction");
     return w;
   }
+  // Floating bodies (pbf_set_collider_body): the installed collider as a rigid body the fluid moves — every later step sums the
+  // reaction, advances the body and writes the next step's pose on the device, pbf_steps and graph replays included.  body.pose
+  // is the start pose (trans = the centre of mass).  Calling it again re-places the body without a recapture;
+  // clearColliderBody() leaves the solid where it is, as an ordinary pose.  colliderBody() synchronises.
+  Solver &setColliderBody(const pbf_collider_body &body) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_body(ctx_, &body), "pbf_set_collider_body");
+    return *this;
+  }
+  Solver &clearColliderBody() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_body(ctx_, nullptr), "pbf_set_collider_body");
+    return *this;
+  }
+  struct pbf_collider_body_state colliderBody() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    struct pbf_collider_body_state st {};
+    check(pbf_collider_body_state(ctx_, &st), "pbf_collider_body_state");
+    return st;
+  }
 
   // ---- device-resident path -------------------------------------------------------------------
   // Several devices: `config` places the cuts (its bounds and scale define the grid columns); the slabs start with
