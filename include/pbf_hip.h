@@ -144,10 +144,10 @@ int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion);
  * pStar is formed from q'.  Obstacles and ghost copies are never moved.  One projection runs per delta-p iteration; the K
  * iterations converge it.  Every gather path ("gather" 0 / 1 / 3, "row_major", "pipeline", "graph", PBF_FLAG_NO_LDS)
  * gives the same bytes; "coop" 2 / 4 / 8 differs at rounding level as it does without a collider.
- * Limitations: there is no friction or restitution term — finalise derives the velocity from the projected position, as it
- * does for the box.  Whitewater's diffuse particles and the observers (surface, sampling, diagnostics, anisotropy) do not
- * see the collider.  One static collider per ctx.  A triangle mesh becomes a lattice through pbf_sdf_from_mesh /
- * pbf_set_collider_mesh below.
+ * Limitations: there is no restitution term — finalise derives the velocity from the projected position, as it does for
+ * the box — and friction is an opt-in pass of its own (pbf_set_collider_friction below).  Whitewater's diffuse particles
+ * and the observers (surface, sampling, diagnostics, anisotropy) do not see the collider.  One static collider per ctx.  A
+ * triangle mesh becomes a lattice through pbf_sdf_from_mesh / pbf_set_collider_mesh below.
  *
  * pbf_collider_sample is the window onto that device function, for debugging an uploaded collider: its own synchronising
  * call, never part of a step.  For each point: round to N, q = point / scale in N, then exactly the function above with
@@ -201,10 +201,11 @@ int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const 
  *   q'_a = hit ? min(maxB_a / scale, max(minB_a / scale, w'_a / scale)) : q_a
  * A particle that does not hit keeps its bits; outside the lattice, NaN included, nothing is loaded.  The margin and the
  * spacing are lengths, so a rotation leaves them alone.  The box is the world's: the second clamp is not rotated.
- * Limitations: the wall is free-slip and pushes through positions; there is no contact velocity, friction or restitution,
- * and finalise derives the velocity from the projected position with the reference's damping.  There is no swept
- * collision: a body that moves further per step than its own thickness can pass through fluid.  One collider per ctx; no
- * pose across slabs; whitewater and the observers do not see the collider. */
+ * Limitations: the wall pushes through positions and is free-slip unless pbf_set_collider_friction (below) is on, which is
+ * also the only place the solid's contact velocity enters; there is no restitution, and finalise derives the velocity
+ * from the projected position with the reference's damping.  There is no swept collision: a body that moves further per
+ * step than its own thickness can pass through fluid.  One collider per ctx; no pose across slabs; whitewater and the
+ * observers do not see the collider. */
 typedef struct pbf_collider_pose {
   double rot[9];     /* row-major R, body -> world */
   double trans[3];   /* t, world */
@@ -295,7 +296,7 @@ int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);
  * centre_max; a start pose pbf_set_collider_pose would refuse.
  *
  * Limitations: one body per ctx; no contact of the body with the box or with obstacles beyond the centre bounds; no swept
- * collision (a body that moves further per step than its own thickness can pass through fluid); no friction; no gyroscopic
+ * collision (a body that moves further per step than its own thickness can pass through fluid); no restitution; no gyroscopic
  * term (a spinning asymmetric body does not precess); not in slab mode; whitewater and the observers still do not see the
  * solid. */
 typedef struct pbf_collider_body {
@@ -321,6 +322,69 @@ int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body);   /* NUL
 /* an observer between steps, like pbf_collider_reaction: it synchronises (a polled mailbox), is part of no step and changes
  * nothing a step reads.  PBF_ERR_STATE without a body. */
 int pbf_collider_body_state(pbf_ctx *ctx, struct pbf_collider_body_state *out);
+
+/* Collider friction: Coulomb drag against the collider, with the solid's contact velocity (no reference counterpart;
+ * Bridson's particle - level-set friction v_t' = max(0, 1 - mu dv_n / |v_t|) v_t).  Opt-in: a ctx that never calls
+ * pbf_set_collider_friction, or has cleared it, launches what it always did.
+ *
+ * With friction on, every step (pbf_step, every step of pbf_steps, hipGraph replays, pbf_stage_finalise) runs ONE streaming
+ * pass right after finalise and before vorticity, XSPH and surface tension, which therefore see the boundary-corrected
+ * velocity; pbf_steps does not fuse finalise(t) with predict(t + 1) then.  The pass reads the step's reaction records: A,
+ * the summed displacement the solid gave the particle over the iterations, is the contact normal and the normal impulse at
+ * once, so no lattice is read.  No host read-back, and no argument that changes per step: mu, V and W live in a small device
+ * record the pass reads through a pointer.
+ *
+ * The contract (csrc/pbf_collider_friction.hpp).  Everything per particle is in N, in the order written, not contracted;
+ * PBF_FLAG_FAST_MATH does not reach it.  vel4 is in the solver frame (world / scale); A, V, W and t are world.
+ *   V, W   = the call's velocity and angular_velocity, rounded to N; while a body is on: N(velocity), N(angular_velocity)
+ *            of the body's state as the pass finds them (after the step's advance)
+ *   t      = the pose record's trans as the pass finds it (no pose ever set: 0); mu rounded to N
+ *   particle a with the record A (obstacles keep a zero record and never act):
+ *   len  = sqrt((A_x A_x + A_y A_y) + A_z A_z)          act = A.w > 0 && len > 0
+ *   n_a  = A_a / len
+ *   r_a  = pos4[a]_a - t_a                               (the finalised world position)
+ *   c_x  = W_y r_z - W_z r_y   (y, z cyclic; each product rounded, one subtraction)
+ *   vb_a = (V_a + c_a) / scale
+ *   u_a  = v_a - vb_a          un = (u_x n_x + u_y n_y) + u_z n_z          ut_a = u_a - un * n_a
+ *   s    = sqrt((ut_x ut_x + ut_y ut_y) + ut_z ut_z)     slide = act && s > 0
+ *   jn   = (VD * (len / scale)) / dt                     VD = N(0.49f): the speed finalise gave the particle from the push
+ *   g    = (mu * jn) / s        f = g < 1 ? g : 1        (a NaN g counts as 1)        dv_a = -(f * ut_a)
+ *   v'_a = slide ? v_a + dv_a : v_a                      (bits kept otherwise; pos4, pStar, lambda untouched)
+ * A lane that does not act loads neither position nor velocity and stores nothing.
+ *
+ * The sum, with the reaction's fixed-shape reduction (no atomics, Morton order, terms formed in double):
+ *   p_a = m * (double(dv_a) * double(scale))     P = sum p     L = sum double(r) x p     and the sums of |term|
+ * pbf_collider_friction_reaction is an observer between steps like pbf_collider_reaction (it synchronises): the LAST pass's
+ * raw sums, impulses in world units x mass / time; the solid received -P and -L, L about t.  hits = particles that slid,
+ * particles = particles with act, step = passes run since friction was turned on.  PBF_ERR_STATE when friction is off, when
+ * no step has run since it was turned on, and in slab mode.
+ *
+ * With a body on as well, the body stage of step t + 1 first folds the sums of step t's pass and kicks the body (in double):
+ *   v_a += (-P_a / mass) * linear_factor_a
+ *   h = R(q)^T (-L) ;  k_b = h_b / inertia_b ;  w_a += (R(q) k)_a * angular_factor_a
+ * a non-finite P or L: no kick, `rejected` goes up by one.  Then it advances as without friction.  The body's x does not
+ * change in between, so L is about the right point.  Each pass's sums are consumed exactly once (a pending word on the
+ * device), whether the step is eager, batched or replayed, or pbf_stage_body runs alone.  The sums outlive an upload, also
+ * one that grows the capacity: the step after it hands them to the body.  pbf_set_collider_body while friction is on drops
+ * sums that are still pending: they were taken against another pose and other velocities, and the body as placed by the
+ * call starts with the velocities it was given (pbf_collider_friction_reaction still returns them).
+ *
+ * pbf_set_collider_friction needs an installed collider (PBF_ERR_STATE otherwise, and in the slab cases pbf_set_collider
+ * refuses); PBF_ERR_INVALID for mu <= 0 or NaN (+inf is no-slip) and for a non-finite velocity; a refusal changes nothing.
+ * It turns the reaction records on if they are off; while friction is on pbf_set_collider_reaction(ctx, 0) returns
+ * PBF_ERR_STATE.  Off <-> on selects another launch sequence and drops the captured graphs; a call while friction is on
+ * rewrites the device record with a one-lane kernel on the ctx's stream that receives it by value: no key changes, no graph
+ * is dropped, nothing synchronises.  pbf_set_collider and pbf_set_collider_mesh, clearing included, turn friction off.
+ *
+ * Limitations: one coefficient (no separate static and kinetic friction); no restitution; no friction against the box walls
+ * or obstacle particles; not in slab mode. */
+typedef struct pbf_collider_friction {
+  double mu;                   /* > 0; +inf = no-slip */
+  double velocity[3];          /* world units per time: the solid's velocity at t (ignored while a body is on) */
+  double angular_velocity[3];  /* rad per time, world frame, about the pose's t (ignored while a body is on) */
+} pbf_collider_friction;
+int pbf_set_collider_friction(pbf_ctx *ctx, const pbf_collider_friction *f);   /* NULL: off */
+int pbf_collider_friction_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);    /* observer between steps */
 
 /* Mesh colliders: the signed-distance lattice of a closed triangle mesh, built on the device (no reference counterpart).
  * Opt-in; neither call is part of a step and both synchronise.  Without a call to them every launch of a step is unchanged.

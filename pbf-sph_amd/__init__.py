@@ -18,6 +18,7 @@ from .capi import (  # noqa: F401
     BUF_WHITEWATER,
     ColliderBody,
     ColliderBodyState,
+    ColliderFriction,
     ColliderPose,
     ColliderSdf,
     ColliderWrench,

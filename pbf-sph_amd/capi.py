@@ -214,6 +214,11 @@ def collider_body(mass, inertia=(1.0, 1.0, 1.0), rot=np.eye(3), centre=(0.0, 0.0
     return b
 
 
+class ColliderFriction(C.Structure):
+    """pbf_collider_friction (include/pbf_hip.h)"""
+    _fields_ = [("mu", C.c_double), ("velocity", C.c_double * 3), ("angular_velocity", C.c_double * 3)]
+
+
 class Mesh(C.Structure):
     """pbf_mesh (include/pbf_hip.h)"""
     _fields_ = [("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64), ("vertices", C.c_void_p), ("triangles", C.c_void_p)]
@@ -264,6 +269,8 @@ _SIGS = {
     "pbf_set_collider_body": (C.c_int, [C.c_void_p, C.POINTER(ColliderBody)]),
     "pbf_collider_body_state": (C.c_int, [C.c_void_p, C.POINTER(ColliderBodyState)]),
     "pbf_stage_body": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
+    "pbf_set_collider_friction": (C.c_int, [C.c_void_p, C.POINTER(ColliderFriction)]),
+    "pbf_collider_friction_reaction": (C.c_int, [C.c_void_p, C.POINTER(ColliderWrench)]),
     "pbf_mesh_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
     "pbf_sdf_from_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.c_void_p, C.POINTER(MeshSdfStats)]),
     "pbf_set_collider_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
@@ -639,6 +646,29 @@ class Solver:
         st = ColliderBodyState()
         self._chk(self.L.pbf_collider_body_state(self.ctx, C.byref(st)), "pbf_collider_body_state")
         return st if raw else st.as_dict()
+
+    def set_collider_friction(self, mu=None, velocity=(0.0, 0.0, 0.0), angular_velocity=(0.0, 0.0, 0.0)):
+        """Coulomb friction against the installed collider (pbf_set_collider_friction, include/pbf_hip.h): one pass after every
+        finalise drags the tangential velocity of the particles the solid pushed towards the solid's contact velocity,
+        velocity + angular_velocity x (x - the pose's t) (a body's own while a body is on).  mu = inf is no-slip; mu=None turns
+        it off.  Calling it again rewrites the device record without a recapture."""
+        if mu is None:
+            self._chk(self.L.pbf_set_collider_friction(self.ctx, None), "pbf_set_collider_friction")
+            return self
+        f = ColliderFriction()
+        f.mu = float(mu)
+        f.velocity[:] = [float(x) for x in np.asarray(velocity, np.float64).reshape(3)]
+        f.angular_velocity[:] = [float(x) for x in np.asarray(angular_velocity, np.float64).reshape(3)]
+        self._chk(self.L.pbf_set_collider_friction(self.ctx, C.byref(f)), "pbf_set_collider_friction")
+        return self
+
+    def collider_friction_reaction(self, raw=False):
+        """The last friction pass's raw sums (pbf_collider_friction_reaction; it synchronises) -> the dict of collider_reaction():
+        impulse, angular (about the pose's t; the solid received their negatives), the sums of |term|, hits = particles that
+        slid, particles = particles in contact, step = passes since friction was turned on; raw: the ColliderWrench itself."""
+        w = ColliderWrench()
+        self._chk(self.L.pbf_collider_friction_reaction(self.ctx, C.byref(w)), "pbf_collider_friction_reaction")
+        return w if raw else w.as_dict()
 
     def collider_push(self):
         """(n, 8): {A.xyz, hits, B.xyz, 0} per particle, the order of pstar() (PBF_BUF_COLLIDER_PUSH)"""

@@ -22,8 +22,8 @@
 // g is the gradient of the trilinear interpolant in lattice units: the spacing is isotropic, so only its direction matters.
 // A particle that does not hit keeps its q bit for bit (a select).  The second clamp uses the images of the box under the
 // stock clamp, so the box always wins over the collider.  One projection runs per delta-p iteration; the K iterations
-// converge it.  There is no friction or restitution term: finalise derives the velocity from the projected position, as it
-// does for the box.
+// converge it.  There is no restitution term, and friction is a pass of its own (csrc/pbf_collider_friction.hpp): finalise
+// derives the velocity from the projected position, as it does for the box.
 //
 // With a pose (pbf_set_collider_pose; the same text as the header's) the lattice is read in a body frame, a world point
 // being w = R b + t.  Everything is in N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it.

@@ -33,8 +33,18 @@
 // with VD = 0.49 (the reference's damping of the position-derived velocity), so with gain = 0.49 the body receives exactly
 // the momentum the fluid was given; gain = 1 is the plain position-based estimate delta / dt.
 //
+// With friction on as well (pbf_set_collider_friction, csrc/pbf_collider_friction.hpp) the stage first hands the body the
+// raw sums P, L of the previous step's friction pass — impulses already, world units x mass / time, L about x — through
+// kick(), then advances as above:
+//
+//   R      = R(q)
+//   v_a    = v_a + (-P_a / mass) * linear_factor_a
+//   h_b    = (R[0][b] (-L_0) + R[1][b] (-L_1)) + R[2][b] (-L_2)         k_b = h_b / inertia_b
+//   w_a    = w_a + ((R[a][0] k_0 + R[a][1] k_1) + R[a][2] k_2) * angular_factor_a
+//            one non-finite P or L: no kick, and `rejected` goes up by one
+//
 // Limitations: there is no gyroscopic term (w x I w): a spinning asymmetric body does not precess.  No contact of the body
-// with the box or with obstacles beyond the bounds of its centre, no swept collision, no friction.
+// with the box or with obstacles beyond the bounds of its centre, no swept collision, no restitution.
 #pragma once
 
 #include <cstddef>
@@ -142,6 +152,23 @@ PBF_BODY_FN inline void advance(const Params &par, struct pbf_collider_body_stat
   for (int a = 0; a < 3; ++a) st.impulse[a] = P[a], st.angular[a] = L[a];
   st.hits = hits;
   st.steps += 1;
+}
+
+// the friction pass's sums P, L (about x) as one impulse on the body: the text of this file's head
+PBF_BODY_FN inline void kick(const Params &par, struct pbf_collider_body_state &st, const double *P, const double *L) {
+  double *v = st.velocity, *w = st.angular_velocity;
+  bool ok = true;
+  for (int a = 0; a < 3; ++a) ok = ok && finite(P[a]) && finite(L[a]);
+  if (!ok) {
+    st.rejected += 1;
+    return;
+  }
+  double R[9];
+  rotation_of(st.quat, R);
+  for (int a = 0; a < 3; ++a) v[a] = v[a] + (-P[a] / par.mass) * par.linear_factor[a];
+  double k[3];
+  for (int b = 0; b < 3; ++b) k[b] = ((R[b] * (-L[0]) + R[3 + b] * (-L[1])) + R[6 + b] * (-L[2])) / par.inertia[b];
+  for (int a = 0; a < 3; ++a) w[a] = w[a] + ((R[3 * a] * k[0] + R[3 * a + 1] * k[1]) + R[3 * a + 2] * k[2]) * par.angular_factor[a];
 }
 
 // the record pbf_set_collider_body writes: the parameters, the state at rest in its start pose (which is kept as given:

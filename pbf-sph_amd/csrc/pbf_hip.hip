@@ -30,6 +30,7 @@
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 #include "pbf_collider_pose.hpp"
+#include "pbf_collider_friction.hpp"
 
 using namespace pbf;
 
@@ -244,6 +245,13 @@ struct pbf_ctx {
   DevBuf bodyRec;
   bool bodyOn = false;
   Mailbox<BodyStateRecord> hostBody;
+  // pbf_set_collider_friction: the record {mu, V, W} the pass reads through a pointer, the device's counters, the pass's own
+  // partial records (they outlive the step: the observer and the next step's body stage fold them), whether friction is on
+  // and whether a pass has run since.  On <-> off bumps colliderGen; a rewritten record changes nothing here.  Friction
+  // implies reactionOn.
+  DevBuf frictionRec, frictionCtl, frictionPartials;
+  bool frictionOn = false, frictionRan = false;
+  Mailbox<WrenchRecord> hostFriction;
   // "sdf_cull": pbf_sdf_from_mesh / pbf_set_collider_mesh skip the triangles out of a brick's reach (same bytes, 5 - 7 x faster)
   bool sdfCull = true;
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
@@ -1181,12 +1189,32 @@ int ensure_surface(pbf_ctx *ctx) {
   return ensure(ctx, ctx->surfB, bytes);
 }
 
+// The friction pass's partial records outlive the step (the observer and the next step's body stage fold them), so unlike
+// every other buffer they are carried across a grow: the old bytes are copied into the new allocation on the ctx's stream
+// before the old one is freed.  (While the stream is being captured the synchronise fails and nothing is replaced: the step
+// is then redone eagerly, as after any allocation.)
+int ensure_friction_partials(pbf_ctx *ctx) {
+  const size_t bytes = (ctx->cap / DIAG_TILE + 2) * sizeof(WrenchPartial);
+  DevBuf &b = ctx->frictionPartials;
+  if (b.cap >= bytes) return PBF_OK;
+  DevBuf fresh;
+  if (int rc = ensure(ctx, fresh, bytes)) return rc;
+  if (b.p) {
+    HIPCHK(ctx, hipMemcpyAsync(fresh.p, b.p, b.cap, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  b = std::move(fresh);  // (frees the old records)
+  return PBF_OK;
+}
+
 // pbf_set_collider_reaction's buffers, sized to the particle capacity: made when the feature is enabled and regrown when an
 // upload grows the capacity, so that no step allocates
 int ensure_reaction(pbf_ctx *ctx) {
   if (!ctx->reactionOn) return PBF_OK;
   const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4);
   if (int rc = ensure(ctx, ctx->pushRec, std::max<size_t>(ctx->cap, 1) * 2 * v)) return rc;
+  if (ctx->frictionOn)
+    if (int rc = ensure_friction_partials(ctx)) return rc;
   return ensure(ctx, ctx->pushPartials, (ctx->cap / DIAG_TILE + 2) * sizeof(WrenchPartial));
 }
 
@@ -1266,11 +1294,32 @@ template <typename N> int extras(pbf_ctx *ctx, const pbf_params *p, const StepCo
   return DISPATCH_FAST(ctx, extras_impl, ctx, p, c);
 }
 
+// pbf_set_collider_friction's pass, right after k_finalise and before the extras: one streaming launch over the step's
+// reaction records (indexed as collider_reaction_impl chooses) on the finalised velocity.  No read-back, nothing allocated;
+// captured with the step.
+template <typename N> int stage_friction(pbf_ctx *ctx, const pbf_params *p) {
+  const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
+  const int s = ctx->st.cur;
+  const pbf_collider_friction *rec = ctx->frictionRec.as<const pbf_collider_friction>();
+  const double *vw = ctx->bodyOn ? ctx->bodyRec.as<const colliderbody::Record>()->st.velocity : rec->velocity;  // (addresses only)
+  hipLaunchKernelGGL((k_collider_friction<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, N(p->scale), N(p->dt), rec, vw,
+                     ctx->colliderPose.as<const ColliderPose<N>>(), ctx->pushRec.as<const vec4<N>>(),
+                     ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[s].as<const vec4<N>>(),
+                     ctx->vel4[s].as<vec4<N>>(), ctx->frictionPartials.as<WrenchPartial>(), ctx->frictionCtl.as<colliderfriction::Ctl>());
+  LAUNCH_CHECK(ctx);
+  ctx->frictionRan = true;
+  return PBF_OK;
+}
+
 template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   const int s = ctx->st.cur;
-  if (ctx->fuseNextPredict && !extras_on(ctx, p)) {
+  if (ctx->frictionOn) {  // (the pass follows the finalise below: refuse before anything is launched)
+    if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+    if (!record_current(ctx, ctx->pushAt)) return fail(ctx, PBF_ERR_STATE, "the collider friction needs a sort since the reaction records were enabled");
+  }
+  if (ctx->fuseNextPredict && !extras_on(ctx, p) && !ctx->frictionOn) {
     // finalise(t) + predict(t + 1) in one pass: everything stage_predict does, around one launch
     ctx->fuseNextPredict = false;
     if (int rc = ensure_table(ctx, c.tableN)) return rc;
@@ -1304,6 +1353,8 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   // keep pstar[cur] as the live buffer so that a later sort scatters pstar[cur] -> pstar[1-cur]
   std::swap(ctx->pstar[ctx->st.pcur], ctx->pstar[s]);
   ctx->st.finalised();
+  if (ctx->frictionOn)  // (before the extras: they see the boundary-corrected velocity)
+    if (int rc = stage_friction<N>(ctx, p)) return rc;
   if (extras_on(ctx, p)) return extras<N>(ctx, p, c);
   return PBF_OK;
 }
@@ -1372,8 +1423,13 @@ template <typename N> int stage_body(pbf_ctx *ctx, const pbf_params *p) {
   hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(),
                      ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[ctx->st.cur].as<const vec4<N>>(),
                      ctx->pushPartials.as<WrenchPartial>());
-  hipLaunchKernelGGL((k_body_advance<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->pushPartials.as<const WrenchPartial>(),
-                     double(p->dt), ctx->bodyRec.as<colliderbody::Record>(), ctx->colliderPose.as<ColliderPose<N>>());
+  if (ctx->frictionOn)  // (the previous step's friction sums kick the body first, consumed once: the device's pending word)
+    hipLaunchKernelGGL((k_body_kick_advance<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->frictionPartials.as<const WrenchPartial>(),
+                       ctx->frictionCtl.as<colliderfriction::Ctl>(), nb, ctx->pushPartials.as<const WrenchPartial>(), double(p->dt),
+                       ctx->bodyRec.as<colliderbody::Record>(), ctx->colliderPose.as<ColliderPose<N>>());
+  else
+    hipLaunchKernelGGL((k_body_advance<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->pushPartials.as<const WrenchPartial>(),
+                       double(p->dt), ctx->bodyRec.as<colliderbody::Record>(), ctx->colliderPose.as<ColliderPose<N>>());
   LAUNCH_CHECK(ctx);
   return PBF_OK;
 }
@@ -1828,6 +1884,7 @@ void restore(pbf_ctx *ctx, const StepState &s) {
   ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
   ctx->orderEpoch++;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
   if (ctx->reactionOn) ctx->pushAt = ctx->orderEpoch, ctx->pushRows = 0;  // (its clear ran with it; a graphed step has no row-major launches)
+  if (ctx->frictionOn) ctx->frictionRan = true;                            // (and so did its friction pass)
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
@@ -2491,6 +2548,7 @@ int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
   ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
   ctx->colliderPosed = false;           // (a new solid starts without a pose)
   ctx->bodyOn = false;                  // (and without a body)
+  ctx->frictionOn = false;              // (and without friction)
   if (int rc = collider_pose_identity(ctx)) return rc;
   for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
   ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
@@ -2649,6 +2707,8 @@ int pbf_set_collider_reaction(pbf_ctx *ctx, int on) {
   if (want == ctx->reactionOn) return PBF_OK;
   if (!want && ctx->bodyOn)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a body is on and needs the records (pbf_set_collider_body(ctx, NULL) first)");
+  if (!want && ctx->frictionOn)
+    return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: friction is on and needs the records (pbf_set_collider_friction(ctx, NULL) first)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (want) {
     ctx->reactionOn = true;
@@ -2705,6 +2765,10 @@ int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body) {
   else
     hipLaunchKernelGGL((k_body_store<float>), dim3(1), dim3(1), 0, ctx->stream, rec, ctx->bodyRec.as<colliderbody::Record>(),
                        ctx->colliderPose.as<ColliderPose<float>>());
+  // (with friction on, sums of a pass that ran before this call were taken against another pose and other velocities: the
+  // body as placed here does not receive them)
+  if (ctx->frictionOn)
+    hipLaunchKernelGGL(k_friction_pending_clear, dim3(1), dim3(1), 0, ctx->stream, ctx->frictionCtl.as<colliderfriction::Ctl>());
   LAUNCH_CHECK(ctx);
   if (!ctx->bodyOn) {  // off -> on selects another launch sequence; a re-placed body changes no key and drops no graph
     if (int rc = collider_drop_graphs(ctx)) return rc;
@@ -2723,6 +2787,59 @@ int pbf_collider_body_state(pbf_ctx *ctx, struct pbf_collider_body_state *out) {
   hipLaunchKernelGGL(k_body_read, dim3(1), dim3(1), 0, ctx->stream, ctx->bodyRec.as<const colliderbody::Record>(), ctx->hostBody.rec.p, seq);
   LAUNCH_CHECK(ctx);
   return receive(ctx, ctx->hostBody, "collider body read-back", *out);
+}
+
+static_assert(sizeof(pbf_collider_friction) == 7 * 8, "the friction record is seven doubles: mu, V, W");
+// (k_collider_friction reads V.xyz, W.xyz as six consecutive doubles from either record)
+static_assert(offsetof(pbf_collider_friction, angular_velocity) == offsetof(pbf_collider_friction, velocity) + 24 &&
+                  offsetof(struct pbf_collider_body_state, angular_velocity) == offsetof(struct pbf_collider_body_state, velocity) + 24,
+              "angular_velocity follows velocity directly in pbf_collider_friction and in pbf_collider_body_state");
+int pbf_set_collider_friction(pbf_ctx *ctx, const pbf_collider_friction *f) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (f) {
+    const char *why = nullptr;
+    if (colliderfriction::check(f, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  }
+  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_friction: no collider set (pbf_set_collider)");
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!f) {  // off: the launch sequence without the pass; the reaction stays on
+    if (!ctx->frictionOn) return PBF_OK;
+    if (int rc = collider_drop_graphs(ctx)) return rc;
+    ctx->frictionOn = false, ctx->frictionRan = false;
+    return PBF_OK;
+  }
+  const bool turnOn = !ctx->frictionOn;
+  if (turnOn) {  // everything a step will need is allocated here
+    if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;  // (a no-op when it is on already)
+    if (int rc = ensure(ctx, ctx->frictionRec, sizeof(pbf_collider_friction))) return rc;
+    if (int rc = ensure(ctx, ctx->frictionCtl, sizeof(colliderfriction::Ctl))) return rc;
+    if (int rc = ensure_friction_partials(ctx)) return rc;
+    HIPCHK(ctx, ctx->hostFriction.rec.ensure(1));  // (so that the observer allocates nothing either)
+  }
+  hipLaunchKernelGGL(k_friction_store, dim3(1), dim3(1), 0, ctx->stream, *f, ctx->frictionRec.as<pbf_collider_friction>(),
+                     ctx->frictionCtl.as<colliderfriction::Ctl>(), turnOn ? 1 : 0);
+  LAUNCH_CHECK(ctx);
+  if (turnOn) {  // off -> on selects another launch sequence; a rewritten record changes no key and drops no graph
+    if (int rc = collider_drop_graphs(ctx)) return rc;
+    ctx->frictionOn = true, ctx->frictionRan = false;
+  }
+  return PBF_OK;
+}
+
+int pbf_collider_friction_reaction(pbf_ctx *ctx, pbf_collider_wrench *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_friction_reaction: out == NULL");
+  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (!ctx->frictionOn) return fail(ctx, PBF_ERR_STATE, "pbf_collider_friction_reaction: friction is off (pbf_set_collider_friction)");
+  if (!ctx->frictionRan) return fail(ctx, PBF_ERR_STATE, "pbf_collider_friction_reaction: no step since friction was turned on");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t seq;
+  HIPCHK(ctx, ctx->hostFriction.arm(seq));
+  hipLaunchKernelGGL(k_friction_final, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->frictionPartials.as<const WrenchPartial>(),
+                     ctx->frictionCtl.as<const colliderfriction::Ctl>(), ctx->hostFriction.rec.p, seq);
+  LAUNCH_CHECK(ctx);
+  return receive(ctx, ctx->hostFriction, "collider friction read-back", *out);
 }
 
 int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records, pbf_mesh_info *info) {

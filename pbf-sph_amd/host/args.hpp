@@ -53,6 +53,10 @@ struct Args {
   bool colliderBody = false;
   double colliderBodyCfg[5] = {0, 0, 0, 0, 0.49};   // mass, the principal moments (0 = a solid ball of the collider's radius), gain
   size_t colliderBodyReport = 0;          // 0 = off
+  // --collider-friction=mu with --resident and --collider: Coulomb friction against the solid (pbf_set_collider_friction; inf =
+  // no-slip), relative to --collider-motion's velocities when given; --collider-friction-report[=every] prints the pass's sums
+  double colliderFriction = 0;            // 0 = off
+  size_t colliderFrictionReport = 0;      // 0 = off
   double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
   size_t wwCapacity = 0;                  // 0 = off
   bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
@@ -133,6 +137,11 @@ struct Args {
           "                                        about the lattice's axes (default: a solid ball of the sphere's radius);\n"
           "                                        gain 0.49 (default) returns the momentum the fluid was given\n"
           "      --collider-body-report[=every]    One JSON line per `every` frames with the body's state\n"
+          "      --collider-friction=[mu]          With --resident and --collider: Coulomb friction against the solid, one pass\n"
+          "                                        after every finalise; mu > 0, inf = no-slip. With --collider-motion the drag is\n"
+          "                                        towards the moving solid's contact velocity, with --collider-body the body's\n"
+          "      --collider-friction-report[=every]  One JSON line per `every` frames with the impulse and angular impulse the\n"
+          "                                        friction pass gave the fluid in that frame\n"
           "      --whitewater=[k_ta,k_wc[,capacity]]  With --resident: spray, foam and air bubbles after Ihmsen et al. 2012,\n"
           "                                        one whitewater step after every frame at these rates; the tau ranges are\n"
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
@@ -256,6 +265,17 @@ struct Args {
             if (!std::isfinite(x)) throw std::runtime_error("--collider-motion: the values must be finite");
           colliderMoves = true;
           for (size_t k = 0; k < f.size(); ++k) colliderMotion[k] = f[k];
+        }
+        else if (a == "--collider-friction-report") colliderFrictionReport = 1;
+        else if (a.rfind("--collider-friction-report=", 0) == 0) {
+          colliderFrictionReport = std::stoull(a.substr(27));
+          if (colliderFrictionReport == 0) throw std::runtime_error("--collider-friction-report: every must be >= 1");
+        }
+        else if (value(i, a, "", "--collider-friction", v)) {
+          const auto f = numbers(v);
+          if (f.size() != 1) throw std::runtime_error("--collider-friction: expected mu");
+          if (!(f[0] > 0)) throw std::runtime_error("--collider-friction: mu must be > 0 (inf = no-slip)");
+          colliderFriction = f[0];
         }
         else if (a == "--collider-body-report") colliderBodyReport = 1;
         else if (a.rfind("--collider-body-report=", 0) == 0) {

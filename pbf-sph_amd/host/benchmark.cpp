@@ -149,6 +149,15 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   const bool colliderBody = args.colliderBody && collider && args.resident;
   const size_t colliderBodyReport = colliderBody ? args.colliderBodyReport : 0;
   const size_t colliderReaction = collider && args.resident ? args.colliderReaction : 0;
+  if ((args.colliderFriction > 0 || args.colliderFrictionReport) && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--collider-friction / --collider-friction-report are single-device features: they cannot be combined with --slabs / --all-devices"
+              << std::endl;
+    return 1;
+  }
+  if ((args.colliderFriction > 0 || args.colliderFrictionReport) && !(collider && args.resident))
+    std::cout << "--collider-friction / --collider-friction-report take effect with --resident and --collider: ignored" << std::endl;
+  const bool colliderFriction = args.colliderFriction > 0 && collider && args.resident;
+  const size_t colliderFrictionReport = colliderFriction ? args.colliderFrictionReport : 0;
   if (args.diagnostics && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--diagnostics is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -275,6 +284,10 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cout << "Collider body        : mass " << body.mass << ", moments " << body.inertia[0] << " " << body.inertia[1] << " " << body.inertia[2]
               << ", gain " << body.gain << ", centre " << bodyCentre[0] << " " << bodyCentre[1] << " " << bodyCentre[2] << std::endl;
   }
+  if (colliderFriction) {  // (against a solid at rest; --collider-motion rewrites the velocities every frame, a body supplies its own)
+    solver.setColliderFriction(args.colliderFriction);
+    std::cout << "Collider friction    : mu " << args.colliderFriction << std::endl;
+  }
   // --collider-motion: the pose of the frame numbered f (warm-up frames included), at time f * dt — a rotation by |w| f dt about
   // the axis w through the pivot p (Rodrigues), then the translation v f dt: w = R (b - p) + p + v f dt
   size_t poseFrame = 0;
@@ -318,8 +331,16 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       if (colliderMoves) {  // the pose of this frame, before it is stepped
         std::array<double, 9> rot;
         std::array<double, 3> trans;
+        const double tau = double(poseFrame) * double(param.dt);
         colliderPoseOf(poseFrame++, rot, trans);
         solver.setColliderPose(rot, trans);
+        if (colliderFriction) {  // the velocity of the solid's point at the pose's t: v + w x (t - (p + v tau)); the spin is w itself
+          const double *m = args.colliderMotion;
+          const double d[3] = {trans[0] - (m[6] + m[0] * tau), trans[1] - (m[7] + m[1] * tau), trans[2] - (m[8] + m[2] * tau)};
+          solver.setColliderFriction(args.colliderFriction,
+                                     {m[0] + (m[4] * d[2] - m[5] * d[1]), m[1] + (m[5] * d[0] - m[3] * d[2]), m[2] + (m[3] * d[1] - m[4] * d[0])},
+                                     {m[3], m[4], m[5]});
+        }
       }
       solver.step(frameParam(frame), scene);
       if (whitewater && solver.count()) {
@@ -407,6 +428,21 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
               << ",\"particles\":" << w.particles << ",\"step\":" << w.step << "}}" << std::endl;
     diagMillis += duration_millis(hrc::now() - d0).count();
   };
+  // --collider-friction-report: the friction pass's sums in the wrench's layout (hits = particles that slid, particles = in contact)
+  auto frictionReport = [&](size_t frame) {
+    const auto d0 = hrc::now();
+    const pbf_collider_wrench w = solver.colliderFrictionReaction();
+    auto num = [](double x) {
+      char buf[40];
+      std::snprintf(buf, sizeof buf, "%.17g", x);
+      return std::isfinite(x) ? std::string(buf) : std::string("null");
+    };
+    auto vec3 = [&](const double *v) { return "[" + num(v[0]) + "," + num(v[1]) + "," + num(v[2]) + "]"; };
+    std::cout << "{\"frame\":" << frame << ",\"friction\":{\"impulse\":" << vec3(w.impulse) << ",\"angular\":" << vec3(w.angular)
+              << ",\"abs_impulse\":" << vec3(w.abs_impulse) << ",\"abs_angular\":" << vec3(w.abs_angular) << ",\"hits\":" << w.hits
+              << ",\"particles\":" << w.particles << ",\"step\":" << w.step << "}}" << std::endl;
+    diagMillis += duration_millis(hrc::now() - d0).count();
+  };
   // --collider-body-report: one JSON line per report, kept out of the timed frames like the wrench's
   auto bodyReport = [&](size_t frame) {
     const auto d0 = hrc::now();
@@ -441,6 +477,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     if (args.resident && args.diagnostics && (frame + 1) % args.diagnostics == 0) report(frame);
     if (colliderReaction && solver.count() && (frame + 1) % colliderReaction == 0) wrench(frame);
     if (colliderBodyReport && (frame + 1) % colliderBodyReport == 0) bodyReport(frame);
+    if (colliderFrictionReport && solver.count() && (frame + 1) % colliderFrictionReport == 0) frictionReport(frame);
     if (probing && (args.probeEvery ? (frame + 1) % args.probeEvery == 0 : frame + 1 == args.iterations)) probe(frame);
   }
   end = hrc::now();

@@ -502,6 +502,29 @@ public:
     check(pbf_collider_body_state(ctx_, &st), "pbf_collider_body_state");
     return st;
   }
+  // Collider friction (pbf_set_collider_friction): Coulomb drag against the installed collider, relative to the solid's contact
+  // velocity (velocity + angular_velocity x (x - the pose's t); a body's own while a body is on), one pass after every finalise,
+  // pbf_steps and graph replays included.  mu = +inf is no-slip.  Calling it again rewrites the record without a recapture.
+  // colliderFrictionReaction() synchronises: the last pass's raw sums; the solid received -impulse and -angular.
+  Solver &setColliderFriction(double mu, const std::array<double, 3> &velocity = {0, 0, 0}, const std::array<double, 3> &angular_velocity = {0, 0, 0}) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_collider_friction f{};
+    f.mu = mu;
+    for (size_t k = 0; k < 3; ++k) f.velocity[k] = velocity[k], f.angular_velocity[k] = angular_velocity[k];
+    check(pbf_set_collider_friction(ctx_, &f), "pbf_set_collider_friction");
+    return *this;
+  }
+  Solver &clearColliderFriction() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_friction(ctx_, nullptr), "pbf_set_collider_friction");
+    return *this;
+  }
+  pbf_collider_wrench colliderFrictionReaction() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_collider_wrench w{};
+    check(pbf_collider_friction_reaction(ctx_, &w), "pbf_collider_friction_reaction");
+    return w;
+  }
 
   // ---- device-resident path -------------------------------------------------------------------
   // Several devices: `config` places the cuts (its bounds and scale define the grid columns); the slabs start with
