@@ -29,6 +29,7 @@
 #include "pbf_mesh_sdf.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
+#include "pbf_collider_state.hpp"
 #include "pbf_collider_pose.hpp"
 #include "pbf_collider_friction.hpp"
 
@@ -147,7 +148,7 @@ struct GraphKey {
   StepState before;
   unsigned char params[sizeof(double) * 11 + 32];  // dt, scale, force, bounds, iteration, xsph, vorticity, cohesion, adhesion
   uint64_t n;
-  uint64_t collider;  // pbf_ctx::colliderGen (pbf_set_collider): a replay never runs on a lattice that has been replaced
+  uint64_t collider;  // ColliderState::gen: a replay never runs on a lattice that has been replaced, nor another launch sequence
   int options[10];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
@@ -220,37 +221,25 @@ struct pbf_ctx {
   // pbf_set_surface_tension (opt-in, Akinci 2013): coefficients, the two Jacobi fields of its passes (allocated on first use)
   double cohesion = 0, adhesion = 0;
   DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE, while st.surfaceValid)
-  // pbf_set_collider (opt-in, csrc/pbf_collider.hpp): the lattice in N on the device (NULL = off) and the setting as given.
-  // colliderGen changes with every call: it is part of a captured step's key (graph_key).
+  // The collider (opt-in): which of lattice / pose / reaction / body / friction is on and what the step's reaction records
+  // describe, changed through its events only (pbf_collider_state.hpp: the rules are there); below it, the memory.
+  ColliderState col;
+  // pbf_set_collider (csrc/pbf_collider.hpp): the lattice in N on the device and the setting as given
   DevBuf colliderPhi;
   uint32_t colliderDims[3] = {0, 0, 0};
   double colliderOrigin[3] = {0, 0, 0}, colliderSpacing = 0, colliderMargin = 0;
-  uint64_t colliderGen = 0;
-  // pbf_set_collider_pose: the one ColliderPose<N> record the posed kernels read through a pointer (allocated by the first
-  // call), and whether a pose is set.  A pose update changes neither; none <-> posed bumps colliderGen (other kernels).
+  // pbf_set_collider_pose: the one ColliderPose<N> record the posed kernels read through a pointer (allocated by the first call)
   DevBuf colliderPose;
-  bool colliderPosed = false;
   // pbf_set_collider_reaction: the records {A, hits}, {B, 0} of DeltaOp<.., COLLIDE_REACT> (2 vec4<N> per particle, sized to
-  // the capacity), the step counter its clear bumps, the partial sums of pbf_collider_reaction and its pinned record.
-  // pushAt: the order epoch of the sort that cleared the records (0: no sort since enabling), believed like diagRhoAt.
-  // pushRows: the delta-p launches since that sort indexed them by row slot (-1: none has run yet).
-  bool reactionOn = false;
+  // the capacity), the step counter its clear bumps, the partial sums of pbf_collider_reaction and its pinned record
   DevBuf pushRec, pushCtl, pushPartials, pushOut;
   Mailbox<WrenchRecord> hostWrench;
-  uint64_t pushAt = 0;
-  int pushRows = -1;
   // pbf_set_collider_body: the one colliderbody::Record on the device (parameters and state; allocated by the first call)
-  // and whether a body is on.  On <-> off bumps colliderGen (another launch sequence); re-placing the body changes nothing
-  // here.  A body implies reactionOn and colliderPosed.
   DevBuf bodyRec;
-  bool bodyOn = false;
   Mailbox<BodyStateRecord> hostBody;
   // pbf_set_collider_friction: the record {mu, V, W} the pass reads through a pointer, the device's counters, the pass's own
-  // partial records (they outlive the step: the observer and the next step's body stage fold them), whether friction is on
-  // and whether a pass has run since.  On <-> off bumps colliderGen; a rewritten record changes nothing here.  Friction
-  // implies reactionOn.
+  // partial records (they outlive the step: the observer and the next step's body stage fold them)
   DevBuf frictionRec, frictionCtl, frictionPartials;
-  bool frictionOn = false, frictionRan = false;
   Mailbox<WrenchRecord> hostFriction;
   // "sdf_cull": pbf_sdf_from_mesh / pbf_set_collider_mesh skip the triangles out of a brick's reach (same bytes, 5 - 7 x faster)
   bool sdfCull = true;
@@ -763,13 +752,13 @@ template <typename N> int stage_sort(pbf_ctx *ctx, const pbf_params *p) {
   ctx->gatherSeq = 0;  // (fresh tickets)
   ctx->st.sorted_now(rows, rowDiffuse);
   ctx->orderEpoch++;  // (a new order: what the observers left describes the old one)
-  if (ctx->reactionOn) {  // the reaction records are indexed by the order just established: cleared once per step, here
+  if (ctx->col.reaction) {  // the reaction records are indexed by the order just established: cleared once per step, here
     if (int rc = ensure_reaction(ctx)) return rc;  // (allocates only if the capacity grew without an upload)
     const uint32_t n2 = 2u * uint32_t(ctx->n);
     hipLaunchKernelGGL((k_push_clear<N>), grid_for(std::max<size_t>(n2, 1)), dim3(BLOCK), 0, ctx->stream, n2, ctx->pushRec.as<vec4<N>>(),
                        ctx->pushCtl.as<unsigned long long>());
     LAUNCH_CHECK(ctx);
-    ctx->pushAt = ctx->orderEpoch, ctx->pushRows = -1;
+    ctx->col.records_cleared(ctx->orderEpoch);
   }
   if (!rowDiffuse) brick_list(ctx, c.tableN, /*counterIsZero=*/true);  // (the row-major diffusion has its own segments)
   return PBF_OK;
@@ -1115,7 +1104,13 @@ template <typename N> int stage_lambda(pbf_ctx *ctx, const pbf_params *p, bool f
 }
 
 // pbf_set_collider's lattice as DeltaOp<.., COLLIDE = true> and k_collider_sample take it (all zero, phi == NULL, without one)
-bool collider_on(const pbf_ctx *ctx) { return ctx->colliderPhi.p != nullptr; }
+bool collider_on(const pbf_ctx *ctx) { return ctx->col.lattice; }
+static_assert(int(ColliderState::DELTA_OFF) == COLLIDE_OFF && int(ColliderState::DELTA_STATIC) == COLLIDE_STATIC &&
+                  int(ColliderState::DELTA_POSED) == COLLIDE_POSED && int(ColliderState::DELTA_REACT) == COLLIDE_REACT,
+              "ColliderState::delta_mode() names pbf_kernels.hpp's ColliderMode");
+// the reaction records of the step: whether they describe the arrays as they are, and the slots their readers index them by
+bool push_current(const pbf_ctx *ctx) { return ctx->col.records_current(ctx->orderEpoch, ctx->st.sorted); }
+const uint32_t *push_slots(const pbf_ctx *ctx) { return ctx->col.records_by_row() ? ctx->rowSlotOf.as<const uint32_t>() : nullptr; }
 template <typename N> ColliderSdf<N> collider_args(const pbf_ctx *ctx) {
   ColliderSdf<N> s{};
   if (!collider_on(ctx)) return s;
@@ -1125,6 +1120,13 @@ template <typename N> ColliderSdf<N> collider_args(const pbf_ctx *ctx) {
   return s;
 }
 constexpr const char *kColliderSlabError = "a collider is not supported in slab mode (pbf_set_collider(ctx, NULL) clears it)";
+bool slab_ctx(const pbf_ctx *ctx) { return ctx->comm || ctx->slabActive || ctx->slabConfigured; }
+int collider_refuse_slab(pbf_ctx *ctx) { return slab_ctx(ctx) ? fail(ctx, PBF_ERR_STATE, kColliderSlabError) : PBF_OK; }
+// what the entry points that need a lattice (`who`) refuse alike, after the refusals that are their own: none set, then slab mode
+int collider_needed(pbf_ctx *ctx, const char *who) {
+  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, std::string(who) + ": no collider set (pbf_set_collider)");
+  return collider_refuse_slab(ctx);
+}
 
 template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const pbf_params *p) {
   using Op = DeltaOp<N, FAST, COLLIDE>;
@@ -1139,11 +1141,9 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   if constexpr (COLLIDE == COLLIDE_REACT) {  // the records follow the index of the launch: one kind of index per step
-    const int rows = ctx->st.delta_on_rows() ? 1 : 0;
-    if (!record_current(ctx, ctx->pushAt)) return fail(ctx, PBF_ERR_STATE, "the collider reaction needs a sort since it was enabled");
-    if (ctx->pushRows >= 0 && ctx->pushRows != rows)
+    if (!push_current(ctx)) return fail(ctx, PBF_ERR_STATE, "the collider reaction needs a sort since it was enabled");
+    if (!ctx->col.delta_indexed(ctx->st.delta_on_rows()))
       return fail(ctx, PBF_ERR_STATE, "the gather path changed between two delta-p launches of a step with the collider reaction on");
-    ctx->pushRows = rows;
   }
   StageTimer t(ctx, ST_DELTA);
   const int s = ctx->st.cur;
@@ -1166,13 +1166,18 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
   return rc;
 }
 template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
-  // the one place that picks the mode
-  if (!collider_on(ctx)) return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
-  if (ctx->reactionOn) return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);  // (the identity pose while none is set)
-  return ctx->colliderPosed ? delta_run<N, FAST, COLLIDE_POSED>(ctx, p) : delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
+  // the one place that turns the mode into an instantiation (this order of first use fixes the kernels' order in the code object)
+  switch (ctx->col.delta_mode()) {
+    case ColliderState::DELTA_OFF: return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
+    case ColliderState::DELTA_REACT: return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);
+    case ColliderState::DELTA_POSED: return delta_run<N, FAST, COLLIDE_POSED>(ctx, p);
+    case ColliderState::DELTA_STATIC: break;
+  }
+  return delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
 }
 template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
-  if (collider_on(ctx) && (ctx->comm || ctx->slabActive || ctx->slabConfigured)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (collider_on(ctx))
+    if (int rc = collider_refuse_slab(ctx)) return rc;
   return DISPATCH_FAST(ctx, delta_impl, ctx, p);
 }
 
@@ -1208,12 +1213,11 @@ int ensure_friction_partials(pbf_ctx *ctx) {
 }
 
 // pbf_set_collider_reaction's buffers, sized to the particle capacity: made when the feature is enabled and regrown when an
-// upload grows the capacity, so that no step allocates
+// upload grows the capacity while it is on, so that no step allocates
 int ensure_reaction(pbf_ctx *ctx) {
-  if (!ctx->reactionOn) return PBF_OK;
   const size_t v = ctx->fp64 ? sizeof(double4) : sizeof(float4);
   if (int rc = ensure(ctx, ctx->pushRec, std::max<size_t>(ctx->cap, 1) * 2 * v)) return rc;
-  if (ctx->frictionOn)
+  if (ctx->col.friction)
     if (int rc = ensure_friction_partials(ctx)) return rc;
   return ensure(ctx, ctx->pushPartials, (ctx->cap / DIAG_TILE + 2) * sizeof(WrenchPartial));
 }
@@ -1301,13 +1305,13 @@ template <typename N> int stage_friction(pbf_ctx *ctx, const pbf_params *p) {
   const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
   const int s = ctx->st.cur;
   const pbf_collider_friction *rec = ctx->frictionRec.as<const pbf_collider_friction>();
-  const double *vw = ctx->bodyOn ? ctx->bodyRec.as<const colliderbody::Record>()->st.velocity : rec->velocity;  // (addresses only)
+  const double *vw = ctx->col.body ? ctx->bodyRec.as<const colliderbody::Record>()->st.velocity : rec->velocity;  // (addresses only)
   hipLaunchKernelGGL((k_collider_friction<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, N(p->scale), N(p->dt), rec, vw,
-                     ctx->colliderPose.as<const ColliderPose<N>>(), ctx->pushRec.as<const vec4<N>>(),
-                     ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[s].as<const vec4<N>>(),
-                     ctx->vel4[s].as<vec4<N>>(), ctx->frictionPartials.as<WrenchPartial>(), ctx->frictionCtl.as<colliderfriction::Ctl>());
+                     ctx->colliderPose.as<const ColliderPose<N>>(), ctx->pushRec.as<const vec4<N>>(), push_slots(ctx),
+                     ctx->pos4[s].as<const vec4<N>>(), ctx->vel4[s].as<vec4<N>>(), ctx->frictionPartials.as<WrenchPartial>(),
+                     ctx->frictionCtl.as<colliderfriction::Ctl>());
   LAUNCH_CHECK(ctx);
-  ctx->frictionRan = true;
+  ctx->col.friction_passed();
   return PBF_OK;
 }
 
@@ -1315,11 +1319,11 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   const int s = ctx->st.cur;
-  if (ctx->frictionOn) {  // (the pass follows the finalise below: refuse before anything is launched)
-    if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
-    if (!record_current(ctx, ctx->pushAt)) return fail(ctx, PBF_ERR_STATE, "the collider friction needs a sort since the reaction records were enabled");
+  if (ctx->col.friction) {  // (the pass follows the finalise below: refuse before anything is launched)
+    if (int rc = collider_refuse_slab(ctx)) return rc;
+    if (!push_current(ctx)) return fail(ctx, PBF_ERR_STATE, "the collider friction needs a sort since the reaction records were enabled");
   }
-  if (ctx->fuseNextPredict && !extras_on(ctx, p) && !ctx->frictionOn) {
+  if (ctx->fuseNextPredict && !extras_on(ctx, p) && !ctx->col.friction) {
     // finalise(t) + predict(t + 1) in one pass: everything stage_predict does, around one launch
     ctx->fuseNextPredict = false;
     if (int rc = ensure_table(ctx, c.tableN)) return rc;
@@ -1353,7 +1357,7 @@ template <typename N> int stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
   // keep pstar[cur] as the live buffer so that a later sort scatters pstar[cur] -> pstar[1-cur]
   std::swap(ctx->pstar[ctx->st.pcur], ctx->pstar[s]);
   ctx->st.finalised();
-  if (ctx->frictionOn)  // (before the extras: they see the boundary-corrected velocity)
+  if (ctx->col.friction)  // (before the extras: they see the boundary-corrected velocity)
     if (int rc = stage_friction<N>(ctx, p)) return rc;
   if (extras_on(ctx, p)) return extras<N>(ctx, p, c);
   return PBF_OK;
@@ -1417,13 +1421,12 @@ template <typename N> int stage_scene(pbf_ctx *ctx, const pbf_params *p) {
 // observer's partial kernel (indexed as collider_reaction_impl chooses) and ONE workgroup that folds the partial records,
 // advances the body and writes the pose of the next step.  No read-back, nothing allocated; captured with the step.
 template <typename N> int stage_body(pbf_ctx *ctx, const pbf_params *p) {
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
-  if (!record_current(ctx, ctx->pushAt)) return fail(ctx, PBF_ERR_STATE, "the collider body needs a sort since the reaction records were enabled");
+  if (int rc = collider_refuse_slab(ctx)) return rc;
+  if (!push_current(ctx)) return fail(ctx, PBF_ERR_STATE, "the collider body needs a sort since the reaction records were enabled");
   const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
-  hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(),
-                     ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[ctx->st.cur].as<const vec4<N>>(),
-                     ctx->pushPartials.as<WrenchPartial>());
-  if (ctx->frictionOn)  // (the previous step's friction sums kick the body first, consumed once: the device's pending word)
+  hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(), push_slots(ctx),
+                     ctx->pos4[ctx->st.cur].as<const vec4<N>>(), ctx->pushPartials.as<WrenchPartial>());
+  if (ctx->col.friction)  // (the previous step's friction sums kick the body first, consumed once: the device's pending word)
     hipLaunchKernelGGL((k_body_kick_advance<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->frictionPartials.as<const WrenchPartial>(),
                        ctx->frictionCtl.as<colliderfriction::Ctl>(), nb, ctx->pushPartials.as<const WrenchPartial>(), double(p->dt),
                        ctx->bodyRec.as<colliderbody::Record>(), ctx->colliderPose.as<ColliderPose<N>>());
@@ -1451,7 +1454,7 @@ template <typename N> int step_impl(pbf_ctx *ctx, const pbf_params *p) {
     if (int rc = stage_lambda<N>(ctx, p, fuse && it == 0)) return rc;
     if (int rc = stage_delta<N>(ctx, p)) return rc;
   }
-  if (ctx->bodyOn)  // (pbf_set_collider_body: the step's reaction moves the solid before the next step reads its pose)
+  if (ctx->col.body)  // (pbf_set_collider_body: the step's reaction moves the solid before the next step reads its pose)
     if (int rc = stage_body<N>(ctx, p)) return rc;
   if (int rc = stage_finalise<N>(ctx, p)) return rc;
   return join_diffuse(ctx);  // the step is complete on ctx->stream only once the colours are
@@ -1498,7 +1501,8 @@ int upload_impl(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type,
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
-  if (int rc = ensure_reaction(ctx)) return rc;
+  if (ctx->col.reaction)
+    if (int rc = ensure_reaction(ctx)) return rc;
   if (ctx->wwOn)
     if (int rc = ensure_whitewater_fields(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
@@ -1763,7 +1767,8 @@ int pbf_upload_aos(pbf_ctx *ctx, size_t n, const void *particles, const pbf_aos_
   if (surface_on(ctx))
     if (int rc = ensure_surface(ctx)) return rc;
   if (int rc = ensure_diag(ctx, /*first=*/false, /*density=*/false)) return rc;
-  if (int rc = ensure_reaction(ctx)) return rc;
+  if (ctx->col.reaction)
+    if (int rc = ensure_reaction(ctx)) return rc;
   if (int rc = drop_histogram(ctx)) return rc;
   ctx->st.arrays_replaced(0);
   ctx->n = n, ctx->uploaded = n;
@@ -1883,8 +1888,7 @@ void restore(pbf_ctx *ctx, const StepState &s) {
   ctx->st = s.st, ctx->hasObstacles = s.hasObstacles;  // (all of the derived state, not only what the key compares)
   ctx->tableN = s.tableN, ctx->gatherSeq = s.gatherSeq;
   ctx->orderEpoch++;  // (a replayed step has sorted; a rolled-back capture re-runs its sort)
-  if (ctx->reactionOn) ctx->pushAt = ctx->orderEpoch, ctx->pushRows = 0;  // (its clear ran with it; a graphed step has no row-major launches)
-  if (ctx->frictionOn) ctx->frictionRan = true;                            // (and so did its friction pass)
+  ctx->col.step_replayed(ctx->orderEpoch);  // (the records' clear ran with it, and the friction pass)
   DevBuf *b[15];
   role_buffers(ctx, b);
   for (int k = 0; k < 3; ++k) ctx->extent[k] = s.extent[k], ctx->minExtent[k] = s.minExtent[k];
@@ -1908,7 +1912,7 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   std::memcpy(k.params + sizeof(v) + 8, xv, 8);
   std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
-  k.collider = ctx->colliderGen;
+  k.collider = ctx->col.gen;
   const int opt[10] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
                        int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap)};
   std::memcpy(k.options, opt, sizeof(opt));
@@ -2032,7 +2036,8 @@ int pbf_stage_lambda(pbf_ctx *ctx, const pbf_params *p) {
   return DISPATCH(ctx, stage_lambda, ctx, p);
 }
 int pbf_stage_delta(pbf_ctx *ctx, const pbf_params *p) {
-  if (ctx && collider_on(ctx) && (ctx->comm || ctx->slabActive || ctx->slabConfigured)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (ctx && collider_on(ctx))
+    if (int rc = collider_refuse_slab(ctx)) return rc;
   if (int rc = check(ctx, p, true)) return rc;
   return DISPATCH(ctx, stage_delta, ctx, p);
 }
@@ -2042,7 +2047,7 @@ int pbf_stage_finalise(pbf_ctx *ctx, const pbf_params *p) {
 }
 int pbf_stage_body(pbf_ctx *ctx, const pbf_params *p) {
   if (int rc = check(ctx, p, false)) return rc;
-  if (!ctx->bodyOn) return fail(ctx, PBF_ERR_STATE, "pbf_stage_body: no body set (pbf_set_collider_body)");
+  if (!ctx->col.body) return fail(ctx, PBF_ERR_STATE, "pbf_stage_body: no body set (pbf_set_collider_body)");
   if (ctx->n == 0) return PBF_OK;  // (a depleted step does not advance the body)
   return DISPATCH(ctx, stage_body, ctx, p);
 }
@@ -2518,38 +2523,34 @@ int collider_lattice_check(pbf_ctx *ctx, const char *who, const pbf_collider_sdf
   if (!std::isfinite(sdf->spacing) || !(sdf->spacing > 0)) return fail(ctx, PBF_ERR_INVALID, w + "spacing must be finite and > 0");
   if (margin && (!std::isfinite(sdf->margin) || sdf->margin < 0)) return fail(ctx, PBF_ERR_INVALID, w + "margin must be finite and >= 0");
   if (phi && !sdf->phi) return fail(ctx, PBF_ERR_INVALID, w + "phi == NULL");
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (int rc = collider_refuse_slab(ctx)) return rc;
   *nodes = n;
   return PBF_OK;
 }
 
-// the one install path: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's collider
-// With the reaction on and no pose set the kernels run the identity pose: keep the record at it.
+// The pose record at the identity: what the REACT kernels read while no pose is set (ColliderState::needs_identity_pose).
 template <typename N> int collider_pose_store(pbf_ctx *ctx, const pbf_collider_pose *pose);
 int collider_pose_identity(pbf_ctx *ctx) {
-  if (!ctx->reactionOn || ctx->colliderPosed) return PBF_OK;
   pbf_collider_pose id{};
   id.rot[0] = id.rot[4] = id.rot[8] = 1.0;
   if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
   return ctx->fp64 ? collider_pose_store<double>(ctx, &id) : collider_pose_store<float>(ctx, &id);
 }
-// the steps captured so far can never be asked for again once colliderGen moves on: drop them
+// synchronise and destroy the captured steps: after an event of ColliderState that returned true none can be asked for again
 int collider_drop_graphs(pbf_ctx *ctx) {
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (auto &g : ctx->graphs)
     if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
   ctx->graphs.clear();
-  ctx->colliderGen++;
   return PBF_OK;
 }
+// the one install path: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's collider
 int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
-  // (they hold the old lattice's address)
-  if (int rc = collider_drop_graphs(ctx)) return rc;
-  ctx->colliderPhi = std::move(fresh);  // (frees the old lattice)
-  ctx->colliderPosed = false;           // (a new solid starts without a pose)
-  ctx->bodyOn = false;                  // (and without a body)
-  ctx->frictionOn = false;              // (and without friction)
-  if (int rc = collider_pose_identity(ctx)) return rc;
+  if (int rc = collider_drop_graphs(ctx)) return rc;  // (first: they hold the old lattice's address)
+  ctx->colliderPhi = std::move(fresh);                // (frees the old lattice)
+  ctx->col.installed(sdf != nullptr);
+  if (ctx->col.needs_identity_pose())
+    if (int rc = collider_pose_identity(ctx)) return rc;
   for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
   ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
   return PBF_OK;
@@ -2617,9 +2618,8 @@ template <typename N> int collider_reaction_impl(pbf_ctx *ctx, pbf_collider_wren
   HIPCHK(ctx, ctx->hostWrench.arm(seq));
   const uint32_t n = uint32_t(ctx->n), nb = (n + DIAG_TILE - 1) / DIAG_TILE;
   if (nb)
-    hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(),
-                       ctx->pushRows > 0 ? ctx->rowSlotOf.as<const uint32_t>() : nullptr, ctx->pos4[ctx->st.cur].as<const vec4<N>>(),
-                       ctx->pushPartials.as<WrenchPartial>());
+    hipLaunchKernelGGL((k_wrench_partial<N>), dim3(nb), dim3(BLOCK), 0, ctx->stream, n, ctx->pushRec.as<const vec4<N>>(), push_slots(ctx),
+                       ctx->pos4[ctx->st.cur].as<const vec4<N>>(), ctx->pushPartials.as<WrenchPartial>());
   hipLaunchKernelGGL(k_wrench_final, dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->pushPartials.as<const WrenchPartial>(),
                      ctx->pushCtl.as<const unsigned long long>(), ctx->hostWrench.rec.p, seq);
   LAUNCH_CHECK(ctx);
@@ -2647,7 +2647,7 @@ int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const doub
   for (int a = 0; a < 3; ++a) f.minB[a] = N(p->min_bound[a]), f.maxB[a] = N(p->max_bound[a]);
   HIPCHK(ctx, hipMemcpyAsync(ctx->samplePoints.p, pts.data(), 3 * e, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL((k_collider_sample<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, collider_args<N>(ctx),
-                     ctx->colliderPosed ? ctx->colliderPose.as<const ColliderPose<N>>() : nullptr, f, uint32_t(n),
+                     ctx->col.posed ? ctx->colliderPose.as<const ColliderPose<N>>() : nullptr, f, uint32_t(n),
                      ctx->samplePoints.as<const N>(), reinterpret_cast<N *>(out), reinterpret_cast<N *>(out + e),
                      reinterpret_cast<uint8_t *>(out + 4 * e));
   LAUNCH_CHECK(ctx);
@@ -2679,61 +2679,47 @@ int pbf_set_collider_pose(pbf_ctx *ctx, const pbf_collider_pose *pose) {
     const char *why = nullptr;
     if (colliderpose::check(pose, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
   }
-  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_pose: no collider set (pbf_set_collider)");
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
-  if (ctx->bodyOn)
+  if (int rc = collider_needed(ctx, "pbf_set_collider_pose")) return rc;
+  if (ctx->col.body)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_pose: a body is on and owns the pose (re-place it through pbf_set_collider_body)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!pose) {  // back to the static kernels
-    if (!ctx->colliderPosed) return PBF_OK;
+    if (!ctx->col.pose_cleared()) return PBF_OK;
     if (int rc = collider_drop_graphs(ctx)) return rc;
-    ctx->colliderPosed = false;
-    return collider_pose_identity(ctx);
+    return ctx->col.needs_identity_pose() ? collider_pose_identity(ctx) : PBF_OK;
   }
   if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
   if (int rc = ctx->fp64 ? collider_pose_store<double>(ctx, pose) : collider_pose_store<float>(ctx, pose)) return rc;
-  if (!ctx->colliderPosed) {  // none -> posed selects other kernels; an update changes no key and drops no graph
-    if (int rc = collider_drop_graphs(ctx)) return rc;
-    ctx->colliderPosed = true;
-  }
-  return PBF_OK;
+  return ctx->col.pose_set() ? collider_drop_graphs(ctx) : PBF_OK;  // (an update changes no key and drops no graph)
 }
 
 int pbf_set_collider_reaction(pbf_ctx *ctx, int on) {
   if (!ctx) return PBF_ERR_INVALID;
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured)
-    return fail(ctx, PBF_ERR_STATE, "the collider reaction is not supported in slab mode");
+  if (slab_ctx(ctx)) return fail(ctx, PBF_ERR_STATE, "the collider reaction is not supported in slab mode");
   const bool want = on != 0;
-  if (want == ctx->reactionOn) return PBF_OK;
-  if (!want && ctx->bodyOn)
+  if (want == ctx->col.reaction) return PBF_OK;
+  if (!want && ctx->col.why_reaction_must_stay() == ColliderState::HELD_BY_BODY)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a body is on and needs the records (pbf_set_collider_body(ctx, NULL) first)");
-  if (!want && ctx->frictionOn)
+  if (!want && ctx->col.why_reaction_must_stay() == ColliderState::HELD_BY_FRICTION)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: friction is on and needs the records (pbf_set_collider_friction(ctx, NULL) first)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (want) {
-    ctx->reactionOn = true;
-    int rc = ensure_reaction(ctx);
-    if (!rc) rc = ensure(ctx, ctx->pushCtl, 8);
-    if (!rc) rc = collider_pose_identity(ctx);
-    if (!rc && hipMemsetAsync(ctx->pushCtl.p, 0, 8, ctx->stream) != hipSuccess) rc = fail(ctx, PBF_ERR_HIP, "pbf_set_collider_reaction: hipMemsetAsync failed");
-    if (rc) {
-      ctx->reactionOn = false;
-      return rc;
-    }
+  if (want) {  // everything a step will need exists before the event: the records, their counter, the pose the kernels read
+    if (int rc = ensure_reaction(ctx)) return rc;
+    if (int rc = ensure(ctx, ctx->pushCtl, 8)) return rc;
+    if (!ctx->col.posed)
+      if (int rc = collider_pose_identity(ctx)) return rc;
+    if (hipMemsetAsync(ctx->pushCtl.p, 0, 8, ctx->stream) != hipSuccess) return fail(ctx, PBF_ERR_HIP, "pbf_set_collider_reaction: hipMemsetAsync failed");
   }
-  if (int rc = collider_drop_graphs(ctx)) return rc;  // (other delta-p kernels, and the sort's clear comes or goes)
-  ctx->reactionOn = want;
-  ctx->pushAt = 0, ctx->pushRows = -1;
-  return PBF_OK;
+  // (other delta-p kernels, and the sort's clear comes or goes)
+  return (want ? ctx->col.reaction_enabled() : ctx->col.reaction_disabled()) ? collider_drop_graphs(ctx) : PBF_OK;
 }
 
 int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out) {
   if (!ctx) return PBF_ERR_INVALID;
   if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_reaction: out == NULL");
-  if (!ctx->reactionOn) return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: not enabled (pbf_set_collider_reaction)");
-  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: no collider set (pbf_set_collider)");
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
-  if (!record_current(ctx, ctx->pushAt))
+  if (!ctx->col.reaction) return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: not enabled (pbf_set_collider_reaction)");
+  if (int rc = collider_needed(ctx, "pbf_collider_reaction")) return rc;
+  if (!push_current(ctx))
     return fail(ctx, PBF_ERR_STATE, "pbf_collider_reaction: no step since the reaction was enabled or the arrays last changed");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return ctx->fp64 ? collider_reaction_impl<double>(ctx, out) : collider_reaction_impl<float>(ctx, out);
@@ -2745,15 +2731,10 @@ int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body) {
     const char *why = nullptr;
     if (colliderbody::check(body, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
   }
-  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_body: no collider set (pbf_set_collider)");
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (int rc = collider_needed(ctx, "pbf_set_collider_body")) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!body) {  // off: the solid stays where it is, as an ordinary pose; the reaction stays on
-    if (!ctx->bodyOn) return PBF_OK;
-    if (int rc = collider_drop_graphs(ctx)) return rc;
-    ctx->bodyOn = false;
-    return PBF_OK;
-  }
+  if (!body)  // off: the solid stays where it is, as an ordinary pose; the reaction stays on
+    return ctx->col.body_cleared() ? collider_drop_graphs(ctx) : PBF_OK;
   if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;  // (a no-op when it is on already)
   if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
   if (int rc = ensure(ctx, ctx->bodyRec, sizeof(colliderbody::Record))) return rc;
@@ -2767,20 +2748,16 @@ int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body) {
                        ctx->colliderPose.as<ColliderPose<float>>());
   // (with friction on, sums of a pass that ran before this call were taken against another pose and other velocities: the
   // body as placed here does not receive them)
-  if (ctx->frictionOn)
+  if (ctx->col.friction)
     hipLaunchKernelGGL(k_friction_pending_clear, dim3(1), dim3(1), 0, ctx->stream, ctx->frictionCtl.as<colliderfriction::Ctl>());
   LAUNCH_CHECK(ctx);
-  if (!ctx->bodyOn) {  // off -> on selects another launch sequence; a re-placed body changes no key and drops no graph
-    if (int rc = collider_drop_graphs(ctx)) return rc;
-    ctx->bodyOn = true, ctx->colliderPosed = true;
-  }
-  return PBF_OK;
+  return ctx->col.body_set() ? collider_drop_graphs(ctx) : PBF_OK;  // (a re-placed body changes no key and drops no graph)
 }
 
 int pbf_collider_body_state(pbf_ctx *ctx, struct pbf_collider_body_state *out) {
   if (!ctx) return PBF_ERR_INVALID;
   if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_body_state: out == NULL");
-  if (!ctx->bodyOn) return fail(ctx, PBF_ERR_STATE, "pbf_collider_body_state: no body set (pbf_set_collider_body)");
+  if (!ctx->col.body) return fail(ctx, PBF_ERR_STATE, "pbf_collider_body_state: no body set (pbf_set_collider_body)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   uint32_t seq;
   HIPCHK(ctx, ctx->hostBody.arm(seq));
@@ -2800,16 +2777,11 @@ int pbf_set_collider_friction(pbf_ctx *ctx, const pbf_collider_friction *f) {
     const char *why = nullptr;
     if (colliderfriction::check(f, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
   }
-  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_friction: no collider set (pbf_set_collider)");
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
+  if (int rc = collider_needed(ctx, "pbf_set_collider_friction")) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!f) {  // off: the launch sequence without the pass; the reaction stays on
-    if (!ctx->frictionOn) return PBF_OK;
-    if (int rc = collider_drop_graphs(ctx)) return rc;
-    ctx->frictionOn = false, ctx->frictionRan = false;
-    return PBF_OK;
-  }
-  const bool turnOn = !ctx->frictionOn;
+  if (!f)  // off: the launch sequence without the pass; the reaction stays on
+    return ctx->col.friction_cleared() ? collider_drop_graphs(ctx) : PBF_OK;
+  const bool turnOn = !ctx->col.friction;
   if (turnOn) {  // everything a step will need is allocated here
     if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;  // (a no-op when it is on already)
     if (int rc = ensure(ctx, ctx->frictionRec, sizeof(pbf_collider_friction))) return rc;
@@ -2820,19 +2792,15 @@ int pbf_set_collider_friction(pbf_ctx *ctx, const pbf_collider_friction *f) {
   hipLaunchKernelGGL(k_friction_store, dim3(1), dim3(1), 0, ctx->stream, *f, ctx->frictionRec.as<pbf_collider_friction>(),
                      ctx->frictionCtl.as<colliderfriction::Ctl>(), turnOn ? 1 : 0);
   LAUNCH_CHECK(ctx);
-  if (turnOn) {  // off -> on selects another launch sequence; a rewritten record changes no key and drops no graph
-    if (int rc = collider_drop_graphs(ctx)) return rc;
-    ctx->frictionOn = true, ctx->frictionRan = false;
-  }
-  return PBF_OK;
+  return ctx->col.friction_set() ? collider_drop_graphs(ctx) : PBF_OK;  // (a rewritten record changes no key and drops no graph)
 }
 
 int pbf_collider_friction_reaction(pbf_ctx *ctx, pbf_collider_wrench *out) {
   if (!ctx) return PBF_ERR_INVALID;
   if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_friction_reaction: out == NULL");
-  if (ctx->comm || ctx->slabActive || ctx->slabConfigured) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);
-  if (!ctx->frictionOn) return fail(ctx, PBF_ERR_STATE, "pbf_collider_friction_reaction: friction is off (pbf_set_collider_friction)");
-  if (!ctx->frictionRan) return fail(ctx, PBF_ERR_STATE, "pbf_collider_friction_reaction: no step since friction was turned on");
+  if (int rc = collider_refuse_slab(ctx)) return rc;
+  if (!ctx->col.friction) return fail(ctx, PBF_ERR_STATE, "pbf_collider_friction_reaction: friction is off (pbf_set_collider_friction)");
+  if (!ctx->col.friction_sums_ready()) return fail(ctx, PBF_ERR_STATE, "pbf_collider_friction_reaction: no step since friction was turned on");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   uint32_t seq;
   HIPCHK(ctx, ctx->hostFriction.arm(seq));
@@ -3089,9 +3057,9 @@ int pbf_read_buffer(pbf_ctx *ctx, int which, void *host, size_t bytes) {
       src = ctx->wwPot.p, avail = std::min(ctx->n * v, ctx->wwPot.cap);
       break;
     case PBF_BUF_COLLIDER_PUSH:
-      if (!ctx->reactionOn || !record_current(ctx, ctx->pushAt))
+      if (!ctx->col.reaction || !push_current(ctx))
         return fail(ctx, PBF_ERR_STATE, "no sort since the collider reaction was enabled or the arrays last changed (pbf_set_collider_reaction)");
-      if (ctx->pushRows > 0) {  // the records are in row order: into the Morton order, as PBF_BUF_PSTAR's are
+      if (ctx->col.records_by_row()) {  // the records are in row order: into the Morton order, as PBF_BUF_PSTAR's are
         if (int rc = ensure(ctx, ctx->pushOut, std::max<size_t>(ctx->cap, 1) * 2 * v)) return rc;
         if (ctx->fp64)
           hipLaunchKernelGGL((k_push_to_morton<double>), grid_for(std::max<size_t>(ctx->n, 1)), dim3(BLOCK), 0, ctx->stream, uint32_t(ctx->n),
