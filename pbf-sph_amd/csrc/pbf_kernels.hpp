@@ -2475,8 +2475,14 @@ __global__ __launch_bounds__(BLOCK) void k_gather_from_lists(StepConsts<N> c, ty
 // with wave shuffles (__shfl_xor) before one lane writes the result.  Lists of very different length then cost a wave
 // max(ceil(len / COOP)) trips over 64 / COOP particles instead of max(len) over 64, and every lane's loop is COOP
 // times shorter.  The summation ORDER differs from the reference walk (COOP interleaved partial sums, then a tree),
-// so results agree with the oracle to rounding, not bit for bit: tests hold it to the stated tolerance
-// (<= 1e-3 world units per step).  Same [block][slot][thread] lists as k_gather_from_lists.
+// so results agree with the oracle to rounding, not bit for bit.  What holds these kernels is a PER-PARTICLE BAR on lambda
+// and on the delta-p move, stage by stage, against the float64 all-pairs evaluation: the roundings of pair_geom, add_bf
+// and end() counted one by one, plus g(n_i) sum |t| for the running sums — which holds for any order of the additions, so
+// the tree costs the bar nothing (tests/core_ref.py; tests/test_core_paths_gpu.py runs every <N, Op, COOP> under it,
+// PRECISE and FAST, with obstacles — begin() false inside a live group —, NBR_OVERFLOW particles — lane 0 walks alone —,
+// lists that end inside a two-entry trip and n that is no multiple of BLOCK / COOP).  launch_gather reaches this kernel in
+// GATHER_FROM_LISTS mode only: delta-p always, lambda only with split_build 4 / 5 (with the default 8 it rides on the
+// list build, one lane per particle).  Same [block][slot][thread] lists as k_gather_from_lists.
 template <typename N, typename Op, int COOP>
 __global__ __launch_bounds__(BLOCK) void k_gather_from_lists_coop(StepConsts<N> c, typename Op::Args args,
                                                                   const uint32_t *__restrict__ key,

@@ -90,11 +90,16 @@ def fast_allowance(value):
 class Pairs:
     """The all-pairs geometry every record shares, with the pair-term bars of pair_geom and of the two kernels."""
 
-    def __init__(self, ps, h, dtype, cells=None):
+    def __init__(self, ps, h, dtype, cells=None, fast=False):
+        """fast: the counts of pair_geom's FAST branch in place of the PRECISE ones (tests/core_ref.py lists them); the six
+        records of this module keep the PRECISE counts under PBF_FLAG_FAST_MATH too, as they were validated"""
         self.h, self.dtype = h, np.dtype(dtype)
         self.uN = float(np.finfo(dtype).eps) / 2
         self.u = u = self.uN + float(np.finfo(np.float64).eps) / 2
         self.ps, self.cells = ps, cells
+        # roundings of r and of Q = (h - r)^2 / r after d2's 5 u (2.5 u once the root is taken)
+        rsq = 2.0 if self.dtype == np.float64 else 0.0           # fast_rsq(double) = 1 / sqrt: two; v_rsq_f32: no count
+        self.cr, self.cQ = (2.5 + rsq + 1.0, 1.0 + 2.5 + rsq + 1.0) if fast else (3.5, 5.5)
         d = ps[:, None, :] - ps[None, :, :]
         r = np.sqrt((d * d).sum(-1))
         if cells is not None:
@@ -108,13 +113,13 @@ class Pairs:
         rs = np.where(self.spiky, r, 1.0)
         self.rs = rs
         hr = np.where(self.spiky, np.maximum(h - r, 0.0), 0.0)
-        self.hr, self.dhr = hr, 4.5 * u * h
+        self.hr, self.dhr = hr, (self.cr + 1.0) * u * h
         K = abs(NV.spiky_factor(h))
         Q = hr * hr / rs
         self.sA = K * Q
-        self.sE = np.where(self.spiky, K * (self.g(8.5) * Q + (2.0 * hr + self.dhr) * self.dhr / rs), 0.0)
+        self.sE = np.where(self.spiky, K * (self.g(self.cQ + 3.0) * Q + (2.0 * hr + self.dhr) * self.dhr / rs), 0.0)
         d2 = np.where(self.inH, np.maximum(h * h - np.where(self.inH, r, 0.0) ** 2, 0.0), 0.0)
-        dd = 9.0 * u * h * h + u * d2
+        dd = (2.0 * self.cr + 2.0) * u * h * h + u * d2
         K6 = NV.poly6_factor(h)
         self.wA = K6 * d2 ** 3
         self.wE = np.where(self.inH, K6 * ((d2 + dd) ** 3 - d2 ** 3 + self.g(5) * (d2 + dd) ** 3), 0.0)
