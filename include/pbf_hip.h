@@ -91,7 +91,9 @@ int pbf_abi_version(void);
  * 0 = sized from the particle count), "row_diffuse" (DEFAULT 1, with row_major: the colour diffusion walks the row-major copy, one
  * wave per segment of 64 x cells, runs staged by LDS-DMA, sums applied in place; 0 = per-cell sums on the Morton order, beside
  * the iterations), "diffuse_cap" (diagnostic: records in that kernel's LDS tile, 0 = default 640), "sdf_cull" (pbf_sdf_from_mesh / pbf_set_collider_mesh only: 1 = a wave skips the
- * triangles whose bounding sphere is out of its brick's reach; DEFAULT 1, 0 = every pair).  Every setting of these
+ * triangles whose bounding sphere is out of its brick's reach; DEFAULT 1, 0 = every pair), "sdf_launch_pairs" (diagnostic, the
+ * same calls and pbf_mesh_winding: the cap on lane-triangle pairs per launch of the distance fold and of the winding fold,
+ * 0 = the default, 2^33 for the distance; a small cap lets a test reach the split across launches).  Every setting of these
  * is bit-identical.  Unknown names return PBF_ERR_INVALID. */
 int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value);
 
@@ -443,7 +445,43 @@ int pbf_collider_friction_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);    /
  * flag bits.  The slab refusals are pbf_set_collider's (PBF_ERR_STATE).  A refusal leaves the ctx, its collider and phi
  * untouched.  stats (may be NULL): pairs_total = nodes x triangles, pairs_tested = the pairs the kernel evaluated — equal
  * with "sdf_cull" 0, fewer with 1 (the default); the field's bytes are the same either way.  The work is split over launches of at most
- * 2^33 lane-triangle pairs so that no single kernel runs for seconds. */
+ * 2^33 lane-triangle pairs so that no single kernel runs for seconds.
+ *
+ * Sign by winding number (PBF_MESH_SIGN_WINDING; combines with PBF_MESH_NEGATE; bit 1 of flags stays unknown).  With the
+ * flag pbf_sdf_from_mesh and pbf_set_collider_mesh take the mesh as a triangle SOUP: open, misoriented, duplicated and
+ * interpenetrating triangles are accepted, and pbf_mesh_soup_records replaces pbf_mesh_records as the check.  The unsigned
+ * distance is the fold above — the same expressions, the same order, the strict < — on the soup's a, b, c; the sign is the
+ * generalised winding number's (Jacobson, Kavan & Sorkine-Hornung 2013, ACM TOG 32(4); solid angles by van Oosterom &
+ * Strackee 1983), which needs no adjacency.  Without the flag nothing changes: every kernel, record and refusal is as above.
+ * Everything is in N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it; sqrt and divides are IEEE;
+ * u . v as above.
+ *   p as the distance fold forms it;   a = A - p   b = B - p   c = C - p          (A, B, C: record values)
+ *   la = sqrt(a . a)   lb = sqrt(b . b)   lc = sqrt(c . c)
+ *   x = (b_y c_z - b_z c_y, b_z c_x - b_x c_z, b_x c_y - b_y c_x)      num = a . x
+ *   den = ((la lb) lc + (a . b) lc) + ((b . c) la + (c . a) lb)
+ *   S += atan2(num, den)          ascending triangle index, from S = 0
+ *   w = S / N(2 pi)                                   (pbf_mesh_winding's output)
+ *   neg = best > 0 && S > N(pi)                       (a node on the mesh keeps the existing +0 / -0 convention)
+ *   phi = (neg != negate) ? -sqrt(best) : sqrt(best)
+ * atan2 is the device library's and has no bit contract, so the sign and w are held by tolerance (DESIGN 5f states the
+ * bar); sqrt(best) stays bit for bit the fold's.  w is 1 inside a closed outward mesh and 0 outside; for an open mesh it is
+ * the share of the sphere of directions the mesh covers, and the solid is where w > 1/2.  Within rounding of a face num
+ * changes sign and w jumps by 1: the field's own discontinuity.  Every pair is evaluated (a solid angle has no exact cull);
+ * stats still describe the distance fold.  Limits: the distance is to the nearest triangle, buried sheets included, so a
+ * union of interpenetrating parts has small |phi| at its inner faces (phi is still negative there); an open sheet without
+ * volume has w < 1/2 everywhere and is no solid; zero-area triangles are refused, not dropped; no mesh is repaired.
+ *
+ * pbf_mesh_soup_records is plain host code beside pbf_mesh_records (no ctx, no GPU): the records of the soup, a, b, c formed
+ * in double and rounded to N once, 9 values per triangle; records == NULL checks only.  It refuses only what the kernels
+ * cannot survive — mesh, vertices or triangles NULL; a count zero or >= 2^31; a vertex that is not finite; an index >=
+ * n_vertices; a triangle of zero area in double — with PBF_ERR_INVALID, the message in pbf_last_error(NULL), `records`
+ * untouched and `info` as pbf_mesh_records leaves it in the same case.  On success `info` is complete: boundary,
+ * non-manifold and misoriented edges are reports here, not refusals.
+ *
+ * pbf_mesh_winding returns the winding-number field itself, w above, N[dims product] in pbf_set_collider's order: for
+ * voxelising, and for checking an asset before trusting it.  The lattice checks and the slab refusals are
+ * pbf_sdf_from_mesh's; a refused mesh is PBF_ERR_INVALID with pbf_mesh_soup_records' message; so are lattice == NULL and
+ * w == NULL.  A refusal leaves the ctx, its collider and w untouched.  It synchronises and is never part of a step. */
 typedef struct pbf_mesh {
   uint64_t n_vertices, n_triangles;
   const double *vertices;      /* 3 per vertex, world units */
@@ -455,12 +493,17 @@ typedef struct pbf_mesh_info { /* filled on success AND on a mesh that is refuse
   double aabb_min[3], aabb_max[3];
 } pbf_mesh_info;
 typedef struct pbf_mesh_sdf_stats { uint64_t pairs_total /* nodes x triangles */, pairs_tested; } pbf_mesh_sdf_stats;
-enum { PBF_MESH_NEGATE = 1u << 0 };  /* solid OUTSIDE the mesh: a cavity the fluid lives in */
+enum {
+  PBF_MESH_NEGATE = 1u << 0,        /* solid OUTSIDE the mesh: a cavity the fluid lives in */
+  PBF_MESH_SIGN_WINDING = 1u << 2   /* a triangle soup signed by the winding number (above) */
+};
 int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records /* N[30 n_triangles] */, pbf_mesh_info *info);
 int pbf_sdf_from_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
                       void *phi /* N[dims product] */, pbf_mesh_sdf_stats *stats /* may be NULL */);
 int pbf_set_collider_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
                           pbf_mesh_sdf_stats *stats /* may be NULL */);
+int pbf_mesh_soup_records(const pbf_mesh *mesh, int fp64, void *records /* N[9 n_triangles] */, pbf_mesh_info *info);
+int pbf_mesh_winding(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, void *w /* N[dims product] */);
 
 /* ---- particle state (replaces the std::vector<Particle>& in/out argument, src/sph.hpp:124) */
 int pbf_upload(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type, const void *mass, const void *pos,

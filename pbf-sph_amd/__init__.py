@@ -29,6 +29,7 @@ from .capi import (  # noqa: F401
     FLAG_STAGE_TIMING,
     LIB_PATH,
     MESH_NEGATE,
+    MESH_SIGN_WINDING,
     Mesh,
     MeshInfo,
     MeshSdfStats,
@@ -51,6 +52,7 @@ from .capi import (  # noqa: F401
     default_params,
     lib,
     mesh_records,
+    mesh_soup_records,
     mesh_struct,
     scene_cubes,
     scene_dambreak,

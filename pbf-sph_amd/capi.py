@@ -25,7 +25,9 @@ WW_SPRAY, WW_FOAM, WW_BUBBLE = 0, 1, 2
 DIAG_DENSITY = 1 << 0
 SAMPLE_VELOCITY, SAMPLE_COLOUR = 1 << 0, 1 << 1
 MESH_NEGATE = 1 << 0
+MESH_SIGN_WINDING = 1 << 2
 MESH_RECORD = 30
+MESH_SOUP_RECORD = 9
 
 
 class PbfError(RuntimeError):
@@ -274,6 +276,8 @@ _SIGS = {
     "pbf_mesh_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
     "pbf_sdf_from_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.c_void_p, C.POINTER(MeshSdfStats)]),
     "pbf_set_collider_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
+    "pbf_mesh_soup_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
+    "pbf_mesh_winding": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_void_p]),
     "pbf_create": (C.c_int, [C.POINTER(Desc), C.POINTER(C.c_void_p)]),
     "pbf_destroy": (None, [C.c_void_p]),
     "pbf_last_error": (C.c_char_p, [C.c_void_p]),
@@ -498,6 +502,25 @@ def mesh_records(vertices, triangles, fp64=False):
     return rec, info.as_dict()
 
 
+def mesh_soup_records(vertices, triangles, fp64=False):
+    """pbf_mesh_soup_records (host only, no GPU): the records of a triangle soup for the winding-number sign -> (records (nt, 9)
+    of N: a, b, c; info dict, complete: boundary, non-manifold and misoriented edges are reports here).  A mesh that is
+    refused raises PbfError; its .info holds what was measured."""
+    m, keep = mesh_struct(vertices, triangles)
+    rec = np.zeros((len(keep[1]), MESH_SOUP_RECORD), np.float64 if fp64 else np.float32)
+    info = MeshInfo()
+    rc = lib().pbf_mesh_soup_records(C.byref(m), int(bool(fp64)), _vp(rec), C.byref(info))
+    if rc < 0:
+        e = PbfError(f"pbf_mesh_soup_records failed ({rc}): {lib().pbf_last_error(None).decode()}")
+        e.info = info.as_dict()
+        raise e
+    return rec, info.as_dict()
+
+
+def _mesh_flags(negate, winding):
+    return (MESH_NEGATE if negate else 0) | (MESH_SIGN_WINDING if winding else 0)
+
+
 def _lattice_struct(origin, spacing, dims, margin=0.0):
     sdf = ColliderSdf()
     sdf.dims[:] = [int(v) for v in dims]
@@ -676,27 +699,38 @@ class Solver:
         self._chk(self.L.pbf_read_buffer(self.ctx, BUF_COLLIDER_PUSH, _vp(a), a.nbytes), "read collider push records")
         return a
 
-    def sdf_from_mesh(self, vertices, triangles, origin, spacing, dims, negate=False):
+    def sdf_from_mesh(self, vertices, triangles, origin, spacing, dims, negate=False, winding=False):
         """pbf_sdf_from_mesh: the signed distance to a closed triangle mesh (counter-clockwise from outside) on the lattice
         origin + (i, j, k) * spacing, computed on the device -> (phi of shape dims, negative inside the mesh; negate: outside),
-        dict(pairs_total, pairs_tested))"""
+        dict(pairs_total, pairs_tested)).  winding: the mesh is a triangle soup signed by the winding number
+        (PBF_MESH_SIGN_WINDING): open, misoriented and non-manifold meshes are accepted."""
         m, keep = mesh_struct(vertices, triangles)
         sdf = _lattice_struct(origin, spacing, dims)
         phi = np.zeros([int(v) for v in dims], self.dtype)
         st = MeshSdfStats()
-        self._chk(self.L.pbf_sdf_from_mesh(self.ctx, C.byref(m), C.byref(sdf), MESH_NEGATE if negate else 0, _vp(phi), C.byref(st)),
+        self._chk(self.L.pbf_sdf_from_mesh(self.ctx, C.byref(m), C.byref(sdf), _mesh_flags(negate, winding), _vp(phi), C.byref(st)),
                   "pbf_sdf_from_mesh")
         return phi, dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
 
-    def set_collider_mesh(self, vertices, triangles, origin, spacing, dims, margin=0.0, negate=False):
+    def set_collider_mesh(self, vertices, triangles, origin, spacing, dims, margin=0.0, negate=False, winding=False):
         """pbf_set_collider_mesh: the lattice of sdf_from_mesh computed and installed as the collider without leaving the
         device -> dict(pairs_total, pairs_tested)"""
         m, keep = mesh_struct(vertices, triangles)
         sdf = _lattice_struct(origin, spacing, dims, margin)
         st = MeshSdfStats()
-        self._chk(self.L.pbf_set_collider_mesh(self.ctx, C.byref(m), C.byref(sdf), MESH_NEGATE if negate else 0, C.byref(st)),
+        self._chk(self.L.pbf_set_collider_mesh(self.ctx, C.byref(m), C.byref(sdf), _mesh_flags(negate, winding), C.byref(st)),
                   "pbf_set_collider_mesh")
         return dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
+
+    def mesh_winding(self, vertices, triangles, origin, spacing, dims):
+        """pbf_mesh_winding: the generalised winding number of a triangle soup at the lattice's nodes, computed on the device ->
+        w of shape dims: 1 inside a closed outward mesh, 0 outside, the covered share of the sphere of directions for an open
+        one (the solid of sdf_from_mesh(winding=True) is where w > 1/2)"""
+        m, keep = mesh_struct(vertices, triangles)
+        sdf = _lattice_struct(origin, spacing, dims)
+        w = np.zeros([int(v) for v in dims], self.dtype)
+        self._chk(self.L.pbf_mesh_winding(self.ctx, C.byref(m), C.byref(sdf), _vp(w)), "pbf_mesh_winding")
+        return w
 
     def collider_sample(self, p, points):
         """The collider's device function at world points (pbf_collider_sample) -> dict(phi (n,) interpolated distance, +inf

@@ -27,6 +27,7 @@
 #include "pbf_anisotropy.hpp"
 #include "pbf_aniso_field.hpp"
 #include "pbf_mesh_sdf.hpp"
+#include "pbf_mesh_winding.hpp"
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 #include "pbf_collider_state.hpp"
@@ -243,6 +244,8 @@ struct pbf_ctx {
   Mailbox<WrenchRecord> hostFriction;
   // "sdf_cull": pbf_sdf_from_mesh / pbf_set_collider_mesh skip the triangles out of a brick's reach (same bytes, 5 - 7 x faster)
   bool sdfCull = true;
+  // "sdf_launch_pairs": the cap on lane-triangle pairs per launch of the distance fold and the winding fold (0 = each fold's own)
+  uint64_t sdfLaunchPairs = 0;
   // pbf_set_sources / pbf_set_drains (ompsph.hpp:93-118 on resident state): the settings as given, their device images in N,
   // the compaction's per-tile counts and total, the pinned words of the drained count's read-back {total, sequence number}
   std::vector<pbf_source> sources;
@@ -1607,6 +1610,10 @@ int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value) {
     ctx->diffuseCap = uint32_t(value);
   }
   else if (n == "sdf_cull") ctx->sdfCull = value != 0;
+  else if (n == "sdf_launch_pairs") {
+    if (value < 0) return fail(ctx, PBF_ERR_INVALID, "sdf_launch_pairs: 0 (default) or the cap on pairs per launch");
+    ctx->sdfLaunchPairs = uint64_t(value);
+  }
   else if (n == "nbr_chunks") {  // diagnostic: size of the lists' second tier (before the first upload; 0 = capacity / 8 + 1024)
     if (ctx->cap) return fail(ctx, PBF_ERR_STATE, "nbr_chunks must be set before the first upload");
     ctx->nbrChunksOpt = uint32_t(value);
@@ -2562,15 +2569,20 @@ template <typename N>
 int mesh_sdf_impl(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lat, uint32_t flags, size_t nodes, DevBuf &fresh,
                   pbf_mesh_sdf_stats *stats) {
   const size_t nt = size_t(mesh->n_triangles);
-  std::vector<N> rec(size_t(meshsdf::RECORD) * nt), bnd(4 * nt);
+  const bool winding = (flags & PBF_MESH_SIGN_WINDING) != 0, negate = (flags & PBF_MESH_NEGATE) != 0;
+  const int stride = winding ? meshsdf::SOUP_RECORD : meshsdf::RECORD;
+  std::vector<N> rec(size_t(stride) * nt), bnd(4 * nt);
   const char *why = nullptr;
-  if (meshsdf::build_records(mesh, sizeof(N) == 8, rec.data(), nullptr, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  const int built = winding ? meshsdf::build_soup_records(mesh, sizeof(N) == 8, rec.data(), nullptr, &why)
+                            : meshsdf::build_records(mesh, sizeof(N) == 8, rec.data(), nullptr, &why);
+  if (built != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
   meshsdf::SdfLattice<N> L;
   N slack;
-  meshsdf::prepare<N>(lat->dims, lat->origin, lat->spacing, rec.data(), nt, &L, bnd.data(), &slack);
+  meshsdf::prepare<N>(lat->dims, lat->origin, lat->spacing, rec.data(), nt, stride, &L, bnd.data(), &slack);
   const size_t bricks = meshsdf::brick_count(L);  // (< 2^31: at most the node count)
 
-  DevBuf dRec, dBnd, dSign, dTested;
+  DevBuf dRec, dBnd, dSign, dTested, dSum;
+  if (winding) HIPCHK(ctx, hipMalloc(&dSum.p, nodes * sizeof(N)));
   HIPCHK(ctx, hipMalloc(&fresh.p, nodes * sizeof(N)));
   fresh.cap = nodes * sizeof(N);
   HIPCHK(ctx, hipMalloc(&dRec.p, rec.size() * sizeof(N)));
@@ -2580,8 +2592,11 @@ int mesh_sdf_impl(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *la
   ctx->allocEpoch++;
   HIPCHK(ctx, hipMemcpyAsync(dRec.p, rec.data(), rec.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(dBnd.p, bnd.data(), bnd.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, meshsdf::launch_fold<N>(ctx->stream, L, dRec.as<const N>(), dBnd.as<const N>(), nt, ctx->sdfCull, (flags & PBF_MESH_NEGATE) != 0,
-                                      slack, fresh.as<N>(), dSign.as<uint8_t>(), dTested.as<unsigned long long>()));
+  HIPCHK(ctx, meshsdf::launch_fold<N>(ctx->stream, L, dRec.as<const N>(), dBnd.as<const N>(), nt, ctx->sdfCull, negate, slack, fresh.as<N>(),
+                                      dSign.as<uint8_t>(), dTested.as<unsigned long long>(), ctx->sdfLaunchPairs, winding));
+  if (winding)  // the lattice holds best: the winding fold's last launch turns it into phi
+    HIPCHK(ctx, meshsdf::launch_winding<N>(ctx->stream, L, dRec.as<const N>(), nt, meshsdf::FINISH_PHI, negate, dSum.as<N>(), fresh.as<N>(),
+                                           ctx->sdfLaunchPairs));
   std::vector<uint64_t> slots(stats ? bricks : 0);
   if (stats) HIPCHK(ctx, hipMemcpyAsync(slots.data(), dTested.p, bricks * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (rec, bnd and the scratch buffers are locals)
@@ -2595,15 +2610,37 @@ int mesh_sdf_impl(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *la
 int mesh_sdf_run(pbf_ctx *ctx, const char *who, const pbf_mesh *mesh, const pbf_collider_sdf *lat, uint32_t flags, bool install,
                  DevBuf &fresh, size_t *nodes, pbf_mesh_sdf_stats *stats) {
   if (!lat) return fail(ctx, PBF_ERR_INVALID, std::string(who) + ": lattice == NULL");
-  if (flags & ~uint32_t(PBF_MESH_NEGATE)) return fail(ctx, PBF_ERR_INVALID, std::string(who) + ": unknown flag bits");
+  if (flags & ~uint32_t(PBF_MESH_NEGATE | PBF_MESH_SIGN_WINDING)) return fail(ctx, PBF_ERR_INVALID, std::string(who) + ": unknown flag bits");
   if (int rc = collider_lattice_check(ctx, who, lat, install, false, nodes)) return rc;
   {  // the mesh, before anything is allocated (mesh_sdf_impl builds the records of the ctx's type)
     const char *why = nullptr;
-    if (meshsdf::build_records(mesh, 0, nullptr, nullptr, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+    const int rc = (flags & PBF_MESH_SIGN_WINDING) ? meshsdf::build_soup_records(mesh, 0, nullptr, nullptr, &why)
+                                                   : meshsdf::build_records(mesh, 0, nullptr, nullptr, &why);
+    if (rc != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return ctx->fp64 ? mesh_sdf_impl<double>(ctx, mesh, lat, flags, *nodes, fresh, stats)
                    : mesh_sdf_impl<float>(ctx, mesh, lat, flags, *nodes, fresh, stats);
+}
+// pbf_mesh_winding: the soup records on the host, the winding fold alone on the device, w copied to the caller's array
+template <typename N> int mesh_winding_impl(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lat, size_t nodes, void *w) {
+  const size_t nt = size_t(mesh->n_triangles);
+  std::vector<N> rec(size_t(meshsdf::SOUP_RECORD) * nt);
+  const char *why = nullptr;
+  if (meshsdf::build_soup_records(mesh, sizeof(N) == 8, rec.data(), nullptr, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  meshsdf::SdfLattice<N> L;
+  for (int a = 0; a < 3; ++a) L.dims[a] = lat->dims[a], L.bricks[a] = (lat->dims[a] + 3u) / 4u, L.origin[a] = N(lat->origin[a]);
+  L.spacing = N(lat->spacing);
+  DevBuf dRec, dSum;
+  HIPCHK(ctx, hipMalloc(&dRec.p, rec.size() * sizeof(N)));
+  HIPCHK(ctx, hipMalloc(&dSum.p, nodes * sizeof(N)));
+  ctx->allocEpoch++;
+  HIPCHK(ctx, hipMemcpyAsync(dRec.p, rec.data(), rec.size() * sizeof(N), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, meshsdf::launch_winding<N>(ctx->stream, L, dRec.as<const N>(), nt, meshsdf::FINISH_W, false, dSum.as<N>(), nullptr,
+                                         ctx->sdfLaunchPairs));
+  HIPCHK(ctx, hipMemcpyAsync(w, dSum.p, nodes * sizeof(N), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (rec and the device buffers are locals; w is the caller's)
+  return PBF_OK;
 }
 // pbf_collider_reaction: the two launches of the sum and the polled read-back, as diagnostics_impl
 static_assert(sizeof(struct pbf_collider_body_state) == 31 * 8 && offsetof(BodyStateRecord, seq) == sizeof(struct pbf_collider_body_state) &&
@@ -2815,6 +2852,27 @@ int pbf_mesh_records(const pbf_mesh *mesh, int fp64, void *records, pbf_mesh_inf
   const int rc = meshsdf::build_records(mesh, fp64, records, info, &why);
   if (rc != PBF_OK) g_create_error = why;  // (no ctx: read with pbf_last_error(NULL))
   return rc;
+}
+
+int pbf_mesh_soup_records(const pbf_mesh *mesh, int fp64, void *records, pbf_mesh_info *info) {
+  const char *why = nullptr;
+  const int rc = meshsdf::build_soup_records(mesh, fp64, records, info, &why);
+  if (rc != PBF_OK) g_create_error = why;  // (no ctx: read with pbf_last_error(NULL))
+  return rc;
+}
+
+int pbf_mesh_winding(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, void *w) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!w) return fail(ctx, PBF_ERR_INVALID, "pbf_mesh_winding: w == NULL");
+  if (!lattice) return fail(ctx, PBF_ERR_INVALID, "pbf_mesh_winding: lattice == NULL");
+  size_t nodes = 0;
+  if (int rc = collider_lattice_check(ctx, "pbf_mesh_winding", lattice, false, false, &nodes)) return rc;
+  {  // the mesh, before anything is allocated
+    const char *why = nullptr;
+    if (meshsdf::build_soup_records(mesh, 0, nullptr, nullptr, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return ctx->fp64 ? mesh_winding_impl<double>(ctx, mesh, lattice, nodes, w) : mesh_winding_impl<float>(ctx, mesh, lattice, nodes, w);
 }
 
 int pbf_sdf_from_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags, void *phi,

@@ -53,7 +53,13 @@
 // Launch size.  The fold is in index order, so the host splits it over triangle ranges [t0, t1): best stays in the output
 // lattice and neg in a byte per node between launches, and the last launch writes phi.  The host keeps a launch to at most
 // 2^33 lane-triangle pairs (launch_fold below), never fewer than 16 triangles: 28 ms in float and 61 ms in double per launch
-// with every pair tested, a fifth of that with the cull (profiles/mesh_sdf.md).
+// with every pair tested, a fifth of that with the cull (profiles/mesh_sdf.md).  "sdf_launch_pairs" (pbf_set_option) lowers
+// the cap so that a test reaches the split on a small lattice.
+//
+// SOUP = true is the distance alone, for the 9-value records of a triangle soup (csrc/pbf_mesh_records.hpp,
+// build_soup_records): the same expressions in the same order and the same strict <, no normal loads and no s.  Its sign
+// comes from the winding number (csrc/pbf_mesh_winding.hpp), which reads `best` from the lattice, so the host never asks
+// this instantiation for the last launch's phi.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,7 +87,7 @@ template <typename N> struct SdfLattice {
 
 constexpr uint32_t SDF_REFRESH = 16;  // triangles between two refreshes of the cull's sqrt(best)
 
-template <typename N, bool CULL>
+template <typename N, bool CULL, bool SOUP = false>
 __global__ __launch_bounds__(256) void k_mesh_sdf(SdfLattice<N> L, const N *__restrict__ rec, const N *__restrict__ bnd, uint32_t t0,
                                                   uint32_t t1, uint32_t first, uint32_t last, uint32_t negate, N slack,
                                                   N *__restrict__ out, uint8_t *__restrict__ sign,
@@ -111,7 +117,7 @@ __global__ __launch_bounds__(256) void k_mesh_sdf(SdfLattice<N> L, const N *__re
       if (__ballot(active && !far) == 0ull) continue;
     }
     ++ran;
-    const N *__restrict__ r = rec + 30u * size_t(t);
+    const N *__restrict__ r = rec + (SOUP ? 9u : 30u) * size_t(t);
     const V3<N> a = vload(r), b = vload(r + 3), c = vload(r + 6);
     const V3<N> ab = vsub(b, a), ac = vsub(c, a), cb = vsub(c, b);
     const V3<N> ap = vsub(p, a), bp = vsub(p, b), cp = vsub(p, c);
@@ -135,14 +141,17 @@ __global__ __launch_bounds__(256) void k_mesh_sdf(SdfLattice<N> L, const N *__re
     const V3<N> qf{q0.x + q2 * ac.x, q0.y + q2 * ac.y, q0.z + q2 * ac.z};
     const bool useC = inC && !inAB;
     const V3<N> q = vsel(inA, a, vsel(inB, b, vsel(useC, c, vsel(face, qf, q0))));
-    const V3<N> n = vsel(inA, vload(r + 21), vsel(inB, vload(r + 24), vsel(useC, vload(r + 27),
-                    vsel(inAB, vload(r + 12), vsel(selCA, vload(r + 18), vsel(selBC, vload(r + 15), vload(r + 9)))))));
     const V3<N> rr = vsub(p, q);
-    const N dd = vdot(rr, rr), sn = vdot(rr, n);
+    const N dd = vdot(rr, rr);
     const bool take = dd < best;
     best = take ? dd : best;
-    const bool below = sn < N(0);
-    neg = take ? below : neg;
+    if constexpr (!SOUP) {
+      const V3<N> n = vsel(inA, vload(r + 21), vsel(inB, vload(r + 24), vsel(useC, vload(r + 27),
+                      vsel(inAB, vload(r + 12), vsel(selCA, vload(r + 18), vsel(selBC, vload(r + 15), vload(r + 9)))))));
+      const N sn = vdot(rr, n);
+      const bool below = sn < N(0);
+      neg = take ? below : neg;
+    }
   }
 
   const unsigned long long nodes = __popcll(__ballot(active));
@@ -162,8 +171,10 @@ __global__ __launch_bounds__(256) void k_mesh_sdf(SdfLattice<N> L, const N *__re
 // ---- host side: what pbf_sdf_from_mesh / pbf_set_collider_mesh (csrc/pbf_hip.hip) and tools/mesh_sdf_rate.hip share ----------
 
 // The lattice as the kernel takes it, the cull's bounding spheres (4 nt values) and its relative slack, from the records.
+// `stride` = values per record: RECORD, or SOUP_RECORD for a soup.
 template <typename N>
-void prepare(const uint32_t dims[3], const double origin[3], double spacing, const N *rec, size_t nt, SdfLattice<N> *L, N *bnd, N *slack) {
+void prepare(const uint32_t dims[3], const double origin[3], double spacing, const N *rec, size_t nt, int stride, SdfLattice<N> *L, N *bnd,
+             N *slack) {
   double reach = 0;  // M: the largest |coordinate| of a node or a vertex
   for (int a = 0; a < 3; ++a) {
     L->dims[a] = dims[a], L->bricks[a] = (dims[a] + 3u) / 4u, L->origin[a] = N(origin[a]);
@@ -171,31 +182,33 @@ void prepare(const uint32_t dims[3], const double origin[3], double spacing, con
   }
   L->spacing = N(spacing);
   for (size_t k = 0; k < nt; ++k)
-    for (int v = 0; v < 9; ++v) reach = std::max(reach, std::fabs(double(rec[size_t(RECORD) * k + v])));
+    for (int v = 0; v < 9; ++v) reach = std::max(reach, std::fabs(double(rec[size_t(stride) * k + v])));
   const double eps = double(std::numeric_limits<N>::epsilon()) / 2;
-  build_bounds<N>(rec, nt, 64 * eps * reach, bnd);
+  build_bounds<N>(rec, nt, stride, 64 * eps * reach, bnd);
   *slack = N(1) + N(16 * eps);
 }
 template <typename N> size_t brick_count(const SdfLattice<N> &L) { return size_t(L.bricks[0]) * L.bricks[1] * L.bricks[2]; }
 
 constexpr uint64_t SDF_PAIRS_PER_LAUNCH = uint64_t(1) << 33;
 
+// triangles per launch under a cap of `pairs` lane-triangle pairs (0 = `fallback`), never fewer than SDF_REFRESH
+inline uint64_t triangles_per_launch(size_t bricks, uint64_t pairs, uint64_t fallback) {
+  return std::max<uint64_t>(SDF_REFRESH, (pairs ? pairs : fallback) / (uint64_t(bricks) * 64u));
+}
+
 // The whole fold, enqueued on `stream`: rec / bnd / out (N[nodes]) / sign (a byte per node) / tested (a uint64 per brick) are
-// device pointers.  Returns the launches' error.
+// device pointers; `pairs` = the cap on lane-triangle pairs per launch (0 = SDF_PAIRS_PER_LAUNCH).  soup: rec holds 9-value
+// records and out is left holding best, not phi (csrc/pbf_mesh_winding.hpp finishes it).  Returns the launches' error.
 template <typename N>
 hipError_t launch_fold(hipStream_t stream, const SdfLattice<N> &L, const N *rec, const N *bnd, size_t nt, bool cull, bool negate, N slack,
-                       N *out, uint8_t *sign, unsigned long long *tested) {
+                       N *out, uint8_t *sign, unsigned long long *tested, uint64_t pairs = 0, bool soup = false) {
   const size_t bricks = brick_count(L);
-  const uint64_t perLaunch = std::max<uint64_t>(SDF_REFRESH, SDF_PAIRS_PER_LAUNCH / (uint64_t(bricks) * 64u));
+  const uint64_t perLaunch = triangles_per_launch(bricks, pairs, SDF_PAIRS_PER_LAUNCH);
   const dim3 grid(unsigned((bricks + 3) / 4)), block(256);
+  auto *kernel = soup ? (cull ? k_mesh_sdf<N, true, true> : k_mesh_sdf<N, false, true>) : (cull ? k_mesh_sdf<N, true> : k_mesh_sdf<N, false>);
   for (uint64_t t0 = 0; t0 < nt; t0 += perLaunch) {
-    const uint32_t t1 = uint32_t(std::min<uint64_t>(nt, t0 + perLaunch)), first = t0 == 0, last = t1 == nt;
-    if (cull)
-      hipLaunchKernelGGL((k_mesh_sdf<N, true>), grid, block, 0, stream, L, rec, bnd, uint32_t(t0), t1, first, last, uint32_t(negate), slack,
-                         out, sign, tested);
-    else
-      hipLaunchKernelGGL((k_mesh_sdf<N, false>), grid, block, 0, stream, L, rec, bnd, uint32_t(t0), t1, first, last, uint32_t(negate), slack,
-                         out, sign, tested);
+    const uint32_t t1 = uint32_t(std::min<uint64_t>(nt, t0 + perLaunch)), first = t0 == 0, last = !soup && t1 == nt;
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, L, rec, bnd, uint32_t(t0), t1, first, last, uint32_t(negate), slack, out, sign, tested);
   }
   return hipGetLastError();
 }

@@ -36,10 +36,12 @@ struct Args {
   size_t slabs = 0;                       // --slabs K: K slabs on the first matching device (in-process exchange: tests)
   double cohesion = 0, adhesion = 0;      // --surface-tension=gamma[,beta]: opt-in Akinci 2013 surface tension / adhesion
   // --collider=sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]] with --resident: opt-in static SDF collider
-  // --collider=mesh:FILE.obj[,margin[,spacing[,negate]]]: the same collider, its lattice built on the device from a closed mesh
+  // --collider=mesh:FILE.obj[,margin[,spacing[,negate[,winding]]]]: the same collider, its lattice built on the device from a
+  // closed mesh, or with the fifth field `winding` (or 1) from a triangle soup signed by the winding number
   std::string colliderShape;              // "" = off
   std::string colliderMesh;               // shape "mesh": the OBJ file
   bool colliderNegate = false;            // shape "mesh": the solid is outside the mesh
+  bool colliderWinding = false;           // shape "mesh": PBF_MESH_SIGN_WINDING (open and broken meshes are accepted)
   double colliderCfg[4] = {0, 0, 0, 0};
   double colliderMargin = 13.5;           // half the rest spacing of 27 world units
   double colliderSpacing = 0;             // 0 = h * scale / 2
@@ -120,9 +122,11 @@ struct Args {
           "                                        plane:nx,ny,nz,d (solid where n.x < d, n normalised). The fluid stays\n"
           "                                        `margin` world units off the solid (default 13.5); lattice spacing in\n"
           "                                        world units (default h * scale / 2). Single device only\n"
-          "      --collider=mesh:[FILE.obj[,margin[,spacing[,negate]]]]  The same, from a closed triangle mesh (v and triangular\n"
-          "                                        f lines, counter-clockwise from outside): the lattice is computed on the\n"
-          "                                        device. negate = 1: the solid is OUTSIDE the mesh (a cavity)\n"
+          "      --collider=mesh:[FILE.obj[,margin[,spacing[,negate[,winding]]]]]  The same, from a closed triangle mesh (v and\n"
+          "                                        triangular f lines, counter-clockwise from outside): the lattice is computed\n"
+          "                                        on the device. negate = 1: the solid is OUTSIDE the mesh (a cavity). A fifth\n"
+          "                                        field `winding` signs the distance by the winding number: open, misoriented\n"
+          "                                        and non-manifold meshes are accepted, their edge counts printed\n"
           "      --collider-motion=[vx,vy,vz[,wx,wy,wz[,px,py,pz]]]  With --resident and --collider: the solid moves rigidly, with\n"
           "                                        a linear velocity and an angular velocity (rad / s) about the pivot p, in\n"
           "                                        world units per second: the pose of a frame is set before it is stepped\n"
@@ -303,12 +307,18 @@ struct Args {
           if (colon != std::string::npos && shape == "mesh") {
             const size_t comma = v.find(',', colon);
             colliderMesh = v.substr(colon + 1, comma == std::string::npos ? std::string::npos : comma - colon - 1);
-            const auto f = comma == std::string::npos ? std::vector<double>{} : numbers(v.substr(comma + 1));
-            if (colliderMesh.empty() || f.size() > 3) throw std::runtime_error("--collider: expected mesh:FILE.obj[,margin[,spacing[,negate]]]");
+            std::string rest = comma == std::string::npos ? std::string() : v.substr(comma + 1);
+            const std::string word = ",winding";  // the fifth field, as a word
+            const bool byWord = rest.size() > word.size() && rest.compare(rest.size() - word.size(), word.size(), word) == 0;
+            if (byWord) rest.resize(rest.size() - word.size());
+            const auto f = rest.empty() ? std::vector<double>{} : numbers(rest);
+            if (colliderMesh.empty() || f.size() > (byWord ? 3u : 4u) || (byWord && f.size() != 3))
+              throw std::runtime_error("--collider: expected mesh:FILE.obj[,margin[,spacing[,negate[,winding]]]]");
             colliderShape = shape;
             if (f.size() > 0) colliderMargin = f[0];
             if (f.size() > 1) colliderSpacing = f[1];
             if (f.size() > 2) colliderNegate = f[2] != 0;
+            colliderWinding = byWord || (f.size() > 3 && f[3] != 0);
             if (!(colliderMargin >= 0) || !(colliderSpacing >= 0)) throw std::runtime_error("--collider: margin and spacing must be >= 0");
             continue;
           }

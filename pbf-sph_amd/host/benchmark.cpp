@@ -234,18 +234,24 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       const objmesh::Mesh mesh = objmesh::read(args.colliderMesh);
       pbf_mesh view{mesh.vertices.size() / 3, mesh.triangles.size() / 3, mesh.vertices.data(), mesh.triangles.data()};
       pbf_mesh_info info{};
-      if (pbf_mesh_records(&view, 0, nullptr, &info) != PBF_OK) {
+      // the pre-check: a closed 2-manifold, or with `winding` a soup the kernels can survive
+      if ((args.colliderWinding ? pbf_mesh_soup_records(&view, 0, nullptr, &info) : pbf_mesh_records(&view, 0, nullptr, &info)) != PBF_OK) {
         std::cerr << args.colliderMesh << ": " << pbf_last_error(nullptr) << " (edges " << info.n_edges << ", boundary " << info.boundary_edges
                   << ", non-manifold " << info.nonmanifold_edges << ", misoriented " << info.misoriented_edges << ", degenerate triangles "
                   << info.degenerate_triangles << ")" << std::endl;
         return 1;
       }
       pbf_mesh_sdf_stats stats{};
-      solver.setColliderMesh(mesh.vertices, mesh.triangles, dims, origin, spacing, args.colliderMargin, args.colliderNegate, &stats);
-      std::cout << "Collider             : mesh " << args.colliderMesh << (args.colliderNegate ? " (negated)" : "") << ", " << view.n_triangles
-                << " triangles, volume " << info.volume << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2] << ", spacing "
-                << spacing << ", margin " << args.colliderMargin << ", pairs tested " << stats.pairs_tested << " / " << stats.pairs_total
-                << std::endl;
+      solver.setColliderMesh(mesh.vertices, mesh.triangles, dims, origin, spacing, args.colliderMargin, args.colliderNegate, &stats,
+                             args.colliderWinding);
+      std::cout << "Collider             : mesh " << args.colliderMesh << (args.colliderNegate ? " (negated)" : "")
+                << (args.colliderWinding ? " (winding sign)" : "") << ", " << view.n_triangles << " triangles, volume " << info.volume
+                << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2] << ", spacing " << spacing << ", margin "
+                << args.colliderMargin << ", pairs tested " << stats.pairs_tested << " / " << stats.pairs_total;
+      if (args.colliderWinding)
+        std::cout << ", boundary " << info.boundary_edges << ", non-manifold " << info.nonmanifold_edges << ", misoriented "
+                  << info.misoriented_edges;
+      std::cout << std::endl;
     } else {
     const double *g = args.colliderCfg;
     const double nl = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);

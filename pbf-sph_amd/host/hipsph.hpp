@@ -435,10 +435,12 @@ public:
   // The same collider from a closed triangle mesh (pbf_set_collider_mesh; no reference counterpart): vertices = 3 doubles per
   // vertex in world units, triangles = 3 indices per triangle, counter-clockwise seen from outside.  The lattice of `dims`
   // nodes at origin + (i, j, k) * spacing is filled with the signed distance on the device (negative inside the mesh; negate:
-  // the solid is OUTSIDE, a cavity the fluid lives in) and installed.  A single-device feature, like setCollider.
+  // the solid is OUTSIDE, a cavity the fluid lives in) and installed.  winding: the mesh is a triangle soup signed by the
+  // winding number (PBF_MESH_SIGN_WINDING) — open, misoriented and non-manifold meshes are accepted.  A single-device
+  // feature, like setCollider.
   Solver &setColliderMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
                           const std::array<double, 3> &origin, double spacing, double margin, bool negate = false,
-                          pbf_mesh_sdf_stats *stats = nullptr) {
+                          pbf_mesh_sdf_stats *stats = nullptr, bool winding = false) {
     if (multi()) throw std::runtime_error("a collider is a single-device feature");
     pbf_mesh mesh{};
     mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
@@ -446,8 +448,24 @@ public:
     pbf_collider_sdf sdf{};
     for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
     sdf.spacing = spacing, sdf.margin = margin, sdf.phi = nullptr;
-    check(pbf_set_collider_mesh(ctx_, &mesh, &sdf, negate ? uint32_t(PBF_MESH_NEGATE) : 0u, stats), "pbf_set_collider_mesh");
+    const uint32_t flags = (negate ? uint32_t(PBF_MESH_NEGATE) : 0u) | (winding ? uint32_t(PBF_MESH_SIGN_WINDING) : 0u);
+    check(pbf_set_collider_mesh(ctx_, &mesh, &sdf, flags, stats), "pbf_set_collider_mesh");
     return *this;
+  }
+  // The winding-number field of a triangle soup on that lattice (pbf_mesh_winding): 1 inside a closed outward mesh, 0
+  // outside, the covered share of the sphere of directions for an open one; node (i, j, k) at (i * dims[1] + j) * dims[2] + k.
+  std::vector<N> meshWinding(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
+                             const std::array<double, 3> &origin, double spacing) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    pbf_mesh mesh{};
+    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
+    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
+    pbf_collider_sdf sdf{};
+    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
+    sdf.spacing = spacing, sdf.phi = nullptr;
+    std::vector<N> w(size_t(dims[0]) * dims[1] * dims[2]);
+    check(pbf_mesh_winding(ctx_, &mesh, &sdf, w.data()), "pbf_mesh_winding");
+    return w;
   }
   Solver &clearCollider() {
     if (!multi()) check(pbf_set_collider(ctx_, nullptr), "pbf_set_collider");
