@@ -776,10 +776,17 @@ enum GatherMode { GATHER_PLAIN = 0, GATHER_SAVE_LISTS = 1, GATHER_FROM_LISTS = 2
 
 // Row-major iterations apply to the default configuration only (neighbour lists, lambda riding on the build, one lane per
 // particle, eager launches); everything else keeps the Morton walk.
+// The last condition is the PRECONDITION of the row kernels' 32-bit candidate offsets (load_at(), pbf_kernels.hpp): every row
+// slot a list can name, times the bytes of a candidate, fits 32 bits.  A list names slots below the count its build ran
+// with.  That is ctx->n as stage_lambda sees it — which evaluates this function itself, after the sort has set the live
+// count, in a slab step the one after assembly — and the sort stage's own evaluation, with the pre-sort count (dead slots
+// included, never less than the live one), only decides whether the copy is written.  The delta-p launches do not come
+// through here: row_offsets_fit() holds them to the same bound.
+bool row_offsets_fit(const pbf_ctx *ctx) { return uint64_t(ctx->n) * (ctx->fp64 ? sizeof(vec4<double>) : sizeof(vec4<float>)) <= ROW_BYTES_MAX; }
 bool row_mode(const pbf_ctx *ctx) {
   return ctx->rowMajor > 0 && ctx->gatherKind == 1 && ctx->splitBuild == 8 && ctx->coop == 0 && ctx->reuseLists &&
          !ctx->fuseDiffuse && ctx->graphMode <= 0 &&
-         !(ctx->desc.flags & PBF_FLAG_NO_LDS) && uint64_t(ctx->n) * (ctx->fp64 ? 32u : 16u) <= 0xFFFFFFFFull;
+         !(ctx->desc.flags & PBF_FLAG_NO_LDS) && row_offsets_fit(ctx);
 }
 template <typename N> RowWalk row_walk(pbf_ctx *ctx) {
   return RowWalk{ctx->linTable.as<const uint32_t>(), ctx->rowXYZ.as<const uint32_t>(), ctx->rowSlotOf.as<const uint32_t>(),
@@ -1151,6 +1158,8 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
   StageTimer t(ctx, ST_DELTA);
   const int s = ctx->st.cur;
   if (ctx->st.delta_on_rows()) {  // list-driven delta-p on the row-major copy
+    // (the lists are those of a lambda launch that went through row_mode(); the count has not grown since, or the state would not be here)
+    if (!row_offsets_fit(ctx)) return fail(ctx, PBF_ERR_STATE, "the row-major copy has outgrown its 32-bit candidate offsets");
     const int rin = ctx->st.rcur, rout = 1 - rin;
     const uint32_t *key = ctx->key[s].as<const uint32_t>(), *table = ctx->table.as<const uint32_t>();
     const typename Op::Args a = args({ctx->rowPstar[rin].as<const vec4<N>>(), ctx->rowPstar[rout].as<vec4<N>>(), ctx->rowType.as<const uint8_t>(), ctx->rowQpos.as<uint2>()});

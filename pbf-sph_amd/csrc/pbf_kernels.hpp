@@ -778,6 +778,20 @@ template <typename N> __device__ inline bool maybe_within_h(const vec4<N> &a, co
 // code in the SAME candidate order, so their results are bit-identical to each other and to the oracle.
 // ------------------------------------------------------------------------------------------------
 
+// The ops that run on the row-major copy (LambdaOp, DeltaOp) have a second form of load(), load_at(): the candidate at a
+// 32-bit BYTE offset from its array's base.  The base is a kernel argument and stays in scalar registers, the lane supplies
+// the offset alone (global_load v, v_off, s[base]: no 64-bit address per candidate).  row_byte_offset(slot) is one shift.
+// PRECONDITION, held on the host where the row-major path is chosen (row_mode(), pbf_hip.hip): n * sizeof(vec4<N>) <= 2^32 - 1,
+// n being the live count that bounds every row slot a list can name.
+constexpr uint64_t ROW_BYTES_MAX = 0xFFFFFFFFull;
+template <typename N> __host__ __device__ constexpr uint32_t row_slot_shift() { return sizeof(vec4<N>) == 16 ? 4u : 5u; }
+static_assert((sizeof(vec4<float>) == 1u << row_slot_shift<float>()) && (sizeof(vec4<double>) == 1u << row_slot_shift<double>()),
+              "a row slot's byte offset is slot << row_slot_shift");
+template <typename N> __device__ inline uint32_t row_byte_offset(uint32_t slot) { return slot << row_slot_shift<N>(); }
+template <typename V> __device__ inline const V *row_candidate(const V *base, uint32_t byteOff) {
+  return reinterpret_cast<const V *>(reinterpret_cast<const char *>(base) + byteOff);
+}
+
 // diffuse (ompsph.hpp:188-207), Jacobi like the OpenCL kernel (ocl/oclsph_kernel.h:67-93)
 template <typename N> struct DiffuseOp {
   using Src = vec4<N>;
@@ -849,6 +863,15 @@ template <typename N, bool FAST> struct LambdaOp {
     return v;
 #else
     return a.pstar[b];
+#endif
+  }
+  __device__ static Src load_at(const Args &a, uint32_t byteOff) {  // (row_byte_offset)
+#ifdef PBF_LAMBDA_X4
+    Src v = *row_candidate(a.pstar, byteOff);
+    asm volatile("" : "+v"(v.w));
+    return v;
+#else
+    return *row_candidate(a.pstar, byteOff);
 #endif
   }
   vec4<N> pa;
@@ -939,6 +962,7 @@ template <typename N, bool FAST, int COLLIDE = COLLIDE_OFF> struct DeltaOp {
   __device__ bool near(const StepConsts<N> &c, const Src &pb) const { return maybe_within_h<N>(pa, pb, c.h2filter); }
   __host__ __device__ static const Src *src(const Args &a) { return a.pstarIn; }
   __device__ static Src load(const Args &a, uint32_t b) { return a.pstarIn[b]; }
+  __device__ static Src load_at(const Args &a, uint32_t byteOff) { return *row_candidate(a.pstarIn, byteOff); }  // (row_byte_offset)
   vec4<N> pa;
   N ax, ay, az;
   __device__ bool begin(const StepConsts<N> &c, const Args &a, uint32_t i) {
@@ -1648,7 +1672,12 @@ struct NbrWriter {
     }
   }
 };
-// ... and as a reader sees it
+// ... and as a reader sees it.  Two rules for whoever turns an entry into an address:
+//   * only slots below the list's length hold entries.  The rows and chunks are reused from launch to launch and from scene to
+//     scene, so a slot at or beyond the length holds an older list's entry or uninitialised memory: it is selected away (or
+//     not read at all) BEFORE it is shifted into an address, never after;
+//   * an entry is a row slot (or a Morton index) below the n its build ran with.  On the row-major copy the readers shift it
+//     into a 32-bit byte offset (row_byte_offset), which row_mode() on the host allows: n * sizeof(vec4<N>) <= 2^32 - 1.
 struct NbrReader {
   const uint32_t *row, *extra;
   uint32_t cnt;  // NBR_OVERFLOW: walk
@@ -2200,6 +2229,9 @@ template <typename N, typename Op, int W, int LMAX = 32, int FW = 4>
 __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typename Op::Args args, const uint2 *__restrict__ qpos,
                                                          RowWalk rw, NbrLists lists) {
   static_assert(4 * W + 2 <= QPOS_PAD, "qpos padding");
+  // (a lane stages at most LMAX - 1 + 2 W entries, so a drain trip starts at q <= that count rounded down to FW and reads
+  // slots up to q + FW - 1 whether they are taken or not)
+  static_assert((LMAX + 2 * W) % FW == 0, "the drain's last trip reads FW slots inside the staging list");
   __shared__ uint32_t list[(LMAX + 2 * W) * BLOCK];  // per-lane staging: a trip appends up to 2 W past LMAX - 1
   const uint32_t tid = threadIdx.x;
   const uint32_t chunk = xcd_chunk();
@@ -2242,10 +2274,20 @@ __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typena
     for (uint32_t q = 0; __any(q < nl); q += FW) {  // FW survivors per trip: their gathers and pair terms interleave
       uint32_t b[FW];
       typename Op::Src cnd[FW];
+      // The FW staged slots of the trip in one straight block, taken or not (q + FW <= LMAX + 2 W, asserted above), then the
+      // select: a slot at or beyond the lane's count holds an older batch's entry or nothing at all, and is selected away
+      // BEFORE it is shifted into an address — the lane takes itself, masked in add_bf.
+      uint32_t e[FW];
 #pragma unroll
-      for (uint32_t w = 0; w < FW; ++w) b[w] = q + w < nl ? staged((q + w) * SLOT) : i;
+      for (uint32_t w = 0; w < FW; ++w) e[w] = staged((q + w) * SLOT);
 #pragma unroll
-      for (uint32_t w = 0; w < FW; ++w) cnd[w] = Op::load(args, b[w]);
+      for (uint32_t w = 0; w < FW; ++w) asm volatile("" : "+v"(e[w]));  // (or the compiler folds a read and its select back into a read under its own exec region)
+#pragma unroll
+      for (uint32_t w = 0; w < FW; ++w) b[w] = q + w < nl ? e[w] : i;
+      // the survivors through load_at(): a 32-bit byte offset from pStar's scalar base (row_byte_offset; every staged entry is
+      // a row slot below c.n, and row_mode() on the host holds n * sizeof(vec4<N>) to 32 bits)
+#pragma unroll
+      for (uint32_t w = 0; w < FW; ++w) cnd[w] = Op::load_at(args, row_byte_offset<N>(b[w]));
       if (rowsOnly) {
 #pragma unroll
         for (uint32_t w = 0; w < FW; ++w) NbrWriter::put_rows(blockRows, bt, q + w, b[w]);
@@ -2446,13 +2488,22 @@ __global__ __launch_bounds__(BLOCK) void k_gather_from_lists(StepConsts<N> c, ty
     constexpr uint32_t RW = sizeof(N) == 4 ? PBF_READER_W : 4;
     // (list_trip's steps, written out: behind a function the compiler drops the first slot's bound test and allocates this
     // kernel's scalar registers differently — the iteration's hottest reader keeps the text it was measured with)
+    // ROWS: the candidates come through load_at(), a 32-bit byte offset from the array's scalar base (row_byte_offset; the
+    // precondition is row_mode()'s on the host).  The entries keep their bound test, here and in the chunk loop below: an entry
+    // from a slot at or beyond the lane's length is stale or uninitialised memory and must never be shifted into an address —
+    // such a slot is not even read, the lane takes itself (masked in add_bf).  (Reading all RW slots of a trip in one straight
+    // block and selecting afterwards was measured and lost: profiles/row_gathers_1m.md.)
+    auto gather = [&](uint32_t b) {
+      if constexpr (ROWS) return Op::load_at(args, row_byte_offset<N>(b));
+      else return Op::load(args, b);
+    };
     for (uint32_t q = 0; q < head; q += RW) {
       uint32_t b[RW];
       typename Op::Src cnd[RW];
 #pragma unroll
       for (uint32_t w = 0; w < RW; ++w) b[w] = q + w < head ? rd.row[(q + w) * BLOCK] : i;
 #pragma unroll
-      for (uint32_t w = 0; w < RW; ++w) cnd[w] = Op::load(args, b[w]);
+      for (uint32_t w = 0; w < RW; ++w) cnd[w] = gather(b[w]);
 #pragma unroll
       for (uint32_t w = 0; w < RW; ++w) op.add_bf(c, cnd[w], q + w < head);
     }
@@ -2462,7 +2513,7 @@ __global__ __launch_bounds__(BLOCK) void k_gather_from_lists(StepConsts<N> c, ty
 #pragma unroll
       for (uint32_t w = 0; w < 4; ++w) b[w] = q + w < tail ? rd.extra[q + w] : i;
 #pragma unroll
-      for (uint32_t w = 0; w < 4; ++w) cnd[w] = Op::load(args, b[w]);
+      for (uint32_t w = 0; w < 4; ++w) cnd[w] = gather(b[w]);
 #pragma unroll
       for (uint32_t w = 0; w < 4; ++w) op.add_bf(c, cnd[w], q + w < tail);
     }
