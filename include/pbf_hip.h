@@ -148,7 +148,7 @@ int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion);
  * gives the same bytes; "coop" 2 / 4 / 8 differs at rounding level as it does without a collider.
  * Limitations: there is no restitution term — finalise derives the velocity from the projected position, as it does for
  * the box — and friction is an opt-in pass of its own (pbf_set_collider_friction below).  Whitewater's diffuse particles
- * and the observers (surface, sampling, diagnostics, anisotropy) do not see the collider.  One static collider per ctx.  A
+ * and the observers (surface, sampling, diagnostics, anisotropy) do not see the collider.  One collider and one static scenery lattice (pbf_set_scenery below) per ctx.  A
  * triangle mesh becomes a lattice through pbf_sdf_from_mesh / pbf_set_collider_mesh below.
  *
  * pbf_collider_sample is the window onto that device function, for debugging an uploaded collider: its own synchronising
@@ -504,6 +504,60 @@ int pbf_set_collider_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider
                           pbf_mesh_sdf_stats *stats /* may be NULL */);
 int pbf_mesh_soup_records(const pbf_mesh *mesh, int fp64, void *records /* N[9 n_triangles] */, pbf_mesh_info *info);
 int pbf_mesh_winding(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, void *w /* N[dims product] */);
+
+/* Scenery: a second, STATIC signed-distance lattice beside the collider (no reference counterpart).  Opt-in: with no
+ * scenery set every launch and every byte of a step is what it is without this feature.  The collider is the one solid
+ * that may carry a pose, a body and friction; the scenery is the harbour, the bowl, the ramp or the floor around it.  It
+ * lives in the world frame and never has a pose, a reaction, friction or a body.
+ *
+ * Setting.  pbf_set_scenery takes a lattice as pbf_set_collider does: rounded to N, kept in a buffer of its own, checked
+ * by the same code with the same refusals in the same order (PBF_ERR_INVALID: a dim < 2; a dims product >= 2^31; a
+ * non-finite origin, spacing or margin; spacing <= 0; margin < 0; phi == NULL; a NaN in phi — infinities are legal).
+ * sdf == NULL clears the scenery and frees the lattice.  pbf_set_scenery_mesh is pbf_set_collider_mesh's build, flags
+ * and refusals included, installed as scenery.  The setting persists until it is replaced or cleared and allocates
+ * nothing inside a step.  It needs no collider; installing, replacing or clearing the collider leaves the scenery alone,
+ * and the pose, the body and friction never touch it.  Slab mode is not supported: setting scenery on a slab-attached or
+ * slab-configured ctx, and pbf_slab_step(s) / a delta-p stage of a slab-configured ctx with scenery set, return
+ * PBF_ERR_STATE, as with a collider.  A refusal leaves the ctx, its scenery and its collider unchanged.
+ *
+ * The contract of a delta-p launch.  Everything is in N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not
+ * reach it.  q is the input of the static contract above: after the world-frame box clamp and the division by scale.
+ *   Scenery alone (no collider lattice): q' = the static contract on q with the scenery's lattice — exactly the kernels
+ *   and arguments pbf_set_collider with that lattice would run.
+ *   Collider and scenery together:
+ *     q1 = the POSED contract on q with the collider's lattice (the pose record holds the identity while no pose is set:
+ *          every value compares equal to the static function's, a zero may change its sign); the reaction record is
+ *          updated from (q, q1) exactly as with pbf_set_collider_reaction alone
+ *     q2 = the static contract on q1 with the scenery's lattice
+ *   q2 is stored and the quantised copy is formed from it.  The scenery writes no record: A, B and hits describe the
+ *   collider's push alone, with r taken at q1, so the friction pass, the body stage and pbf_collider_reaction see exactly
+ *   what they would see without scenery for the same q.  The scenery comes last, so where both press on a particle the
+ *   static wall wins, and the box wins over both through each projection's own second clamp; the K iterations converge the
+ *   rest.  A lane that hits neither keeps its bits.  Obstacles and ghost copies are never moved.  Every gather path gives
+ *   the same bytes, "coop" 2 / 4 / 8 within its usual rounding.
+ *
+ * The reaction is on whenever both lattices are installed, as it is with a body or with friction: the combined kernel is
+ * the reaction's kernel plus one projection, and no variant without records is built.  The call that completes the pair
+ * (pbf_set_scenery / pbf_set_scenery_mesh with a collider present, pbf_set_collider / pbf_set_collider_mesh with scenery
+ * present) turns the records on if they are off, allocating what pbf_set_collider_reaction(ctx, 1) allocates before
+ * anything is changed, so a failed allocation leaves everything as it was.  While both are installed
+ * pbf_set_collider_reaction(ctx, 0) returns PBF_ERR_STATE.  Clearing either solid leaves the reaction on.
+ *
+ * Captured graphs.  Every pbf_set_scenery / pbf_set_scenery_mesh call, clearing included, changes a captured step's key
+ * and drops the captured graphs (and synchronises, once): a replay never runs on a replaced or freed lattice.
+ *
+ * pbf_scenery_sample is pbf_collider_sample on the scenery's lattice (always the static function): the same arguments,
+ * outputs and refusals, PBF_ERR_STATE without scenery.
+ *
+ * Limitations: the body does not collide with the scenery — only its centre bounds hold it.  There is no friction
+ * against the scenery and no reaction on it.  Whitewater's diffuse particles and the observers do not see it.  One
+ * collider and one static scenery lattice per ctx: several static solids are composed into the scenery's lattice on the
+ * host, by the min of their distances.  Not in slab mode. */
+int pbf_set_scenery(pbf_ctx *ctx, const pbf_collider_sdf *sdf);   /* NULL clears and frees the lattice */
+int pbf_set_scenery_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
+                         pbf_mesh_sdf_stats *stats /* may be NULL */);
+int pbf_scenery_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const double *points /* 3n, world */,
+                       void *phi /* N[n] */, void *moved /* N[3n], solver frame */, uint8_t *hit /* [n] */);
 
 /* ---- particle state (replaces the std::vector<Particle>& in/out argument, src/sph.hpp:124) */
 int pbf_upload(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type, const void *mass, const void *pos,

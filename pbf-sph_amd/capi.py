@@ -278,6 +278,9 @@ _SIGS = {
     "pbf_set_collider_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
     "pbf_mesh_soup_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
     "pbf_mesh_winding": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_void_p]),
+    "pbf_set_scenery": (C.c_int, [C.c_void_p, C.POINTER(ColliderSdf)]),
+    "pbf_set_scenery_mesh": (C.c_int, [C.c_void_p, C.POINTER(Mesh), C.POINTER(ColliderSdf), C.c_uint32, C.POINTER(MeshSdfStats)]),
+    "pbf_scenery_sample": (C.c_int, [C.c_void_p, C.POINTER(Params), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbf_create": (C.c_int, [C.POINTER(Desc), C.POINTER(C.c_void_p)]),
     "pbf_destroy": (None, [C.c_void_p]),
     "pbf_last_error": (C.c_char_p, [C.c_void_p]),
@@ -740,6 +743,40 @@ class Solver:
         o = dict(phi=np.zeros(n, self.dtype), moved=np.zeros((n, 3), self.dtype), hit=np.zeros(n, np.uint8))
         self._chk(self.L.pbf_collider_sample(self.ctx, C.byref(p), n, _vp(pts), _vp(o["phi"]), _vp(o["moved"]), _vp(o["hit"])),
                   "pbf_collider_sample")
+        return o
+
+    def set_scenery(self, phi, origin=(0.0, 0.0, 0.0), spacing=1.0, margin=0.0):
+        """Opt-in scenery (pbf_set_scenery, include/pbf_hip.h): a second, static lattice in the world frame beside the collider,
+        given as set_collider's is; delta-p projects the fluid out of it after the collider.  It never has a pose, a body,
+        friction or a reaction; with a collider installed as well the reaction records are on.  phi=None clears it."""
+        if phi is None:
+            self._chk(self.L.pbf_set_scenery(self.ctx, None), "pbf_set_scenery")
+            return self
+        a = np.ascontiguousarray(phi, self.dtype)
+        if a.ndim != 3:
+            raise ValueError("set_scenery: phi must have shape (nx, ny, nz)")
+        sdf = _lattice_struct(origin, spacing, a.shape, margin)
+        sdf.phi = a.ctypes.data
+        self._chk(self.L.pbf_set_scenery(self.ctx, C.byref(sdf)), "pbf_set_scenery")
+        return self
+
+    def set_scenery_mesh(self, vertices, triangles, origin, spacing, dims, margin=0.0, negate=False, winding=False):
+        """pbf_set_scenery_mesh: set_collider_mesh's build, installed as the scenery -> dict(pairs_total, pairs_tested)"""
+        m, keep = mesh_struct(vertices, triangles)
+        sdf = _lattice_struct(origin, spacing, dims, margin)
+        st = MeshSdfStats()
+        self._chk(self.L.pbf_set_scenery_mesh(self.ctx, C.byref(m), C.byref(sdf), _mesh_flags(negate, winding), C.byref(st)),
+                  "pbf_set_scenery_mesh")
+        return dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
+
+    def scenery_sample(self, points, params):
+        """The static device function on the scenery's lattice at world points (pbf_scenery_sample) -> the dict of
+        collider_sample()"""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = len(pts)
+        o = dict(phi=np.zeros(n, self.dtype), moved=np.zeros((n, 3), self.dtype), hit=np.zeros(n, np.uint8))
+        self._chk(self.L.pbf_scenery_sample(self.ctx, C.byref(params), n, _vp(pts), _vp(o["phi"]), _vp(o["moved"]), _vp(o["hit"])),
+                  "pbf_scenery_sample")
         return o
 
     def surface_state(self):

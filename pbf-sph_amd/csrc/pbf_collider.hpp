@@ -41,6 +41,24 @@
 // the identity pose every value compares equal to the static function's (x * 1, + 0 and - 0 are exact; a zero may change
 // its sign, and an infinite coordinate becomes a NaN, which is outside as well).
 //
+// With scenery (pbf_set_scenery; the same text as the header's): a second, STATIC lattice in the world frame beside the
+// collider.  Everything is in N, in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it.  q is the input
+// of the static contract: after the world-frame box clamp and the division by scale.
+//
+//   scenery alone (no collider lattice):  q' = the static contract on q with the scenery's lattice — exactly the kernels and
+//                                         arguments pbf_set_collider with that lattice would run
+//   collider and scenery together:        q1 = the POSED contract on q with the collider's lattice (the pose record holds the
+//                                              identity while no pose is set: a zero may change its sign); the reaction
+//                                              record is updated from (q, q1) exactly as DeltaOp<.., COLLIDE_REACT> does
+//                                         q2 = the static contract on q1 with the scenery's lattice
+//
+// q2 is stored, and the quantised copy is formed from it.  The scenery writes no record: A, B and hits describe the
+// collider's push alone, with r taken at q1, so the friction pass, the body stage and pbf_collider_reaction see exactly what
+// they would see without scenery for the same q.  The scenery comes last, so where both press on a particle the static wall
+// wins, and the box wins over both through each projection's own second clamp; the K iterations converge the rest.  A lane
+// that hits neither keeps its bits.  Obstacles and ghost copies are never moved.  collider_eval / collider_project below are
+// used as they stand: there is no second copy of the trilinear code.
+//
 // The eight lattice loads are scalar-per-lane gathers from a read-only array that is small against L2 and shared by every
 // wave of the launch (neighbouring particles read neighbouring nodes): plain loads, nothing staged.
 #pragma once

@@ -31,6 +31,7 @@
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 #include "pbf_collider_state.hpp"
+#include "pbf_scenery_state.hpp"
 #include "pbf_collider_pose.hpp"
 #include "pbf_collider_friction.hpp"
 
@@ -150,6 +151,7 @@ struct GraphKey {
   unsigned char params[sizeof(double) * 11 + 32];  // dt, scale, force, bounds, iteration, xsph, vorticity, cohesion, adhesion
   uint64_t n;
   uint64_t collider;  // ColliderState::gen: a replay never runs on a lattice that has been replaced, nor another launch sequence
+  uint64_t scenery;   // SceneryState::gen: nor on a scenery lattice that has been replaced or freed (8 bytes: no padding for memcmp)
   int options[10];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
@@ -229,6 +231,9 @@ struct pbf_ctx {
   DevBuf colliderPhi;
   uint32_t colliderDims[3] = {0, 0, 0};
   double colliderOrigin[3] = {0, 0, 0}, colliderSpacing = 0, colliderMargin = 0;
+  // pbf_set_scenery (pbf_scenery_state.hpp): one static lattice in the world frame beside the collider, changed by
+  // scenery_install only.  The collider's events, the pose, the body and friction never touch it.
+  SceneryState<DevBuf> scenery;
   // pbf_set_collider_pose: the one ColliderPose<N> record the posed kernels read through a pointer (allocated by the first call)
   DevBuf colliderPose;
   // pbf_set_collider_reaction: the records {A, hits}, {B, 0} of DeltaOp<.., COLLIDE_REACT> (2 vec4<N> per particle, sized to
@@ -1129,6 +1134,16 @@ template <typename N> ColliderSdf<N> collider_args(const pbf_ctx *ctx) {
   s.inv = N(1) / N(ctx->colliderSpacing), s.margin = N(ctx->colliderMargin);
   return s;
 }
+// pbf_set_scenery's lattice, as the static contract takes it (all zero, phi == NULL, without one)
+bool scenery_on(const pbf_ctx *ctx) { return ctx->scenery.phi.p != nullptr; }
+template <typename N> ColliderSdf<N> scenery_args(const pbf_ctx *ctx) {
+  ColliderSdf<N> s{};
+  if (!scenery_on(ctx)) return s;
+  s.phi = ctx->scenery.phi.as<const N>();
+  for (int a = 0; a < 3; ++a) s.dims[a] = ctx->scenery.dims[a], s.origin[a] = N(ctx->scenery.origin[a]);
+  s.inv = N(1) / N(ctx->scenery.spacing), s.margin = N(ctx->scenery.margin);
+  return s;
+}
 constexpr const char *kColliderSlabError = "a collider is not supported in slab mode (pbf_set_collider(ctx, NULL) clears it)";
 bool slab_ctx(const pbf_ctx *ctx) { return ctx->comm || ctx->slabActive || ctx->slabConfigured; }
 int collider_refuse_slab(pbf_ctx *ctx) { return slab_ctx(ctx) ? fail(ctx, PBF_ERR_STATE, kColliderSlabError) : PBF_OK; }
@@ -1142,15 +1157,19 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
   using Op = DeltaOp<N, FAST, COLLIDE>;
   // (with a collider the lattice follows the stock arguments, and with a pose the pointer to its record follows the lattice)
   auto args = [&](const typename Op::ArgsPlain &plain) {
-    if constexpr (COLLIDE == COLLIDE_REACT)
+    if constexpr (COLLIDE == COLLIDE_REACT_SCENERY)  // (the scenery's lattice follows the records)
+      return typename Op::Args{{{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()}, scenery_args<N>(ctx)};
+    else if constexpr (COLLIDE == COLLIDE_REACT)
       return typename Op::Args{{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()};
     else if constexpr (COLLIDE == COLLIDE_POSED) return typename Op::Args{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()};
-    else if constexpr (COLLIDE == COLLIDE_STATIC) return typename Op::Args{plain, collider_args<N>(ctx)};
+    else if constexpr (COLLIDE == COLLIDE_STATIC)  // (a static collider, or scenery without a collider: the same kernels)
+      return typename Op::Args{plain, collider_on(ctx) ? collider_args<N>(ctx) : scenery_args<N>(ctx)};
     else return plain;
   };
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
-  if constexpr (COLLIDE == COLLIDE_REACT) {  // the records follow the index of the launch: one kind of index per step
+  if constexpr (COLLIDE == COLLIDE_REACT || COLLIDE == COLLIDE_REACT_SCENERY) {  // the records follow the index of the launch: one kind of index per step
+    if (!ctx->col.reaction) return fail(ctx, PBF_ERR_STATE, "a collider beside scenery needs the reaction records");  // (the setters keep it on)
     if (!push_current(ctx)) return fail(ctx, PBF_ERR_STATE, "the collider reaction needs a sort since it was enabled");
     if (!ctx->col.delta_indexed(ctx->st.delta_on_rows()))
       return fail(ctx, PBF_ERR_STATE, "the gather path changed between two delta-p launches of a step with the collider reaction on");
@@ -1179,16 +1198,22 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
 }
 template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
   // the one place that turns the mode into an instantiation (this order of first use fixes the kernels' order in the code object)
-  switch (ctx->col.delta_mode()) {
-    case ColliderState::DELTA_OFF: return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
-    case ColliderState::DELTA_REACT: return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);
-    case ColliderState::DELTA_POSED: return delta_run<N, FAST, COLLIDE_POSED>(ctx, p);
-    case ColliderState::DELTA_STATIC: break;
+  // Scenery alone runs the static kernels on its lattice; beside a collider it is the one mode the state header does not
+  // name (dispatched last: the instantiations before it keep their place).
+  const bool scenery = scenery_on(ctx);
+  if (!scenery || !collider_on(ctx)) {
+    switch (scenery ? ColliderState::DELTA_STATIC : ctx->col.delta_mode()) {
+      case ColliderState::DELTA_OFF: return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
+      case ColliderState::DELTA_REACT: return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);
+      case ColliderState::DELTA_POSED: return delta_run<N, FAST, COLLIDE_POSED>(ctx, p);
+      case ColliderState::DELTA_STATIC: break;
+    }
+    return delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
   }
-  return delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
+  return delta_run<N, FAST, COLLIDE_REACT_SCENERY>(ctx, p);
 }
 template <typename N> int stage_delta(pbf_ctx *ctx, const pbf_params *p) {
-  if (collider_on(ctx))
+  if (collider_on(ctx) || scenery_on(ctx))
     if (int rc = collider_refuse_slab(ctx)) return rc;
   return DISPATCH_FAST(ctx, delta_impl, ctx, p);
 }
@@ -1929,6 +1954,7 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
   k.collider = ctx->col.gen;
+  k.scenery = ctx->scenery.gen;
   const int opt[10] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
                        int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap)};
   std::memcpy(k.options, opt, sizeof(opt));
@@ -2052,7 +2078,7 @@ int pbf_stage_lambda(pbf_ctx *ctx, const pbf_params *p) {
   return DISPATCH(ctx, stage_lambda, ctx, p);
 }
 int pbf_stage_delta(pbf_ctx *ctx, const pbf_params *p) {
-  if (ctx && collider_on(ctx))
+  if (ctx && (collider_on(ctx) || scenery_on(ctx)))
     if (int rc = collider_refuse_slab(ctx)) return rc;
   if (int rc = check(ctx, p, true)) return rc;
   return DISPATCH(ctx, stage_delta, ctx, p);
@@ -2514,10 +2540,10 @@ const char *whitewater_config_error(const pbf_whitewater *g) {
 }  // namespace
 
 namespace {
-template <typename N> int set_collider_impl(pbf_ctx *ctx, const pbf_collider_sdf *sdf, size_t nodes, DevBuf &fresh) {
+template <typename N> int set_collider_impl(pbf_ctx *ctx, const char *who, const pbf_collider_sdf *sdf, size_t nodes, DevBuf &fresh) {
   const N *phi = static_cast<const N *>(sdf->phi);
   for (size_t k = 0; k < nodes; ++k)
-    if (phi[k] != phi[k]) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider: a NaN in phi");
+    if (phi[k] != phi[k]) return fail(ctx, PBF_ERR_INVALID, std::string(who) + ": a NaN in phi");
   // an allocation of its own, exactly sized: the current lattice stays in place until the new one has arrived
   HIPCHK(ctx, hipMalloc(&fresh.p, nodes * sizeof(N)));
   fresh.cap = nodes * sizeof(N);
@@ -2569,6 +2595,22 @@ int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
     if (int rc = collider_pose_identity(ctx)) return rc;
   for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
   ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
+  return PBF_OK;
+}
+
+// A collider and scenery together run DeltaOp<.., COLLIDE_REACT_SCENERY>, which writes the records: the call that completes
+// the pair (`other`: the other solid is installed) turns the reaction on if it is off.  Called once the new lattice is on the
+// device and BEFORE anything of the ctx is changed, so a failed allocation leaves everything as it was.  Clearing either solid
+// leaves the reaction on, as a cleared body does.
+int pair_needs_reaction(pbf_ctx *ctx, bool other) { return other ? pbf_set_collider_reaction(ctx, 1) : PBF_OK; }  // (a no-op when it is on)
+// the one install path of the scenery: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's
+// scenery.  Every install moves the captured steps' key; the collider, its pose, its records and its body are left alone.
+int scenery_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
+  if (int rc = collider_drop_graphs(ctx)) return rc;  // (first: they hold the old lattice's address)
+  ctx->scenery.phi = std::move(fresh);                // (frees the old lattice)
+  ctx->scenery.gen++;
+  for (int a = 0; a < 3; ++a) ctx->scenery.dims[a] = sdf ? sdf->dims[a] : 0u, ctx->scenery.origin[a] = sdf ? sdf->origin[a] : 0.0;
+  ctx->scenery.spacing = sdf ? sdf->spacing : 0.0, ctx->scenery.margin = sdf ? sdf->margin : 0.0;
   return PBF_OK;
 }
 
@@ -2681,7 +2723,8 @@ template <typename N> int collider_pose_store(pbf_ctx *ctx, const pbf_collider_p
   return PBF_OK;
 }
 template <typename N>
-int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, N *phi, N *moved, uint8_t *hit) {
+int collider_sample_impl(pbf_ctx *ctx, const ColliderSdf<N> &sdf, const ColliderPose<N> *pose, const pbf_params *p, size_t n,
+                         const double *points, N *phi, N *moved, uint8_t *hit) {
   std::vector<N> pts(3 * n);
   for (size_t k = 0; k < 3 * n; ++k) pts[k] = N(points[k]);
   const size_t e = n * sizeof(N);
@@ -2692,8 +2735,7 @@ int collider_sample_impl(pbf_ctx *ctx, const pbf_params *p, size_t n, const doub
   f.scale = N(p->scale);
   for (int a = 0; a < 3; ++a) f.minB[a] = N(p->min_bound[a]), f.maxB[a] = N(p->max_bound[a]);
   HIPCHK(ctx, hipMemcpyAsync(ctx->samplePoints.p, pts.data(), 3 * e, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL((k_collider_sample<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, collider_args<N>(ctx),
-                     ctx->col.posed ? ctx->colliderPose.as<const ColliderPose<N>>() : nullptr, f, uint32_t(n),
+  hipLaunchKernelGGL((k_collider_sample<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, sdf, pose, f, uint32_t(n),
                      ctx->samplePoints.as<const N>(), reinterpret_cast<N *>(out), reinterpret_cast<N *>(out + e),
                      reinterpret_cast<uint8_t *>(out + 4 * e));
   LAUNCH_CHECK(ctx);
@@ -2715,7 +2757,11 @@ int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   DevBuf fresh;
   if (sdf)
-    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, sdf, nodes, fresh) : set_collider_impl<float>(ctx, sdf, nodes, fresh)) return rc;
+    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, "pbf_set_collider", sdf, nodes, fresh)
+                           : set_collider_impl<float>(ctx, "pbf_set_collider", sdf, nodes, fresh))
+      return rc;
+  if (sdf)
+    if (int rc = pair_needs_reaction(ctx, scenery_on(ctx))) return rc;
   return collider_install(ctx, sdf, fresh);
 }
 
@@ -2748,6 +2794,8 @@ int pbf_set_collider_reaction(pbf_ctx *ctx, int on) {
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a body is on and needs the records (pbf_set_collider_body(ctx, NULL) first)");
   if (!want && ctx->col.why_reaction_must_stay() == ColliderState::HELD_BY_FRICTION)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: friction is on and needs the records (pbf_set_collider_friction(ctx, NULL) first)");
+  if (!want && collider_on(ctx) && scenery_on(ctx))
+    return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a collider beside scenery writes the records (clear either solid first)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (want) {  // everything a step will need exists before the event: the records, their counter, the pose the kernels read
     if (int rc = ensure_reaction(ctx)) return rc;
@@ -2905,22 +2953,69 @@ int pbf_set_collider_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider
   size_t nodes = 0;
   pbf_mesh_sdf_stats st{};
   if (int rc = mesh_sdf_run(ctx, "pbf_set_collider_mesh", mesh, lattice, flags, true, fresh, &nodes, &st)) return rc;
+  if (int rc = pair_needs_reaction(ctx, scenery_on(ctx))) return rc;
   if (int rc = collider_install(ctx, lattice, fresh)) return rc;
   if (stats) *stats = st;
   return PBF_OK;
 }
 
-int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, void *phi, void *moved, uint8_t *hit) {
+// pbf_collider_sample / pbf_scenery_sample: one check, one launch; the scenery is the static function (pose == NULL)
+static int sample_entry(pbf_ctx *ctx, const char *who, bool scenery, const pbf_params *p, size_t n, const double *points, void *phi,
+                        void *moved, uint8_t *hit) {
   if (!ctx) return PBF_ERR_INVALID;
-  if (!p) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_sample: params == NULL");
+  const std::string w = std::string(who) + ": ";
+  if (!p) return fail(ctx, PBF_ERR_INVALID, w + "params == NULL");
   if (!(p->scale > 0) || !(p->dt > 0)) return fail(ctx, PBF_ERR_INVALID, "dt and scale must be > 0");
-  if (n >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_sample: 2^31 points or more");
+  if (n >= (size_t(1) << 31)) return fail(ctx, PBF_ERR_INVALID, w + "2^31 points or more");
   if (n == 0) return PBF_OK;
-  if (!points) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_sample: points == NULL");
-  if (!collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_collider_sample: no collider set (pbf_set_collider)");
+  if (!points) return fail(ctx, PBF_ERR_INVALID, w + "points == NULL");
+  if (scenery && !scenery_on(ctx)) return fail(ctx, PBF_ERR_STATE, w + "no scenery set (pbf_set_scenery)");
+  if (!scenery && !collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, w + "no collider set (pbf_set_collider)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->fp64) return collider_sample_impl<double>(ctx, p, n, points, static_cast<double *>(phi), static_cast<double *>(moved), hit);
-  return collider_sample_impl<float>(ctx, p, n, points, static_cast<float *>(phi), static_cast<float *>(moved), hit);
+  const bool posed = !scenery && ctx->col.posed;
+  if (ctx->fp64)
+    return collider_sample_impl<double>(ctx, scenery ? scenery_args<double>(ctx) : collider_args<double>(ctx),
+                                        posed ? ctx->colliderPose.as<const ColliderPose<double>>() : nullptr, p, n, points,
+                                        static_cast<double *>(phi), static_cast<double *>(moved), hit);
+  return collider_sample_impl<float>(ctx, scenery ? scenery_args<float>(ctx) : collider_args<float>(ctx),
+                                     posed ? ctx->colliderPose.as<const ColliderPose<float>>() : nullptr, p, n, points,
+                                     static_cast<float *>(phi), static_cast<float *>(moved), hit);
+}
+int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, void *phi, void *moved, uint8_t *hit) {
+  return sample_entry(ctx, "pbf_collider_sample", false, p, n, points, phi, moved, hit);
+}
+
+// ---- the scenery: one static lattice in the world frame beside the collider (the contract: include/pbf_hip.h) ----
+int pbf_set_scenery(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
+  if (!ctx) return PBF_ERR_INVALID;
+  size_t nodes = 1;
+  if (sdf)
+    if (int rc = collider_lattice_check(ctx, "pbf_set_scenery", sdf, true, true, &nodes)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DevBuf fresh;
+  if (sdf)
+    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, "pbf_set_scenery", sdf, nodes, fresh)
+                           : set_collider_impl<float>(ctx, "pbf_set_scenery", sdf, nodes, fresh))
+      return rc;
+  if (sdf)
+    if (int rc = pair_needs_reaction(ctx, collider_on(ctx))) return rc;
+  return scenery_install(ctx, sdf, fresh);
+}
+
+int pbf_set_scenery_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags, pbf_mesh_sdf_stats *stats) {
+  if (!ctx) return PBF_ERR_INVALID;
+  DevBuf fresh;
+  size_t nodes = 0;
+  pbf_mesh_sdf_stats st{};
+  if (int rc = mesh_sdf_run(ctx, "pbf_set_scenery_mesh", mesh, lattice, flags, true, fresh, &nodes, &st)) return rc;
+  if (int rc = pair_needs_reaction(ctx, collider_on(ctx))) return rc;
+  if (int rc = scenery_install(ctx, lattice, fresh)) return rc;
+  if (stats) *stats = st;
+  return PBF_OK;
+}
+
+int pbf_scenery_sample(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, void *phi, void *moved, uint8_t *hit) {
+  return sample_entry(ctx, "pbf_scenery_sample", true, p, n, points, phi, moved, hit);
 }
 
 }  // extern "C"
@@ -3813,7 +3908,7 @@ int pbf_slab_attach(pbf_ctx *ctx, pbf_comm *comm, const uint32_t *cuts, uint32_t
 int pbf_slab_step(pbf_ctx *ctx, const pbf_params *p) { return pbf_slab_steps(ctx, p, 1); }
 int pbf_slab_steps(pbf_ctx *ctx, const pbf_params *p, uint32_t count) {
   if (int rc = check(ctx, p, false)) return rc;
-  if (collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);  // (set before the ctx was configured or attached)
+  if (collider_on(ctx) || scenery_on(ctx)) return fail(ctx, PBF_ERR_STATE, kColliderSlabError);  // (set before the ctx was configured or attached)
   if (!ctx->comm) return fail(ctx, PBF_ERR_STATE, "pbf_slab_step needs pbf_slab_attach first");
   if (surface_on(ctx))
     return fail(ctx, PBF_ERR_STATE, "surface tension is not supported in slab mode (pbf_set_surface_tension(ctx, 0, 0) turns it off)");

@@ -936,7 +936,13 @@ template <typename N, bool FAST> struct LambdaOp {
 //   A_a += delta_a                                hits += 1          (kept in A.w as N)
 //   B_x += r_y * delta_z - r_z * delta_y          (y, z cyclic; each product rounded, one subtraction, one add)
 // The sort stage clears the records once per step; every delta-p launch until the next sort accumulates into them.
-enum ColliderMode : int { COLLIDE_OFF = 0, COLLIDE_STATIC = 1, COLLIDE_POSED = 2, COLLIDE_REACT = 3 };
+//
+// COLLIDE_REACT_SCENERY (pbf_set_scenery beside a collider): the REACT block unchanged, then the static projection of the
+// scenery's lattice (world frame) on its result.  The scenery writes no record: A, B and hits describe the collider's push
+// alone, with r taken at the collider's q', so the friction pass, the body stage and pbf_collider_reaction see what they
+// would without scenery for the same q.  The scenery comes last, so where both press on a particle the static wall wins.
+// Scenery without a collider is COLLIDE_STATIC on the scenery's lattice: no instantiation of its own.
+enum ColliderMode : int { COLLIDE_OFF = 0, COLLIDE_STATIC = 1, COLLIDE_POSED = 2, COLLIDE_REACT = 3, COLLIDE_REACT_SCENERY = 4 };
 template <typename N, bool FAST, int COLLIDE = COLLIDE_OFF> struct DeltaOp {
   using Src = vec4<N>;
   struct ArgsPlain {
@@ -954,8 +960,13 @@ template <typename N, bool FAST, int COLLIDE = COLLIDE_OFF> struct DeltaOp {
   struct ArgsReact : ArgsPosed {
     vec4<N> *push;  // {A.xyz, hits}, {B.xyz, 0} per particle, indexed like pstarOut
   };
-  using Args = std::conditional_t<COLLIDE == COLLIDE_REACT, ArgsReact,
-                                  std::conditional_t<COLLIDE == COLLIDE_POSED, ArgsPosed, std::conditional_t<COLLIDE == COLLIDE_STATIC, ArgsSdf, ArgsPlain>>>;
+  struct ArgsScenery : ArgsReact {
+    ColliderSdf<N> scenery;  // pbf_set_scenery's lattice (world frame), scenery.phi != NULL; by value like sdf: uniform, in SGPRs
+  };
+  using Args = std::conditional_t<
+      COLLIDE == COLLIDE_REACT_SCENERY, ArgsScenery,
+      std::conditional_t<COLLIDE == COLLIDE_REACT, ArgsReact,
+                         std::conditional_t<COLLIDE == COLLIDE_POSED, ArgsPosed, std::conditional_t<COLLIDE == COLLIDE_STATIC, ArgsSdf, ArgsPlain>>>>;
   static constexpr bool kNeedsCandidateType = false;
   static constexpr bool kFilter = true;
   static constexpr bool kTileable = true;
@@ -1019,7 +1030,7 @@ template <typename N, bool FAST, int COLLIDE = COLLIDE_OFF> struct DeltaOp {
     x = x / c.scale, y = y / c.scale, z = z / c.scale;
     if constexpr (COLLIDE == COLLIDE_STATIC) collider_project<N>(a.sdf, c.scale, c.minB, c.maxB, x, y, z, nullptr);
     if constexpr (COLLIDE == COLLIDE_POSED) collider_project_posed<N>(a.sdf, a.pose, c.scale, c.minB, c.maxB, x, y, z, nullptr);
-    if constexpr (COLLIDE == COLLIDE_REACT) {
+    if constexpr (COLLIDE == COLLIDE_REACT || COLLIDE == COLLIDE_REACT_SCENERY) {
       const N qx = x, qy = y, qz = z;
       if (collider_project_posed<N>(a.sdf, a.pose, c.scale, c.minB, c.maxB, x, y, z, nullptr)) {
         const N dx = (x - qx) * c.scale, dy = (y - qy) * c.scale, dz = (z - qz) * c.scale;
@@ -1030,6 +1041,8 @@ template <typename N, bool FAST, int COLLIDE = COLLIDE_OFF> struct DeltaOp {
         a.push[2u * i] = A, a.push[2u * i + 1u] = B;
       }
     }
+    // (after the record: the scenery's push is no part of it)
+    if constexpr (COLLIDE == COLLIDE_REACT_SCENERY) collider_project<N>(a.scenery, c.scale, c.minB, c.maxB, x, y, z, nullptr);
     const vec4<N> out = make_vec4<N>(x, y, z, pa.w);
     a.pstarOut[i] = out;
     if (a.qpos) {

@@ -38,13 +38,18 @@ struct Args {
   // --collider=sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]] with --resident: opt-in static SDF collider
   // --collider=mesh:FILE.obj[,margin[,spacing[,negate[,winding]]]]: the same collider, its lattice built on the device from a
   // closed mesh, or with the fifth field `winding` (or 1) from a triangle soup signed by the winding number
-  std::string colliderShape;              // "" = off
-  std::string colliderMesh;               // shape "mesh": the OBJ file
-  bool colliderNegate = false;            // shape "mesh": the solid is outside the mesh
-  bool colliderWinding = false;           // shape "mesh": PBF_MESH_SIGN_WINDING (open and broken meshes are accepted)
-  double colliderCfg[4] = {0, 0, 0, 0};
-  double colliderMargin = 13.5;           // half the rest spacing of 27 world units
-  double colliderSpacing = 0;             // 0 = h * scale / 2
+  // --scenery=<the same grammar> with --resident: a second, STATIC solid beside the collider (pbf_set_scenery); combines with
+  // every --collider* flag
+  struct Solid {
+    std::string shape;                    // "" = off
+    std::string mesh;                     // shape "mesh": the OBJ file
+    bool negate = false;                  // shape "mesh": the solid is outside the mesh
+    bool winding = false;                 // shape "mesh": PBF_MESH_SIGN_WINDING (open and broken meshes are accepted)
+    double cfg[4] = {0, 0, 0, 0};
+    double margin = 13.5;                 // half the rest spacing of 27 world units
+    double spacing = 0;                   // 0 = h * scale / 2
+  };
+  Solid solid, scenery;                   // --collider, --scenery
   // --collider-motion=vx,vy,vz[,wx,wy,wz[,px,py,pz]] with --resident and --collider: the solid moves rigidly — a linear velocity
   // and an angular velocity (rad / s) about a pivot, world units per second; --collider-reaction[=every] prints the wrench
   bool colliderMoves = false;
@@ -127,6 +132,11 @@ struct Args {
           "                                        on the device. negate = 1: the solid is OUTSIDE the mesh (a cavity). A fifth\n"
           "                                        field `winding` signs the distance by the winding number: open, misoriented\n"
           "                                        and non-manifold meshes are accepted, their edge counts printed\n"
+          "      --scenery=[shape:... | mesh:...]  With --resident: a second, STATIC solid beside the collider, in --collider's\n"
+          "                                        grammar with the same defaults (the harbour, bowl, ramp or floor around a\n"
+          "                                        moving or floating collider). It stays in the world frame and has no pose,\n"
+          "                                        body, friction or reaction; the fluid is projected out of it after the\n"
+          "                                        collider. Combines with every --collider* flag. Single device only\n"
           "      --collider-motion=[vx,vy,vz[,wx,wy,wz[,px,py,pz]]]  With --resident and --collider: the solid moves rigidly, with\n"
           "                                        a linear velocity and an angular velocity (rad / s) about the pivot p, in\n"
           "                                        world units per second: the pose of a frame is set before it is stepped\n"
@@ -185,6 +195,41 @@ struct Args {
       at = comma + 1;
     }
     return out;
+  }
+
+  // one grammar and one parser for --collider and --scenery (`flag` names the option in the messages)
+  static void parseSolid(const std::string &flag, const std::string &v, Solid &s) {
+    const size_t colon = v.find(':');
+    const std::string shape = v.substr(0, colon);
+    if (colon != std::string::npos && shape == "mesh") {
+      const size_t comma = v.find(',', colon);
+      s.mesh = v.substr(colon + 1, comma == std::string::npos ? std::string::npos : comma - colon - 1);
+      std::string rest = comma == std::string::npos ? std::string() : v.substr(comma + 1);
+      const std::string word = ",winding";  // the fifth field, as a word
+      const bool byWord = rest.size() > word.size() && rest.compare(rest.size() - word.size(), word.size(), word) == 0;
+      if (byWord) rest.resize(rest.size() - word.size());
+      const auto f = rest.empty() ? std::vector<double>{} : numbers(rest);
+      if (s.mesh.empty() || f.size() > (byWord ? 3u : 4u) || (byWord && f.size() != 3))
+        throw std::runtime_error(flag + ": expected mesh:FILE.obj[,margin[,spacing[,negate[,winding]]]]");
+      s.shape = shape;
+      if (f.size() > 0) s.margin = f[0];
+      if (f.size() > 1) s.spacing = f[1];
+      if (f.size() > 2) s.negate = f[2] != 0;
+      s.winding = byWord || (f.size() > 3 && f[3] != 0);
+      if (!(s.margin >= 0) || !(s.spacing >= 0)) throw std::runtime_error(flag + ": margin and spacing must be >= 0");
+      return;
+    }
+    if (colon == std::string::npos || (shape != "sphere" && shape != "bowl" && shape != "plane"))
+      throw std::runtime_error(flag + ": expected sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]]");
+    const auto f = numbers(v.substr(colon + 1));
+    if (f.size() < 4 || f.size() > 6) throw std::runtime_error(flag + ": expected four numbers and optionally margin, spacing");
+    s.shape = shape;
+    for (int k = 0; k < 4; ++k) s.cfg[k] = f[size_t(k)];
+    if (f.size() > 4) s.margin = f[4];
+    if (f.size() > 5) s.spacing = f[5];
+    if (shape != "plane" && !(s.cfg[3] > 0)) throw std::runtime_error(flag + ": the radius must be > 0");
+    if (shape == "plane" && !(f[0] * f[0] + f[1] * f[1] + f[2] * f[2] > 0)) throw std::runtime_error(flag + ": the normal must not be zero");
+    if (!(s.margin >= 0) || !(s.spacing >= 0)) throw std::runtime_error(flag + ": margin and spacing must be >= 0");
   }
 
   // returns false if the program should exit (help / parse error), like the reference's parse()
@@ -301,39 +346,8 @@ struct Args {
           colliderReaction = std::stoull(a.substr(20));
           if (colliderReaction == 0) throw std::runtime_error("--collider-reaction: every must be >= 1");
         }
-        else if (value(i, a, "", "--collider", v)) {
-          const size_t colon = v.find(':');
-          const std::string shape = v.substr(0, colon);
-          if (colon != std::string::npos && shape == "mesh") {
-            const size_t comma = v.find(',', colon);
-            colliderMesh = v.substr(colon + 1, comma == std::string::npos ? std::string::npos : comma - colon - 1);
-            std::string rest = comma == std::string::npos ? std::string() : v.substr(comma + 1);
-            const std::string word = ",winding";  // the fifth field, as a word
-            const bool byWord = rest.size() > word.size() && rest.compare(rest.size() - word.size(), word.size(), word) == 0;
-            if (byWord) rest.resize(rest.size() - word.size());
-            const auto f = rest.empty() ? std::vector<double>{} : numbers(rest);
-            if (colliderMesh.empty() || f.size() > (byWord ? 3u : 4u) || (byWord && f.size() != 3))
-              throw std::runtime_error("--collider: expected mesh:FILE.obj[,margin[,spacing[,negate[,winding]]]]");
-            colliderShape = shape;
-            if (f.size() > 0) colliderMargin = f[0];
-            if (f.size() > 1) colliderSpacing = f[1];
-            if (f.size() > 2) colliderNegate = f[2] != 0;
-            colliderWinding = byWord || (f.size() > 3 && f[3] != 0);
-            if (!(colliderMargin >= 0) || !(colliderSpacing >= 0)) throw std::runtime_error("--collider: margin and spacing must be >= 0");
-            continue;
-          }
-          if (colon == std::string::npos || (shape != "sphere" && shape != "bowl" && shape != "plane"))
-            throw std::runtime_error("--collider: expected sphere:cx,cy,cz,r | bowl:cx,cy,cz,r | plane:nx,ny,nz,d [,margin[,spacing]]");
-          const auto f = numbers(v.substr(colon + 1));
-          if (f.size() < 4 || f.size() > 6) throw std::runtime_error("--collider: expected four numbers and optionally margin, spacing");
-          colliderShape = shape;
-          for (int k = 0; k < 4; ++k) colliderCfg[k] = f[size_t(k)];
-          if (f.size() > 4) colliderMargin = f[4];
-          if (f.size() > 5) colliderSpacing = f[5];
-          if (shape != "plane" && !(colliderCfg[3] > 0)) throw std::runtime_error("--collider: the radius must be > 0");
-          if (shape == "plane" && !(f[0] * f[0] + f[1] * f[1] + f[2] * f[2] > 0)) throw std::runtime_error("--collider: the normal must not be zero");
-          if (!(colliderMargin >= 0) || !(colliderSpacing >= 0)) throw std::runtime_error("--collider: margin and spacing must be >= 0");
-        }
+        else if (value(i, a, "", "--collider", v)) parseSolid("--collider", v, solid);
+        else if (value(i, a, "", "--scenery", v)) parseSolid("--scenery", v, scenery);
         else if (value(i, a, "", "--surface-tension", v)) {
           const size_t comma = v.find(',');
           cohesion = std::stod(v.substr(0, comma));

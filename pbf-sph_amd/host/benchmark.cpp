@@ -113,12 +113,18 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cerr << "--surface-tension is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
   }
-  const bool collider = !args.colliderShape.empty();
+  const bool collider = !args.solid.shape.empty();
   if (collider && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--collider is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
   }
   if (collider && !args.resident) std::cout << "--collider takes effect with --resident: ignored" << std::endl;
+  const bool scenery = !args.scenery.shape.empty();
+  if (scenery && (slabbed || args.allDevices || args.slabs > 0)) {
+    std::cerr << "--scenery is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
+    return 1;
+  }
+  if (scenery && !args.resident) std::cout << "--scenery takes effect with --resident: ignored" << std::endl;
   if ((args.colliderMoves || args.colliderReaction) && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--collider-motion / --collider-reaction are single-device features: they cannot be combined with --slabs / --all-devices"
               << std::endl;
@@ -136,11 +142,11 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cerr << "--collider-body and --collider-motion both own the collider's pose: give one of them" << std::endl;
     return 1;
   }
-  if (args.colliderBody && collider && args.colliderShape == "mesh") {
+  if (args.colliderBody && collider && args.solid.shape == "mesh") {
     std::cerr << "--collider-body needs --collider=sphere, bowl or plane (the lattice is built about the body's centre)" << std::endl;
     return 1;
   }
-  if (args.colliderBody && collider && args.colliderShape == "plane" && !(args.colliderBodyCfg[1] > 0)) {
+  if (args.colliderBody && collider && args.solid.shape == "plane" && !(args.colliderBodyCfg[1] > 0)) {
     std::cerr << "--collider-body with a plane needs its moments: mass,Ixx,Iyy,Izz" << std::endl;
     return 1;
   }
@@ -211,9 +217,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   sph::hip_impl::Solver<T, N> solver(N(0.1), devices, flags);
   std::array<double, 3> bodyCentre{0, 0, 0}, bodyMin{0, 0, 0}, bodyMax{0, 0, 0};
   if (surfaceTension) solver.surfaceTension(N(args.cohesion), N(args.adhesion));
-  if (collider && args.resident) {
+  // --collider / --scenery: one builder for both solids (`asScenery`: installed in the world frame through setScenery /
+  // setSceneryMesh, never about a body's centre).  false: the mesh was refused and the message printed.
+  auto installSolid = [&](const sph::driver::Args::Solid &solid, bool asScenery) -> bool {
+    const char *label = asScenery ? "Scenery              : " : "Collider             : ";
     // the analytic distance on a lattice over the box plus one spacing (float64, rounded to N at the end)
-    const double spacing = args.colliderSpacing > 0 ? args.colliderSpacing : 0.1 * double(param.scale) / 2;
+    const double spacing = solid.spacing > 0 ? solid.spacing : 0.1 * double(param.scale) / 2;
     const double lo[3] = {double(param.minBound.x), double(param.minBound.y), double(param.minBound.z)};
     const double hi[3] = {double(param.maxBound.x), double(param.maxBound.y), double(param.maxBound.z)};
     std::array<uint32_t, 3> dims;
@@ -224,59 +233,64 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     }
     // --collider-body: the lattice is the body's own frame, whose origin is the centre of mass — the sphere's centre, for a
     // plane the box's; the start pose puts it back where the static collider would stand
-    if (colliderBody)
+    if (colliderBody && !asScenery)
       for (int a = 0; a < 3; ++a) {
-        bodyCentre[size_t(a)] = args.colliderShape == "plane" ? 0.5 * (lo[a] + hi[a]) : args.colliderCfg[a];
+        bodyCentre[size_t(a)] = solid.shape == "plane" ? 0.5 * (lo[a] + hi[a]) : solid.cfg[a];
         origin[size_t(a)] -= bodyCentre[size_t(a)];
         bodyMin[size_t(a)] = lo[a], bodyMax[size_t(a)] = hi[a];
       }
-    if (args.colliderShape == "mesh") {
-      const objmesh::Mesh mesh = objmesh::read(args.colliderMesh);
+    if (solid.shape == "mesh") {
+      const objmesh::Mesh mesh = objmesh::read(solid.mesh);
       pbf_mesh view{mesh.vertices.size() / 3, mesh.triangles.size() / 3, mesh.vertices.data(), mesh.triangles.data()};
       pbf_mesh_info info{};
       // the pre-check: a closed 2-manifold, or with `winding` a soup the kernels can survive
-      if ((args.colliderWinding ? pbf_mesh_soup_records(&view, 0, nullptr, &info) : pbf_mesh_records(&view, 0, nullptr, &info)) != PBF_OK) {
-        std::cerr << args.colliderMesh << ": " << pbf_last_error(nullptr) << " (edges " << info.n_edges << ", boundary " << info.boundary_edges
+      if ((solid.winding ? pbf_mesh_soup_records(&view, 0, nullptr, &info) : pbf_mesh_records(&view, 0, nullptr, &info)) != PBF_OK) {
+        std::cerr << solid.mesh << ": " << pbf_last_error(nullptr) << " (edges " << info.n_edges << ", boundary " << info.boundary_edges
                   << ", non-manifold " << info.nonmanifold_edges << ", misoriented " << info.misoriented_edges << ", degenerate triangles "
                   << info.degenerate_triangles << ")" << std::endl;
-        return 1;
+        return false;
       }
       pbf_mesh_sdf_stats stats{};
-      solver.setColliderMesh(mesh.vertices, mesh.triangles, dims, origin, spacing, args.colliderMargin, args.colliderNegate, &stats,
-                             args.colliderWinding);
-      std::cout << "Collider             : mesh " << args.colliderMesh << (args.colliderNegate ? " (negated)" : "")
-                << (args.colliderWinding ? " (winding sign)" : "") << ", " << view.n_triangles << " triangles, volume " << info.volume
+      if (asScenery) solver.setSceneryMesh(mesh.vertices, mesh.triangles, dims, origin, spacing, solid.margin, solid.negate, &stats, solid.winding);
+      else solver.setColliderMesh(mesh.vertices, mesh.triangles, dims, origin, spacing, solid.margin, solid.negate, &stats, solid.winding);
+      std::cout << label << "mesh " << solid.mesh << (solid.negate ? " (negated)" : "")
+                << (solid.winding ? " (winding sign)" : "") << ", " << view.n_triangles << " triangles, volume " << info.volume
                 << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2] << ", spacing " << spacing << ", margin "
-                << args.colliderMargin << ", pairs tested " << stats.pairs_tested << " / " << stats.pairs_total;
-      if (args.colliderWinding)
+                << solid.margin << ", pairs tested " << stats.pairs_tested << " / " << stats.pairs_total;
+      if (solid.winding)
         std::cout << ", boundary " << info.boundary_edges << ", non-manifold " << info.nonmanifold_edges << ", misoriented "
                   << info.misoriented_edges;
       std::cout << std::endl;
     } else {
-    const double *g = args.colliderCfg;
+    const double *g = solid.cfg;
+    const std::array<double, 3> centre = asScenery ? std::array<double, 3>{0, 0, 0} : bodyCentre;
     const double nl = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
     std::vector<N> phi(size_t(dims[0]) * dims[1] * dims[2]);
     for (uint32_t i = 0; i < dims[0]; ++i)
       for (uint32_t j = 0; j < dims[1]; ++j)
         for (uint32_t k = 0; k < dims[2]; ++k) {
-          const double x = (origin[0] + i * spacing) + bodyCentre[0], y = (origin[1] + j * spacing) + bodyCentre[1],
-                       z = (origin[2] + k * spacing) + bodyCentre[2];
+          const double x = (origin[0] + i * spacing) + centre[0], y = (origin[1] + j * spacing) + centre[1],
+                       z = (origin[2] + k * spacing) + centre[2];
           double d;
-          if (args.colliderShape == "plane") d = (g[0] * x + g[1] * y + g[2] * z) / nl - g[3];
+          if (solid.shape == "plane") d = (g[0] * x + g[1] * y + g[2] * z) / nl - g[3];
           else d = std::sqrt((x - g[0]) * (x - g[0]) + (y - g[1]) * (y - g[1]) + (z - g[2]) * (z - g[2])) - g[3];
-          phi[(size_t(i) * dims[1] + j) * dims[2] + k] = N(args.colliderShape == "bowl" ? -d : d);
+          phi[(size_t(i) * dims[1] + j) * dims[2] + k] = N(solid.shape == "bowl" ? -d : d);
         }
-    solver.setCollider(dims, origin, spacing, args.colliderMargin, phi.data());
-    std::cout << "Collider             : " << args.colliderShape << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2]
-              << ", spacing " << spacing << ", margin " << args.colliderMargin << std::endl;
+    if (asScenery) solver.setScenery(dims, origin, spacing, solid.margin, phi.data());
+    else solver.setCollider(dims, origin, spacing, solid.margin, phi.data());
+    std::cout << label << solid.shape << ", lattice " << dims[0] << " x " << dims[1] << " x " << dims[2]
+              << ", spacing " << spacing << ", margin " << solid.margin << std::endl;
     }
-  }
+    return true;
+  };
+  if (collider && args.resident && !installSolid(args.solid, false)) return 1;
+  if (scenery && args.resident && !installSolid(args.scenery, true)) return 1;
   if (colliderReaction) solver.enableColliderReaction();
   if (colliderBody) {
     // at rest at the collider's centre under the fluid's own acceleration in world units (a unit mass gains constant_force *
     // scale per time: predict works in solver units), its centre kept inside the box
     pbf_collider_body body{};
-    const double *c = args.colliderBodyCfg, r = args.colliderCfg[3];
+    const double *c = args.colliderBodyCfg, r = args.solid.cfg[3];
     body.mass = c[0], body.gain = c[4];
     const double force[3] = {double(param.constantForce.x), double(param.constantForce.y), double(param.constantForce.z)};
     for (int a = 0; a < 3; ++a) {

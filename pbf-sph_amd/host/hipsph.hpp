@@ -471,6 +471,49 @@ public:
     if (!multi()) check(pbf_set_collider(ctx_, nullptr), "pbf_set_collider");
     return *this;
   }
+  // Scenery (pbf_set_scenery; no reference counterpart): a second, STATIC lattice in the world frame beside the collider, given
+  // as setCollider's is.  It never has a pose, a body, friction or a reaction; delta-p projects the fluid out of it after the
+  // collider, and with both installed the reaction records are on.  Persists until clearScenery(); installing or clearing the
+  // collider leaves it alone.  A single-device feature, like setCollider.
+  Solver &setScenery(const std::array<uint32_t, 3> &dims, const std::array<double, 3> &origin, double spacing, double margin,
+                     const N *phi) {
+    if (multi()) throw std::runtime_error("scenery is a single-device feature");
+    pbf_collider_sdf sdf{};
+    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
+    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = phi;
+    check(pbf_set_scenery(ctx_, &sdf), "pbf_set_scenery");
+    return *this;
+  }
+  // setColliderMesh's build, installed as the scenery (pbf_set_scenery_mesh)
+  Solver &setSceneryMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
+                         const std::array<double, 3> &origin, double spacing, double margin, bool negate = false,
+                         pbf_mesh_sdf_stats *stats = nullptr, bool winding = false) {
+    if (multi()) throw std::runtime_error("scenery is a single-device feature");
+    pbf_mesh mesh{};
+    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
+    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
+    pbf_collider_sdf sdf{};
+    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
+    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = nullptr;
+    const uint32_t flags = (negate ? uint32_t(PBF_MESH_NEGATE) : 0u) | (winding ? uint32_t(PBF_MESH_SIGN_WINDING) : 0u);
+    check(pbf_set_scenery_mesh(ctx_, &mesh, &sdf, flags, stats), "pbf_set_scenery_mesh");
+    return *this;
+  }
+  Solver &clearScenery() {
+    if (!multi()) check(pbf_set_scenery(ctx_, nullptr), "pbf_set_scenery");
+    return *this;
+  }
+  // The static device function on the scenery's lattice at world points (pbf_scenery_sample; it synchronises): points = 3
+  // doubles per point; phi, moved (3 per point, solver frame) and hit are resized to the point count.
+  // The scale and the box are config's.
+  void sampleScenery(const sph::SphParams<T, N, V> &config, const std::vector<double> &points, std::vector<N> &phi, std::vector<N> &moved,
+                     std::vector<uint8_t> &hit) {
+    if (multi()) throw std::runtime_error("scenery is a single-device feature");
+    const size_t n = points.size() / 3;
+    phi.resize(n), moved.resize(3 * n), hit.resize(n);
+    const pbf_params p = params(config, sph::Scene<T, N, V>{});
+    check(pbf_scenery_sample(ctx_, &p, n, points.data(), phi.data(), moved.data(), hit.data()), "pbf_scenery_sample");
+  }
   // Moving colliders (pbf_set_collider_pose; no reference counterpart): the installed lattice is read in a body frame, a world
   // point being w = rot b + trans (rot row-major, body -> world).  No upload, no synchronisation and no recapture per call;
   // persists until it is changed, clearColliderPose() or a new collider.  A single-device feature, like setCollider.
