@@ -605,22 +605,41 @@ class Solver:
         self._chk(self.L.pbf_set_surface_tension(self.ctx, float(cohesion), float(adhesion)), "pbf_set_surface_tension")
         return self
 
+    # the collider and the scenery are given, built from a mesh and sampled alike: `which` names the entry point
+    def _set_solid(self, which, phi, origin, spacing, margin):
+        entry = f"pbf_set_{which}"
+        if phi is None:
+            self._chk(getattr(self.L, entry)(self.ctx, None), entry)
+            return self
+        a = np.ascontiguousarray(phi, self.dtype)
+        if a.ndim != 3:
+            raise ValueError(f"set_{which}: phi must have shape (nx, ny, nz)")
+        sdf = _lattice_struct(origin, spacing, a.shape, margin)
+        sdf.phi = a.ctypes.data
+        self._chk(getattr(self.L, entry)(self.ctx, C.byref(sdf)), entry)
+        return self
+
+    def _set_solid_mesh(self, which, vertices, triangles, origin, spacing, dims, margin, negate, winding):
+        entry = f"pbf_set_{which}_mesh"
+        m, keep = mesh_struct(vertices, triangles)
+        sdf = _lattice_struct(origin, spacing, dims, margin)
+        st = MeshSdfStats()
+        self._chk(getattr(self.L, entry)(self.ctx, C.byref(m), C.byref(sdf), _mesh_flags(negate, winding), C.byref(st)), entry)
+        return dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
+
+    def _solid_sample(self, which, p, points):
+        entry = f"pbf_{which}_sample"
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = len(pts)
+        o = dict(phi=np.zeros(n, self.dtype), moved=np.zeros((n, 3), self.dtype), hit=np.zeros(n, np.uint8))
+        self._chk(getattr(self.L, entry)(self.ctx, C.byref(p), n, _vp(pts), _vp(o["phi"]), _vp(o["moved"]), _vp(o["hit"])), entry)
+        return o
+
     def set_collider(self, phi, origin=(0.0, 0.0, 0.0), spacing=1.0, margin=0.0):
         """Opt-in static collider (pbf_set_collider, include/pbf_hip.h): phi = signed distances in world units on a lattice
         of shape (nx, ny, nz), negative inside the solid (sdf_lattice makes one); origin = world position of node (0, 0, 0);
         delta-p keeps the fluid at phi >= margin.  phi=None clears it.  Persists in the solver."""
-        if phi is None:
-            self._chk(self.L.pbf_set_collider(self.ctx, None), "pbf_set_collider")
-            return self
-        a = np.ascontiguousarray(phi, self.dtype)
-        if a.ndim != 3:
-            raise ValueError("set_collider: phi must have shape (nx, ny, nz)")
-        sdf = ColliderSdf()
-        sdf.dims[:] = [int(v) for v in a.shape]
-        sdf.origin[:] = [float(v) for v in origin]
-        sdf.spacing, sdf.margin, sdf.phi = float(spacing), float(margin), a.ctypes.data
-        self._chk(self.L.pbf_set_collider(self.ctx, C.byref(sdf)), "pbf_set_collider")
-        return self
+        return self._set_solid("collider", phi, origin, spacing, margin)
 
     def set_collider_pose(self, rot, trans=(0.0, 0.0, 0.0)):
         """A rigid pose for the installed collider (pbf_set_collider_pose, include/pbf_hip.h): the lattice is read in a body
@@ -718,12 +737,7 @@ class Solver:
     def set_collider_mesh(self, vertices, triangles, origin, spacing, dims, margin=0.0, negate=False, winding=False):
         """pbf_set_collider_mesh: the lattice of sdf_from_mesh computed and installed as the collider without leaving the
         device -> dict(pairs_total, pairs_tested)"""
-        m, keep = mesh_struct(vertices, triangles)
-        sdf = _lattice_struct(origin, spacing, dims, margin)
-        st = MeshSdfStats()
-        self._chk(self.L.pbf_set_collider_mesh(self.ctx, C.byref(m), C.byref(sdf), _mesh_flags(negate, winding), C.byref(st)),
-                  "pbf_set_collider_mesh")
-        return dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
+        return self._set_solid_mesh("collider", vertices, triangles, origin, spacing, dims, margin, negate, winding)
 
     def mesh_winding(self, vertices, triangles, origin, spacing, dims):
         """pbf_mesh_winding: the generalised winding number of a triangle soup at the lattice's nodes, computed on the device ->
@@ -738,46 +752,22 @@ class Solver:
     def collider_sample(self, p, points):
         """The collider's device function at world points (pbf_collider_sample) -> dict(phi (n,) interpolated distance, +inf
         outside the lattice; moved (n,3) the solver-frame position delta-p would store; hit (n,) uint8)"""
-        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
-        n = len(pts)
-        o = dict(phi=np.zeros(n, self.dtype), moved=np.zeros((n, 3), self.dtype), hit=np.zeros(n, np.uint8))
-        self._chk(self.L.pbf_collider_sample(self.ctx, C.byref(p), n, _vp(pts), _vp(o["phi"]), _vp(o["moved"]), _vp(o["hit"])),
-                  "pbf_collider_sample")
-        return o
+        return self._solid_sample("collider", p, points)
 
     def set_scenery(self, phi, origin=(0.0, 0.0, 0.0), spacing=1.0, margin=0.0):
         """Opt-in scenery (pbf_set_scenery, include/pbf_hip.h): a second, static lattice in the world frame beside the collider,
         given as set_collider's is; delta-p projects the fluid out of it after the collider.  It never has a pose, a body,
         friction or a reaction; with a collider installed as well the reaction records are on.  phi=None clears it."""
-        if phi is None:
-            self._chk(self.L.pbf_set_scenery(self.ctx, None), "pbf_set_scenery")
-            return self
-        a = np.ascontiguousarray(phi, self.dtype)
-        if a.ndim != 3:
-            raise ValueError("set_scenery: phi must have shape (nx, ny, nz)")
-        sdf = _lattice_struct(origin, spacing, a.shape, margin)
-        sdf.phi = a.ctypes.data
-        self._chk(self.L.pbf_set_scenery(self.ctx, C.byref(sdf)), "pbf_set_scenery")
-        return self
+        return self._set_solid("scenery", phi, origin, spacing, margin)
 
     def set_scenery_mesh(self, vertices, triangles, origin, spacing, dims, margin=0.0, negate=False, winding=False):
         """pbf_set_scenery_mesh: set_collider_mesh's build, installed as the scenery -> dict(pairs_total, pairs_tested)"""
-        m, keep = mesh_struct(vertices, triangles)
-        sdf = _lattice_struct(origin, spacing, dims, margin)
-        st = MeshSdfStats()
-        self._chk(self.L.pbf_set_scenery_mesh(self.ctx, C.byref(m), C.byref(sdf), _mesh_flags(negate, winding), C.byref(st)),
-                  "pbf_set_scenery_mesh")
-        return dict(pairs_total=int(st.pairs_total), pairs_tested=int(st.pairs_tested))
+        return self._set_solid_mesh("scenery", vertices, triangles, origin, spacing, dims, margin, negate, winding)
 
     def scenery_sample(self, points, params):
         """The static device function on the scenery's lattice at world points (pbf_scenery_sample) -> the dict of
         collider_sample()"""
-        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
-        n = len(pts)
-        o = dict(phi=np.zeros(n, self.dtype), moved=np.zeros((n, 3), self.dtype), hit=np.zeros(n, np.uint8))
-        self._chk(self.L.pbf_scenery_sample(self.ctx, C.byref(params), n, _vp(pts), _vp(o["phi"]), _vp(o["moved"]), _vp(o["hit"])),
-                  "pbf_scenery_sample")
-        return o
+        return self._solid_sample("scenery", params, points)
 
     def surface_state(self):
         """(n,4): {n.xyz, rho} of the last surface-tension pass — surface normal and density per particle, device order

@@ -1,6 +1,7 @@
-// pbf_collider_state.hpp — which collider features are on, what the reaction records of the current step describe, and the
-// events that move either.  The buffers, the mailboxes and the lattice's geometry stay in pbf_ctx; this is only what decides
-// which kernels and which launch sequence a step runs, and what an observer may believe.  No HIP in here (plain C++17):
+// pbf_collider_state.hpp — which solids are installed (the collider's lattice, the scenery's), which collider features are on,
+// what the reaction records of the current step describe, and the events that move either.  The buffers, the mailboxes and the
+// lattices' geometry (pbf_solid_lattice.hpp) stay in pbf_ctx; this is only what decides which kernels and which launch
+// sequence a step runs, and what an observer may believe.  No HIP in here (plain C++17):
 // host/test_collider_state.cpp walks it without a device.  pbf_hip.hip reads the fields and questions freely; it changes
 // them through the events ONLY (tests/test_collider_state_cpu.py holds it to that).
 //
@@ -8,7 +9,8 @@
 //   posed, body, friction  =>  a lattice is installed        (a new lattice, clearing included, starts without them)
 //   body      =>  reaction and posed                         (the body owns the pose; turned off, it leaves it behind)
 //   friction  =>  reaction
-//   the reaction may be on without a lattice, and stays on across a replaced one
+//   lattice and scenery  =>  reaction                        (the pair's kernels write the records; the scenery alone is static)
+//   the reaction may be on without a lattice, and stays on across a replaced or cleared solid
 //   frictionRan  =>  friction
 //   reaction off  =>  pushAt == 0 and pushRows == -1
 //
@@ -24,6 +26,7 @@ namespace pbf {
 
 struct ColliderState {
   bool lattice = false;      // pbf_set_collider / pbf_set_collider_mesh: a lattice is installed
+  bool scenery = false;      // pbf_set_scenery / pbf_set_scenery_mesh: the static lattice beside it is installed
   bool posed = false;        // pbf_set_collider_pose (or a body, now or before): the kernels read the pose record
   bool reaction = false;     // pbf_set_collider_reaction: delta-p writes the records, the sort clears them
   bool body = false;         // pbf_set_collider_body: stage_body runs after the iterations
@@ -35,9 +38,14 @@ struct ColliderState {
 
   // ---- questions --------------------------------------------------------------------------------
   // which DeltaOp delta-p runs; the values are pbf_kernels.hpp's ColliderMode (pbf_hip.hip asserts it).  With the reaction on
-  // and no pose set the kernels run the identity pose.
-  enum DeltaMode : int { DELTA_OFF = 0, DELTA_STATIC = 1, DELTA_POSED = 2, DELTA_REACT = 3 };
-  DeltaMode delta_mode() const { return !lattice ? DELTA_OFF : reaction ? DELTA_REACT : posed ? DELTA_POSED : DELTA_STATIC; }
+  // and no pose set the kernels run the identity pose.  The scenery alone runs the static kernels on its own lattice.
+  enum DeltaMode : int { DELTA_OFF = 0, DELTA_STATIC = 1, DELTA_POSED = 2, DELTA_REACT = 3, DELTA_REACT_SCENERY = 4 };
+  DeltaMode delta_mode() const {
+    if (!lattice) return scenery ? DELTA_STATIC : DELTA_OFF;
+    return scenery ? DELTA_REACT_SCENERY : reaction ? DELTA_REACT : posed ? DELTA_POSED : DELTA_STATIC;
+  }
+  // the lattice the static kernels read is the scenery's, not the collider's
+  bool static_reads_scenery() const { return scenery && !lattice; }
   // the step's records are indexed by row slot: their readers go through rowSlotOf
   bool records_by_row() const { return pushRows > 0; }
   // the records describe the arrays as they are: cleared by the sort of the current order, and that order still stands
@@ -46,17 +54,31 @@ struct ColliderState {
   bool friction_sums_ready() const { return frictionRan; }
   // the REACT kernels read the pose record although no pose is set: it must hold the identity
   bool needs_identity_pose() const { return reaction && !posed; }
-  // who reads the records after delta-p and so forbids turning the reaction off (the body is named first)
-  enum Holder { HELD_BY_NONE, HELD_BY_BODY, HELD_BY_FRICTION };
-  Holder why_reaction_must_stay() const { return body ? HELD_BY_BODY : friction ? HELD_BY_FRICTION : HELD_BY_NONE; }
+  // who needs the records and so forbids turning the reaction off (the body is named first, the pair of solids last)
+  enum Holder { HELD_BY_NONE, HELD_BY_BODY, HELD_BY_FRICTION, HELD_BY_SCENERY };
+  Holder why_reaction_must_stay() const {
+    return body ? HELD_BY_BODY : friction ? HELD_BY_FRICTION : lattice && scenery ? HELD_BY_SCENERY : HELD_BY_NONE;
+  }
+  // Installing this solid (`present`; clearing never does) would complete the pair with the reaction off.  The entry point
+  // then enables the reaction first — the record buffers must exist before the event, which is why the caller does it.
+  enum Solid { COLLIDER, SCENERY };
+  bool install_needs_reaction(Solid which, bool present) const { return present && !reaction && (which == COLLIDER ? scenery : lattice); }
 
   // ---- events: the entry points -------------------------------------------------------------------
   // A lattice was installed (`present`) or cleared.  Drops the pose, the body and friction with its pass; keeps the reaction
   // and what its records describe.  (Before there was this struct frictionRan outlived the lattice; nothing could read it
-  // until friction_set() had reset it.)
+  // until friction_set() had reset it.)  Refused (nothing changes) where install_needs_reaction().
   bool installed(bool present) {
+    if (install_needs_reaction(COLLIDER, present)) return false;
     lattice = present;
     posed = body = friction = frictionRan = false;
+    return bump();
+  }
+  // The scenery was installed (`present`) or cleared: a replay never runs on a replaced or freed lattice, so gen always
+  // moves.  The collider's pose, body, friction and records are left alone.  Refused where install_needs_reaction().
+  bool scenery_installed(bool present) {
+    if (install_needs_reaction(SCENERY, present)) return false;
+    scenery = present;
     return bump();
   }
   // A pose was stored.  none -> posed selects other kernels; an update keeps everything.
@@ -80,7 +102,7 @@ struct ColliderState {
   }
   // Drops the records.  Refused (nothing changes) while why_reaction_must_stay() names a reader.
   bool reaction_disabled() {
-    if (!reaction || body || friction) return false;
+    if (!reaction || why_reaction_must_stay() != HELD_BY_NONE) return false;
     reaction = false;
     pushAt = 0, pushRows = -1;
     return bump();

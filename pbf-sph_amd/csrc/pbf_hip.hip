@@ -31,7 +31,7 @@
 #include "pbf_comm.hpp"
 #include "pbf_state.hpp"
 #include "pbf_collider_state.hpp"
-#include "pbf_scenery_state.hpp"
+#include "pbf_solid_lattice.hpp"
 #include "pbf_collider_pose.hpp"
 #include "pbf_collider_friction.hpp"
 
@@ -150,8 +150,8 @@ struct GraphKey {
   StepState before;
   unsigned char params[sizeof(double) * 11 + 32];  // dt, scale, force, bounds, iteration, xsph, vorticity, cohesion, adhesion
   uint64_t n;
-  uint64_t collider;  // ColliderState::gen: a replay never runs on a lattice that has been replaced, nor another launch sequence
-  uint64_t scenery;   // SceneryState::gen: nor on a scenery lattice that has been replaced or freed (8 bytes: no padding for memcmp)
+  uint64_t collider;  // ColliderState::gen: a replay never runs on a lattice (the collider's or the scenery's) that has been
+                      // replaced or freed, nor another launch sequence
   int options[10];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
@@ -224,16 +224,12 @@ struct pbf_ctx {
   // pbf_set_surface_tension (opt-in, Akinci 2013): coefficients, the two Jacobi fields of its passes (allocated on first use)
   double cohesion = 0, adhesion = 0;
   DevBuf surfA, surfB;         // A = {0, rho}; B = {n, rho} (PBF_BUF_SURFACE, while st.surfaceValid)
-  // The collider (opt-in): which of lattice / pose / reaction / body / friction is on and what the step's reaction records
-  // describe, changed through its events only (pbf_collider_state.hpp: the rules are there); below it, the memory.
+  // The solids (opt-in): which of lattice / scenery / pose / reaction / body / friction is on and what the step's reaction
+  // records describe, changed through its events only (pbf_collider_state.hpp: the rules are there); below it, the memory.
   ColliderState col;
-  // pbf_set_collider (csrc/pbf_collider.hpp): the lattice in N on the device and the setting as given
-  DevBuf colliderPhi;
-  uint32_t colliderDims[3] = {0, 0, 0};
-  double colliderOrigin[3] = {0, 0, 0}, colliderSpacing = 0, colliderMargin = 0;
-  // pbf_set_scenery (pbf_scenery_state.hpp): one static lattice in the world frame beside the collider, changed by
-  // scenery_install only.  The collider's events, the pose, the body and friction never touch it.
-  SceneryState<DevBuf> scenery;
+  // pbf_set_collider (csrc/pbf_collider.hpp) and pbf_set_scenery (one static lattice in the world frame beside it): each
+  // lattice in N on the device and the setting as given (pbf_solid_lattice.hpp), changed by solid_install only
+  SolidLattice<DevBuf> solid[2];  // [ColliderState::COLLIDER], [ColliderState::SCENERY]
   // pbf_set_collider_pose: the one ColliderPose<N> record the posed kernels read through a pointer (allocated by the first call)
   DevBuf colliderPose;
   // pbf_set_collider_reaction: the records {A, hits}, {B, 0} of DeltaOp<.., COLLIDE_REACT> (2 vec4<N> per particle, sized to
@@ -1118,30 +1114,24 @@ template <typename N> int stage_lambda(pbf_ctx *ctx, const pbf_params *p, bool f
   return DISPATCH_FAST(ctx, lambda_impl, ctx, p, fuseDiffuse);
 }
 
-// pbf_set_collider's lattice as DeltaOp<.., COLLIDE = true> and k_collider_sample take it (all zero, phi == NULL, without one)
+// which solids are installed (ColliderState's flags: solid_install keeps each in step with its SolidLattice::present())
 bool collider_on(const pbf_ctx *ctx) { return ctx->col.lattice; }
+bool scenery_on(const pbf_ctx *ctx) { return ctx->col.scenery; }
 static_assert(int(ColliderState::DELTA_OFF) == COLLIDE_OFF && int(ColliderState::DELTA_STATIC) == COLLIDE_STATIC &&
-                  int(ColliderState::DELTA_POSED) == COLLIDE_POSED && int(ColliderState::DELTA_REACT) == COLLIDE_REACT,
+                  int(ColliderState::DELTA_POSED) == COLLIDE_POSED && int(ColliderState::DELTA_REACT) == COLLIDE_REACT &&
+                  int(ColliderState::DELTA_REACT_SCENERY) == COLLIDE_REACT_SCENERY,
               "ColliderState::delta_mode() names pbf_kernels.hpp's ColliderMode");
 // the reaction records of the step: whether they describe the arrays as they are, and the slots their readers index them by
 bool push_current(const pbf_ctx *ctx) { return ctx->col.records_current(ctx->orderEpoch, ctx->st.sorted); }
 const uint32_t *push_slots(const pbf_ctx *ctx) { return ctx->col.records_by_row() ? ctx->rowSlotOf.as<const uint32_t>() : nullptr; }
-template <typename N> ColliderSdf<N> collider_args(const pbf_ctx *ctx) {
+// a solid's lattice as DeltaOp<.., COLLIDE> and k_collider_sample take it: N(origin), N(1) / N(spacing), N(margin), each
+// rounded once from the setting as given (all zero, phi == NULL, without one)
+template <typename N> ColliderSdf<N> sdf_args(const SolidLattice<DevBuf> &l) {
   ColliderSdf<N> s{};
-  if (!collider_on(ctx)) return s;
-  s.phi = ctx->colliderPhi.as<const N>();
-  for (int a = 0; a < 3; ++a) s.dims[a] = ctx->colliderDims[a], s.origin[a] = N(ctx->colliderOrigin[a]);
-  s.inv = N(1) / N(ctx->colliderSpacing), s.margin = N(ctx->colliderMargin);
-  return s;
-}
-// pbf_set_scenery's lattice, as the static contract takes it (all zero, phi == NULL, without one)
-bool scenery_on(const pbf_ctx *ctx) { return ctx->scenery.phi.p != nullptr; }
-template <typename N> ColliderSdf<N> scenery_args(const pbf_ctx *ctx) {
-  ColliderSdf<N> s{};
-  if (!scenery_on(ctx)) return s;
-  s.phi = ctx->scenery.phi.as<const N>();
-  for (int a = 0; a < 3; ++a) s.dims[a] = ctx->scenery.dims[a], s.origin[a] = N(ctx->scenery.origin[a]);
-  s.inv = N(1) / N(ctx->scenery.spacing), s.margin = N(ctx->scenery.margin);
+  if (!l.present()) return s;
+  s.phi = l.phi.as<const N>();
+  for (int a = 0; a < 3; ++a) s.dims[a] = l.dims[a], s.origin[a] = N(l.origin[a]);
+  s.inv = N(1) / N(l.spacing), s.margin = N(l.margin);
   return s;
 }
 constexpr const char *kColliderSlabError = "a collider is not supported in slab mode (pbf_set_collider(ctx, NULL) clears it)";
@@ -1158,18 +1148,17 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
   // (with a collider the lattice follows the stock arguments, and with a pose the pointer to its record follows the lattice)
   auto args = [&](const typename Op::ArgsPlain &plain) {
     if constexpr (COLLIDE == COLLIDE_REACT_SCENERY)  // (the scenery's lattice follows the records)
-      return typename Op::Args{{{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()}, scenery_args<N>(ctx)};
+      return typename Op::Args{{{{plain, sdf_args<N>(ctx->solid[ColliderState::COLLIDER])}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()}, sdf_args<N>(ctx->solid[ColliderState::SCENERY])};
     else if constexpr (COLLIDE == COLLIDE_REACT)
-      return typename Op::Args{{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()};
-    else if constexpr (COLLIDE == COLLIDE_POSED) return typename Op::Args{{plain, collider_args<N>(ctx)}, ctx->colliderPose.as<const ColliderPose<N>>()};
+      return typename Op::Args{{{plain, sdf_args<N>(ctx->solid[ColliderState::COLLIDER])}, ctx->colliderPose.as<const ColliderPose<N>>()}, ctx->pushRec.as<vec4<N>>()};
+    else if constexpr (COLLIDE == COLLIDE_POSED) return typename Op::Args{{plain, sdf_args<N>(ctx->solid[ColliderState::COLLIDER])}, ctx->colliderPose.as<const ColliderPose<N>>()};
     else if constexpr (COLLIDE == COLLIDE_STATIC)  // (a static collider, or scenery without a collider: the same kernels)
-      return typename Op::Args{plain, collider_on(ctx) ? collider_args<N>(ctx) : scenery_args<N>(ctx)};
+      return typename Op::Args{plain, sdf_args<N>(ctx->solid[ctx->col.static_reads_scenery() ? ColliderState::SCENERY : ColliderState::COLLIDER])};
     else return plain;
   };
   StepConsts<N> c;
   if (int rc = make_consts<N>(ctx, p, c)) return rc;
   if constexpr (COLLIDE == COLLIDE_REACT || COLLIDE == COLLIDE_REACT_SCENERY) {  // the records follow the index of the launch: one kind of index per step
-    if (!ctx->col.reaction) return fail(ctx, PBF_ERR_STATE, "a collider beside scenery needs the reaction records");  // (the setters keep it on)
     if (!push_current(ctx)) return fail(ctx, PBF_ERR_STATE, "the collider reaction needs a sort since it was enabled");
     if (!ctx->col.delta_indexed(ctx->st.delta_on_rows()))
       return fail(ctx, PBF_ERR_STATE, "the gather path changed between two delta-p launches of a step with the collider reaction on");
@@ -1197,18 +1186,14 @@ template <typename N, bool FAST, int COLLIDE> int delta_run(pbf_ctx *ctx, const 
   return rc;
 }
 template <typename N, bool FAST> int delta_impl(pbf_ctx *ctx, const pbf_params *p) {
-  // the one place that turns the mode into an instantiation (this order of first use fixes the kernels' order in the code object)
-  // Scenery alone runs the static kernels on its lattice; beside a collider it is the one mode the state header does not
-  // name (dispatched last: the instantiations before it keep their place).
-  const bool scenery = scenery_on(ctx);
-  if (!scenery || !collider_on(ctx)) {
-    switch (scenery ? ColliderState::DELTA_STATIC : ctx->col.delta_mode()) {
-      case ColliderState::DELTA_OFF: return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
-      case ColliderState::DELTA_REACT: return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);
-      case ColliderState::DELTA_POSED: return delta_run<N, FAST, COLLIDE_POSED>(ctx, p);
-      case ColliderState::DELTA_STATIC: break;
-    }
-    return delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
+  // the one place that turns the mode into an instantiation.  The cases stand in this order, not the enum's, on purpose: the
+  // order of first use fixes the kernels' order in the code object.
+  switch (ctx->col.delta_mode()) {
+    case ColliderState::DELTA_OFF: return delta_run<N, FAST, COLLIDE_OFF>(ctx, p);
+    case ColliderState::DELTA_REACT: return delta_run<N, FAST, COLLIDE_REACT>(ctx, p);
+    case ColliderState::DELTA_POSED: return delta_run<N, FAST, COLLIDE_POSED>(ctx, p);
+    case ColliderState::DELTA_STATIC: return delta_run<N, FAST, COLLIDE_STATIC>(ctx, p);
+    case ColliderState::DELTA_REACT_SCENERY: break;
   }
   return delta_run<N, FAST, COLLIDE_REACT_SCENERY>(ctx, p);
 }
@@ -1954,7 +1939,6 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
   k.collider = ctx->col.gen;
-  k.scenery = ctx->scenery.gen;
   const int opt[10] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
                        int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap)};
   std::memcpy(k.options, opt, sizeof(opt));
@@ -2586,32 +2570,32 @@ int collider_drop_graphs(pbf_ctx *ctx) {
   ctx->graphs.clear();
   return PBF_OK;
 }
-// the one install path: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's collider
-int collider_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
+// The one install path of both solids: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's
+// collider or scenery.  Every install moves the captured steps' key.  A collider and scenery together run
+// DeltaOp<.., COLLIDE_REACT_SCENERY>, which writes the records: the call that completes the pair turns the reaction on if it
+// is off — once the new lattice is on the device and BEFORE anything of the ctx is changed, so a failed allocation leaves
+// everything as it was.  Clearing either solid leaves the reaction on, as a cleared body does.
+int solid_install(pbf_ctx *ctx, ColliderState::Solid which, const pbf_collider_sdf *sdf, DevBuf &fresh) {
+  if (ctx->col.install_needs_reaction(which, sdf != nullptr))
+    if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;
   if (int rc = collider_drop_graphs(ctx)) return rc;  // (first: they hold the old lattice's address)
-  ctx->colliderPhi = std::move(fresh);                // (frees the old lattice)
-  ctx->col.installed(sdf != nullptr);
-  if (ctx->col.needs_identity_pose())
-    if (int rc = collider_pose_identity(ctx)) return rc;
-  for (int a = 0; a < 3; ++a) ctx->colliderDims[a] = sdf ? sdf->dims[a] : 0u, ctx->colliderOrigin[a] = sdf ? sdf->origin[a] : 0.0;
-  ctx->colliderSpacing = sdf ? sdf->spacing : 0.0, ctx->colliderMargin = sdf ? sdf->margin : 0.0;
-  return PBF_OK;
+  ctx->solid[which].put(sdf, fresh);                  // (frees the old lattice)
+  if (!(which == ColliderState::SCENERY ? ctx->col.scenery_installed(sdf != nullptr) : ctx->col.installed(sdf != nullptr)))
+    return fail(ctx, PBF_ERR_STATE, "a collider beside scenery needs the reaction records");  // (enabled above: not reached)
+  return ctx->col.needs_identity_pose() ? collider_pose_identity(ctx) : PBF_OK;
 }
-
-// A collider and scenery together run DeltaOp<.., COLLIDE_REACT_SCENERY>, which writes the records: the call that completes
-// the pair (`other`: the other solid is installed) turns the reaction on if it is off.  Called once the new lattice is on the
-// device and BEFORE anything of the ctx is changed, so a failed allocation leaves everything as it was.  Clearing either solid
-// leaves the reaction on, as a cleared body does.
-int pair_needs_reaction(pbf_ctx *ctx, bool other) { return other ? pbf_set_collider_reaction(ctx, 1) : PBF_OK; }  // (a no-op when it is on)
-// the one install path of the scenery: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's
-// scenery.  Every install moves the captured steps' key; the collider, its pose, its records and its body are left alone.
-int scenery_install(pbf_ctx *ctx, const pbf_collider_sdf *sdf, DevBuf &fresh) {
-  if (int rc = collider_drop_graphs(ctx)) return rc;  // (first: they hold the old lattice's address)
-  ctx->scenery.phi = std::move(fresh);                // (frees the old lattice)
-  ctx->scenery.gen++;
-  for (int a = 0; a < 3; ++a) ctx->scenery.dims[a] = sdf ? sdf->dims[a] : 0u, ctx->scenery.origin[a] = sdf ? sdf->origin[a] : 0.0;
-  ctx->scenery.spacing = sdf ? sdf->spacing : 0.0, ctx->scenery.margin = sdf ? sdf->margin : 0.0;
-  return PBF_OK;
+// pbf_set_collider / pbf_set_scenery: the lattice as given, uploaded into an allocation of its own, then installed
+int set_solid(pbf_ctx *ctx, const char *who, ColliderState::Solid which, const pbf_collider_sdf *sdf) {
+  if (!ctx) return PBF_ERR_INVALID;
+  size_t nodes = 1;
+  if (sdf)
+    if (int rc = collider_lattice_check(ctx, who, sdf, true, true, &nodes)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  DevBuf fresh;
+  if (sdf)
+    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, who, sdf, nodes, fresh) : set_collider_impl<float>(ctx, who, sdf, nodes, fresh))
+      return rc;
+  return solid_install(ctx, which, sdf, fresh);
 }
 
 // pbf_sdf_from_mesh / pbf_set_collider_mesh: the records on the host, then the fold on the device (csrc/pbf_mesh_sdf.hpp,
@@ -2672,6 +2656,18 @@ int mesh_sdf_run(pbf_ctx *ctx, const char *who, const pbf_mesh *mesh, const pbf_
   HIPCHK(ctx, hipSetDevice(ctx->device));
   return ctx->fp64 ? mesh_sdf_impl<double>(ctx, mesh, lat, flags, *nodes, fresh, stats)
                    : mesh_sdf_impl<float>(ctx, mesh, lat, flags, *nodes, fresh, stats);
+}
+// pbf_set_collider_mesh / pbf_set_scenery_mesh: the fold into an allocation of its own, then installed
+int set_solid_mesh(pbf_ctx *ctx, const char *who, ColliderState::Solid which, const pbf_mesh *mesh, const pbf_collider_sdf *lattice,
+                   uint32_t flags, pbf_mesh_sdf_stats *stats) {
+  if (!ctx) return PBF_ERR_INVALID;
+  DevBuf fresh;
+  size_t nodes = 0;
+  pbf_mesh_sdf_stats st{};
+  if (int rc = mesh_sdf_run(ctx, who, mesh, lattice, flags, true, fresh, &nodes, &st)) return rc;
+  if (int rc = solid_install(ctx, which, lattice, fresh)) return rc;
+  if (stats) *stats = st;
+  return PBF_OK;
 }
 // pbf_mesh_winding: the soup records on the host, the winding fold alone on the device, w copied to the caller's array
 template <typename N> int mesh_winding_impl(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lat, size_t nodes, void *w) {
@@ -2749,21 +2745,7 @@ int collider_sample_impl(pbf_ctx *ctx, const ColliderSdf<N> &sdf, const Collider
 
 extern "C" {
 
-int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
-  if (!ctx) return PBF_ERR_INVALID;
-  size_t nodes = 1;
-  if (sdf)
-    if (int rc = collider_lattice_check(ctx, "pbf_set_collider", sdf, true, true, &nodes)) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  DevBuf fresh;
-  if (sdf)
-    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, "pbf_set_collider", sdf, nodes, fresh)
-                           : set_collider_impl<float>(ctx, "pbf_set_collider", sdf, nodes, fresh))
-      return rc;
-  if (sdf)
-    if (int rc = pair_needs_reaction(ctx, scenery_on(ctx))) return rc;
-  return collider_install(ctx, sdf, fresh);
-}
+int pbf_set_collider(pbf_ctx *ctx, const pbf_collider_sdf *sdf) { return set_solid(ctx, "pbf_set_collider", ColliderState::COLLIDER, sdf); }
 
 int pbf_set_collider_pose(pbf_ctx *ctx, const pbf_collider_pose *pose) {
   if (!ctx) return PBF_ERR_INVALID;
@@ -2794,7 +2776,7 @@ int pbf_set_collider_reaction(pbf_ctx *ctx, int on) {
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a body is on and needs the records (pbf_set_collider_body(ctx, NULL) first)");
   if (!want && ctx->col.why_reaction_must_stay() == ColliderState::HELD_BY_FRICTION)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: friction is on and needs the records (pbf_set_collider_friction(ctx, NULL) first)");
-  if (!want && collider_on(ctx) && scenery_on(ctx))
+  if (!want && ctx->col.why_reaction_must_stay() == ColliderState::HELD_BY_SCENERY)
     return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_reaction: a collider beside scenery writes the records (clear either solid first)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (want) {  // everything a step will need exists before the event: the records, their counter, the pose the kernels read
@@ -2948,15 +2930,7 @@ int pbf_sdf_from_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf
 
 int pbf_set_collider_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags,
                           pbf_mesh_sdf_stats *stats) {
-  if (!ctx) return PBF_ERR_INVALID;
-  DevBuf fresh;
-  size_t nodes = 0;
-  pbf_mesh_sdf_stats st{};
-  if (int rc = mesh_sdf_run(ctx, "pbf_set_collider_mesh", mesh, lattice, flags, true, fresh, &nodes, &st)) return rc;
-  if (int rc = pair_needs_reaction(ctx, scenery_on(ctx))) return rc;
-  if (int rc = collider_install(ctx, lattice, fresh)) return rc;
-  if (stats) *stats = st;
-  return PBF_OK;
+  return set_solid_mesh(ctx, "pbf_set_collider_mesh", ColliderState::COLLIDER, mesh, lattice, flags, stats);
 }
 
 // pbf_collider_sample / pbf_scenery_sample: one check, one launch; the scenery is the static function (pose == NULL)
@@ -2973,11 +2947,12 @@ static int sample_entry(pbf_ctx *ctx, const char *who, bool scenery, const pbf_p
   if (!scenery && !collider_on(ctx)) return fail(ctx, PBF_ERR_STATE, w + "no collider set (pbf_set_collider)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const bool posed = !scenery && ctx->col.posed;
+  const SolidLattice<DevBuf> &l = ctx->solid[scenery ? ColliderState::SCENERY : ColliderState::COLLIDER];
   if (ctx->fp64)
-    return collider_sample_impl<double>(ctx, scenery ? scenery_args<double>(ctx) : collider_args<double>(ctx),
+    return collider_sample_impl<double>(ctx, sdf_args<double>(l),
                                         posed ? ctx->colliderPose.as<const ColliderPose<double>>() : nullptr, p, n, points,
                                         static_cast<double *>(phi), static_cast<double *>(moved), hit);
-  return collider_sample_impl<float>(ctx, scenery ? scenery_args<float>(ctx) : collider_args<float>(ctx),
+  return collider_sample_impl<float>(ctx, sdf_args<float>(l),
                                      posed ? ctx->colliderPose.as<const ColliderPose<float>>() : nullptr, p, n, points,
                                      static_cast<float *>(phi), static_cast<float *>(moved), hit);
 }
@@ -2986,32 +2961,10 @@ int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *p, size_t n, const doubl
 }
 
 // ---- the scenery: one static lattice in the world frame beside the collider (the contract: include/pbf_hip.h) ----
-int pbf_set_scenery(pbf_ctx *ctx, const pbf_collider_sdf *sdf) {
-  if (!ctx) return PBF_ERR_INVALID;
-  size_t nodes = 1;
-  if (sdf)
-    if (int rc = collider_lattice_check(ctx, "pbf_set_scenery", sdf, true, true, &nodes)) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  DevBuf fresh;
-  if (sdf)
-    if (int rc = ctx->fp64 ? set_collider_impl<double>(ctx, "pbf_set_scenery", sdf, nodes, fresh)
-                           : set_collider_impl<float>(ctx, "pbf_set_scenery", sdf, nodes, fresh))
-      return rc;
-  if (sdf)
-    if (int rc = pair_needs_reaction(ctx, collider_on(ctx))) return rc;
-  return scenery_install(ctx, sdf, fresh);
-}
+int pbf_set_scenery(pbf_ctx *ctx, const pbf_collider_sdf *sdf) { return set_solid(ctx, "pbf_set_scenery", ColliderState::SCENERY, sdf); }
 
 int pbf_set_scenery_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf *lattice, uint32_t flags, pbf_mesh_sdf_stats *stats) {
-  if (!ctx) return PBF_ERR_INVALID;
-  DevBuf fresh;
-  size_t nodes = 0;
-  pbf_mesh_sdf_stats st{};
-  if (int rc = mesh_sdf_run(ctx, "pbf_set_scenery_mesh", mesh, lattice, flags, true, fresh, &nodes, &st)) return rc;
-  if (int rc = pair_needs_reaction(ctx, collider_on(ctx))) return rc;
-  if (int rc = scenery_install(ctx, lattice, fresh)) return rc;
-  if (stats) *stats = st;
-  return PBF_OK;
+  return set_solid_mesh(ctx, "pbf_set_scenery_mesh", ColliderState::SCENERY, mesh, lattice, flags, stats);
 }
 
 int pbf_scenery_sample(pbf_ctx *ctx, const pbf_params *p, size_t n, const double *points, void *phi, void *moved, uint8_t *hit) {

@@ -340,6 +340,36 @@ class Solver final : public sph::Solver<T, N, V> {
     }
   }
 
+  // The collider and the scenery are given and built from a mesh alike: the lattice and the mesh as the C ABI takes them, and
+  // the two setters behind setCollider / setScenery and setColliderMesh / setSceneryMesh (`set`, `who`: the entry point;
+  // `single`: what is refused across several devices)
+  static pbf_collider_sdf latticeOf(const std::array<uint32_t, 3> &dims, const std::array<double, 3> &origin, double spacing, double margin,
+                                    const void *phi) {
+    pbf_collider_sdf sdf{};
+    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
+    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = phi;
+    return sdf;
+  }
+  static pbf_mesh meshOf(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles) {
+    pbf_mesh mesh{};
+    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
+    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
+    return mesh;
+  }
+  Solver &setSolid(int (*set)(pbf_ctx *, const pbf_collider_sdf *), const char *who, const char *single, const pbf_collider_sdf &sdf) {
+    if (multi()) throw std::runtime_error(single);
+    check(set(ctx_, &sdf), who);
+    return *this;
+  }
+  Solver &setSolidMesh(int (*set)(pbf_ctx *, const pbf_mesh *, const pbf_collider_sdf *, uint32_t, pbf_mesh_sdf_stats *), const char *who,
+                       const char *single, const pbf_mesh &mesh, const pbf_collider_sdf &sdf, bool negate, pbf_mesh_sdf_stats *stats,
+                       bool winding) {
+    if (multi()) throw std::runtime_error(single);
+    const uint32_t flags = (negate ? uint32_t(PBF_MESH_NEGATE) : 0u) | (winding ? uint32_t(PBF_MESH_SIGN_WINDING) : 0u);
+    check(set(ctx_, &mesh, &sdf, flags, stats), who);
+    return *this;
+  }
+
 public:
   explicit Solver(N h, int device = 0, uint32_t flags = 0) : h_(h) {
     pbf_desc d{};
@@ -425,12 +455,7 @@ public:
   // single-device feature (not in slab mode).
   Solver &setCollider(const std::array<uint32_t, 3> &dims, const std::array<double, 3> &origin, double spacing, double margin,
                       const N *phi) {
-    if (multi()) throw std::runtime_error("a collider is a single-device feature");
-    pbf_collider_sdf sdf{};
-    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
-    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = phi;
-    check(pbf_set_collider(ctx_, &sdf), "pbf_set_collider");
-    return *this;
+    return setSolid(pbf_set_collider, "pbf_set_collider", "a collider is a single-device feature", latticeOf(dims, origin, spacing, margin, phi));
   }
   // The same collider from a closed triangle mesh (pbf_set_collider_mesh; no reference counterpart): vertices = 3 doubles per
   // vertex in world units, triangles = 3 indices per triangle, counter-clockwise seen from outside.  The lattice of `dims`
@@ -441,28 +466,16 @@ public:
   Solver &setColliderMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
                           const std::array<double, 3> &origin, double spacing, double margin, bool negate = false,
                           pbf_mesh_sdf_stats *stats = nullptr, bool winding = false) {
-    if (multi()) throw std::runtime_error("a collider is a single-device feature");
-    pbf_mesh mesh{};
-    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
-    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
-    pbf_collider_sdf sdf{};
-    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
-    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = nullptr;
-    const uint32_t flags = (negate ? uint32_t(PBF_MESH_NEGATE) : 0u) | (winding ? uint32_t(PBF_MESH_SIGN_WINDING) : 0u);
-    check(pbf_set_collider_mesh(ctx_, &mesh, &sdf, flags, stats), "pbf_set_collider_mesh");
-    return *this;
+    return setSolidMesh(pbf_set_collider_mesh, "pbf_set_collider_mesh", "a collider is a single-device feature", meshOf(vertices, triangles),
+                        latticeOf(dims, origin, spacing, margin, nullptr), negate, stats, winding);
   }
   // The winding-number field of a triangle soup on that lattice (pbf_mesh_winding): 1 inside a closed outward mesh, 0
   // outside, the covered share of the sphere of directions for an open one; node (i, j, k) at (i * dims[1] + j) * dims[2] + k.
   std::vector<N> meshWinding(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
                              const std::array<double, 3> &origin, double spacing) {
     if (multi()) throw std::runtime_error("a collider is a single-device feature");
-    pbf_mesh mesh{};
-    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
-    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
-    pbf_collider_sdf sdf{};
-    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
-    sdf.spacing = spacing, sdf.phi = nullptr;
+    const pbf_mesh mesh = meshOf(vertices, triangles);
+    const pbf_collider_sdf sdf = latticeOf(dims, origin, spacing, 0.0, nullptr);
     std::vector<N> w(size_t(dims[0]) * dims[1] * dims[2]);
     check(pbf_mesh_winding(ctx_, &mesh, &sdf, w.data()), "pbf_mesh_winding");
     return w;
@@ -477,27 +490,14 @@ public:
   // collider leaves it alone.  A single-device feature, like setCollider.
   Solver &setScenery(const std::array<uint32_t, 3> &dims, const std::array<double, 3> &origin, double spacing, double margin,
                      const N *phi) {
-    if (multi()) throw std::runtime_error("scenery is a single-device feature");
-    pbf_collider_sdf sdf{};
-    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
-    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = phi;
-    check(pbf_set_scenery(ctx_, &sdf), "pbf_set_scenery");
-    return *this;
+    return setSolid(pbf_set_scenery, "pbf_set_scenery", "scenery is a single-device feature", latticeOf(dims, origin, spacing, margin, phi));
   }
   // setColliderMesh's build, installed as the scenery (pbf_set_scenery_mesh)
   Solver &setSceneryMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const std::array<uint32_t, 3> &dims,
                          const std::array<double, 3> &origin, double spacing, double margin, bool negate = false,
                          pbf_mesh_sdf_stats *stats = nullptr, bool winding = false) {
-    if (multi()) throw std::runtime_error("scenery is a single-device feature");
-    pbf_mesh mesh{};
-    mesh.n_vertices = vertices.size() / 3, mesh.n_triangles = triangles.size() / 3;
-    mesh.vertices = vertices.data(), mesh.triangles = triangles.data();
-    pbf_collider_sdf sdf{};
-    for (int a = 0; a < 3; ++a) sdf.dims[a] = dims[a], sdf.origin[a] = origin[a];
-    sdf.spacing = spacing, sdf.margin = margin, sdf.phi = nullptr;
-    const uint32_t flags = (negate ? uint32_t(PBF_MESH_NEGATE) : 0u) | (winding ? uint32_t(PBF_MESH_SIGN_WINDING) : 0u);
-    check(pbf_set_scenery_mesh(ctx_, &mesh, &sdf, flags, stats), "pbf_set_scenery_mesh");
-    return *this;
+    return setSolidMesh(pbf_set_scenery_mesh, "pbf_set_scenery_mesh", "scenery is a single-device feature", meshOf(vertices, triangles),
+                        latticeOf(dims, origin, spacing, margin, nullptr), negate, stats, winding);
   }
   Solver &clearScenery() {
     if (!multi()) check(pbf_set_scenery(ctx_, nullptr), "pbf_set_scenery");

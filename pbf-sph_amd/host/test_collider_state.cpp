@@ -14,17 +14,21 @@ namespace {
 int g_failures = 0;
 std::set<int> g_seen;  // the flag combinations the walks have stood in
 
-int flags_of(const ColliderState &c) { return c.lattice | c.posed << 1 | c.reaction << 2 | c.body << 3 | c.friction << 4; }
-bool allowed(int f) {  // the header's rules on the five flags
-  const bool lattice = f & 1, posed = f & 2, reaction = f & 4, body = f & 8, friction = f & 16;
-  return (!body || (reaction && posed && lattice)) && (!friction || (reaction && lattice)) && (!posed || lattice);
+int flags_of(const ColliderState &c) { return c.lattice | c.posed << 1 | c.reaction << 2 | c.body << 3 | c.friction << 4 | c.scenery << 5; }
+bool allowed(int f) {  // the header's rules on the six flags
+  const bool lattice = f & 1, posed = f & 2, reaction = f & 4, body = f & 8, friction = f & 16, scenery = f & 32;
+  return (!body || (reaction && posed && lattice)) && (!friction || (reaction && lattice)) && (!posed || lattice) &&
+         (!(lattice && scenery) || reaction);
 }
-// the table delta_impl (pbf_hip.hip) instantiates from, written out: no lattice -> OFF; else the reaction wins over a pose
+// the table delta_impl (pbf_hip.hip) instantiates from, written out.  Without scenery: no lattice -> OFF; else the reaction
+// wins over a pose.  With it: alone it is STATIC, beside a lattice REACT_SCENERY whatever else is on.
 ColliderState::DeltaMode mode_of(int f) {
-  static const ColliderState::DeltaMode table[8] = {ColliderState::DELTA_OFF,    ColliderState::DELTA_OFF,   ColliderState::DELTA_OFF,
-                                                    ColliderState::DELTA_OFF,    ColliderState::DELTA_STATIC, ColliderState::DELTA_POSED,
-                                                    ColliderState::DELTA_REACT,  ColliderState::DELTA_REACT};
-  return table[(f & 1) << 2 | ((f >> 2) & 1) << 1 | ((f >> 1) & 1)];  // (lattice, reaction, posed)
+  static const ColliderState::DeltaMode table[16] = {
+      ColliderState::DELTA_OFF,           ColliderState::DELTA_OFF,           ColliderState::DELTA_OFF,           ColliderState::DELTA_OFF,
+      ColliderState::DELTA_STATIC,        ColliderState::DELTA_POSED,         ColliderState::DELTA_REACT,         ColliderState::DELTA_REACT,
+      ColliderState::DELTA_STATIC,        ColliderState::DELTA_STATIC,        ColliderState::DELTA_STATIC,        ColliderState::DELTA_STATIC,
+      ColliderState::DELTA_REACT_SCENERY, ColliderState::DELTA_REACT_SCENERY, ColliderState::DELTA_REACT_SCENERY, ColliderState::DELTA_REACT_SCENERY};
+  return table[((f >> 5) & 1) << 3 | (f & 1) << 2 | ((f >> 2) & 1) << 1 | ((f >> 1) & 1)];  // (scenery, lattice, reaction, posed)
 }
 
 struct Walk {
@@ -39,7 +43,7 @@ struct Walk {
     ++g_failures;
   }
   // after EVERY event.  `before`: the state it found; `said`: what it returned (an event of the step says nothing: false);
-  // `install`: it was installed(), which moves gen whatever the flags do
+  // `install`: it was installed() or scenery_installed(), which move gen whatever the flags do
   void check(const char *event, const ColliderState &before, bool said, bool install = false) {
     trail += trail.empty() ? event : std::string(" > ") + event;
     const int f = flags_of(col);
@@ -47,6 +51,8 @@ struct Walk {
     expect(!col.body || (col.reaction && col.posed && col.lattice), event, "body without reaction, pose and lattice");
     expect(!col.friction || (col.reaction && col.lattice), event, "friction without reaction and lattice");
     expect(!col.posed || col.lattice, event, "posed without a lattice");
+    expect(!(col.lattice && col.scenery) || col.reaction, event, "a collider beside scenery without the reaction");
+    expect(col.static_reads_scenery() == (col.scenery && !col.lattice), event, "static_reads_scenery");
     expect(!col.frictionRan || col.friction, event, "frictionRan without friction");
     expect(col.reaction || (col.pushAt == 0 && col.pushRows == -1), event, "records described with the reaction off");
     expect(col.pushRows >= -1 && col.pushRows <= 1, event, "pushRows out of range");
@@ -61,12 +67,32 @@ struct Walk {
   bool records_current() const { return col.records_current(orderEpoch, sorted); }
 
   // ---- the entry points, as pbf_hip.hip calls the events; false = the call is refused ---------------------------------------
-  void set_collider(bool present) {  // collider_install
+  // solid_install's first act: the call that completes the pair turns the reaction on (the event alone refuses, and drops nothing)
+  void pair_first(ColliderState::Solid which, bool present) {
+    const bool completes = present && !col.reaction && (which == ColliderState::COLLIDER ? col.scenery : col.lattice);
+    expect(col.install_needs_reaction(which, present) == completes, "install_needs_reaction", "not the pair rule");
+    if (!completes) return;
+    const ColliderState b = col;
+    const bool said = which == ColliderState::COLLIDER ? col.installed(true) : col.scenery_installed(true);
+    check("install(refused)", b, said);
+    expect(same_records(b) && col.frictionRan == b.frictionRan, "install(refused)", "a refused install changed something");
+    set_reaction(true);
+  }
+  void set_collider(bool present) {  // solid_install(.., COLLIDER, ..)
+    pair_first(ColliderState::COLLIDER, present);
     const ColliderState b = col;
     const bool said = col.installed(present);
     check(present ? "installed(true)" : "installed(false)", b, said, true);
     expect(col.lattice == present && !col.posed && !col.body && !col.friction && !col.frictionRan, "installed", "a feature of the old solid survived");
-    expect(col.reaction == b.reaction && same_records(b), "installed", "the reaction or its records changed");
+    expect(col.reaction == b.reaction && same_records(b) && col.scenery == b.scenery, "installed", "the reaction, its records or the scenery changed");
+  }
+  void set_scenery(bool present) {  // solid_install(.., SCENERY, ..)
+    pair_first(ColliderState::SCENERY, present);
+    const ColliderState b = col;
+    const bool said = col.scenery_installed(present);
+    check(present ? "scenery_installed(true)" : "scenery_installed(false)", b, said, true);
+    expect(col.scenery == present && (flags_of(col) & 31) == (flags_of(b) & 31) && col.frictionRan == b.frictionRan && same_records(b),
+           "scenery_installed", "the scenery's install touched the collider");
   }
   bool set_pose(bool pose) {  // pbf_set_collider_pose
     if (!col.lattice || col.body) return false;
@@ -80,7 +106,8 @@ struct Walk {
     if (on == col.reaction) return true;
     const ColliderState b = col;
     if (!on && col.why_reaction_must_stay() != ColliderState::HELD_BY_NONE) {
-      expect(col.why_reaction_must_stay() == (col.body ? ColliderState::HELD_BY_BODY : ColliderState::HELD_BY_FRICTION), "why_reaction_must_stay", "the body is named first");
+      expect(col.why_reaction_must_stay() == (col.body ? ColliderState::HELD_BY_BODY : col.friction ? ColliderState::HELD_BY_FRICTION : ColliderState::HELD_BY_SCENERY),
+             "why_reaction_must_stay", "the body is named first, then friction, then the pair");
       const bool said = col.reaction_disabled();  // (pbf_hip.hip refuses before; the event refuses as well)
       check("reaction_disabled(refused)", b, said);
       expect(col.reaction && same_records(b), "reaction_disabled(refused)", "the records were dropped under their reader");
@@ -135,8 +162,9 @@ struct Walk {
     check("records_cleared", b, false);
     expect(records_current() && col.pushRows == -1, "records_cleared", "the fresh records are not believed");
   }
-  bool delta(bool rows) {  // delta_run<.., COLLIDE_REACT>; false = "the gather path changed"
-    if (col.delta_mode() != ColliderState::DELTA_REACT) return true;
+  bool delta(bool rows) {  // delta_run<.., COLLIDE_REACT / COLLIDE_REACT_SCENERY>; false = "the gather path changed"
+    if (col.delta_mode() != ColliderState::DELTA_REACT && col.delta_mode() != ColliderState::DELTA_REACT_SCENERY) return true;
+    expect(col.reaction, "delta", "kernels that write the records run without them");
     if (!records_current()) return false;  // "needs a sort since it was enabled"
     const ColliderState b = col;
     const bool ok = col.delta_indexed(rows);
@@ -177,7 +205,7 @@ Walk fresh(const std::string &name) {
 
 // every sequence of `depth` calls out of the entry points and the step, from a fresh context
 const char *kActions[] = {"install", "clear", "pose", "unpose", "react", "unreact", "body", "unbody", "friction", "unfriction",
-                          "step(rows)", "step(morton)", "replay", "upload"};
+                          "step(rows)", "step(morton)", "replay", "upload", "scenery", "unscenery"};
 void act(Walk &w, int a) {
   switch (a) {
     case 0: w.set_collider(true); break;
@@ -193,13 +221,15 @@ void act(Walk &w, int a) {
     case 10: w.step(true); break;
     case 11: w.step(false); break;
     case 12: w.replay(); break;
-    default: w.upload(); break;
+    case 13: w.upload(); break;
+    case 14: w.set_scenery(true); break;
+    default: w.set_scenery(false); break;
   }
 }
 long every_sequence(const Walk &from, int depth) {
   if (depth == 0) return 1;
   long n = 0;
-  for (int a = 0; a < 14; ++a) {
+  for (int a = 0; a < 16; ++a) {
     Walk w = from;
     w.name += std::string(" ") + kActions[a];
     act(w, a);
@@ -327,10 +357,73 @@ int main() {
     w.expect(w.col.pushAt == 0 && !w.col.friction_sums_ready(), "replay", "a replay invented records");
     ++sequences;
   }
+  {  // the pair completed in both orders: the completing call turns the reaction on, and it is held while both stand
+    for (bool sceneryFirst : {false, true}) {
+      Walk w = fresh(sceneryFirst ? "pair, scenery first" : "pair, collider first");
+      sceneryFirst ? w.set_scenery(true) : w.set_collider(true);
+      w.expect(!w.col.reaction && w.col.delta_mode() == ColliderState::DELTA_STATIC && w.col.static_reads_scenery() == sceneryFirst, "pair", "one solid alone is static");
+      sceneryFirst ? w.set_collider(true) : w.set_scenery(true);
+      w.expect(w.col.reaction && w.col.needs_identity_pose() && w.col.delta_mode() == ColliderState::DELTA_REACT_SCENERY, "pair", "the pair runs the fifth mode with the reaction on");
+      w.expect(!w.delta(true), "pair", "delta-p before the sort");
+      w.step(true), w.step(false);
+      w.expect(!w.set_reaction(false) && w.col.why_reaction_must_stay() == ColliderState::HELD_BY_SCENERY, "pair", "the reaction went off under the pair");
+      w.set_pose(true);
+      w.expect(w.col.delta_mode() == ColliderState::DELTA_REACT_SCENERY, "pair", "a pose changes the record, not the mode");
+      ++sequences;
+    }
+  }
+  {  // each solid cleared: the reaction stays on, and is then free to go
+    for (bool clearScenery : {false, true}) {
+      Walk w = fresh(clearScenery ? "pair, scenery cleared" : "pair, collider cleared");
+      w.set_collider(true), w.set_scenery(true);
+      w.step(true);
+      const ColliderState b = w.col;
+      clearScenery ? w.set_scenery(false) : w.set_collider(false);
+      w.expect(w.col.reaction && w.same_records(b) && w.records_current(), "clear one", "the reaction and its records stay");
+      w.expect(w.col.delta_mode() == (clearScenery ? ColliderState::DELTA_REACT : ColliderState::DELTA_STATIC), "clear one", "mode");
+      w.expect(w.col.static_reads_scenery() == !clearScenery, "clear one", "whose lattice the static kernels read");
+      w.step(true);
+      w.expect(w.set_reaction(false), "clear one", "the reaction is free");
+      w.expect(w.col.delta_mode() == ColliderState::DELTA_STATIC, "clear one", "the solid left is static");
+      ++sequences;
+    }
+  }
+  {  // the lattice replaced beside scenery with everything on; the scenery replaced under a body
+    Walk w = fresh("replace beside scenery");
+    w.set_scenery(true), w.set_collider(true);
+    w.set_body(true), w.set_friction(true);
+    w.step(true), w.step(true);
+    w.expect(!w.set_reaction(false) && w.col.why_reaction_must_stay() == ColliderState::HELD_BY_BODY, "replace", "the body is named before the pair");
+    ColliderState b = w.col;
+    w.set_scenery(true);
+    w.expect(w.col.body && w.col.friction && w.col.posed && w.col.frictionRan && w.records_current(), "replace", "a new scenery left the collider alone");
+    b = w.col;
+    w.set_collider(true);
+    w.expect(w.col.scenery && w.col.reaction && w.same_records(b) && w.records_current() && w.col.needs_identity_pose(), "replace", "the reaction and its records outlive the lattice");
+    w.expect(w.col.delta_mode() == ColliderState::DELTA_REACT_SCENERY, "replace", "mode");
+    w.step(true);
+    ++sequences;
+  }
+  {  // scenery alone is static on its own lattice, whatever the reaction; every install moves gen by one, clears included
+    Walk w = fresh("scenery alone");
+    uint64_t g = w.col.gen;
+    for (bool present : {true, true, false, false, true}) {
+      w.set_scenery(present);
+      w.expect(w.col.gen == ++g, "scenery alone", "an install did not move gen by one");
+      w.expect(w.col.delta_mode() == (present ? ColliderState::DELTA_STATIC : ColliderState::DELTA_OFF) && w.col.static_reads_scenery() == present, "scenery alone", "mode");
+    }
+    w.step(true);
+    w.set_reaction(true);
+    w.expect(w.col.delta_mode() == ColliderState::DELTA_STATIC && w.delta(true), "scenery alone", "the reaction without a lattice changes no kernel");
+    w.expect(!w.set_pose(true) && !w.set_body(true) && !w.set_friction(true), "scenery alone", "a feature without a lattice");
+    w.step(false);
+    w.expect(w.set_reaction(false), "scenery alone", "the reaction is free");
+    ++sequences;
+  }
   sequences += every_sequence(fresh("all:"), 5);
 
   int reachable = 0;
-  for (int f = 0; f < 32; ++f) {
+  for (int f = 0; f < 64; ++f) {
     if (!allowed(f)) {
       if (g_seen.count(f)) std::printf("FAIL: the walks stood in the forbidden combination %d\n", f), ++g_failures;
       continue;
