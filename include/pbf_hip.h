@@ -90,7 +90,10 @@ int pbf_abi_version(void);
  * everything in Morton order), "nbr_chunks" (size of the pool of 120-slot overflow chunks of the two-tier neighbour lists;
  * 0 = sized from the particle count), "row_diffuse" (DEFAULT 1, with row_major: the colour diffusion walks the row-major copy, one
  * wave per segment of 64 x cells, runs staged by LDS-DMA, sums applied in place; 0 = per-cell sums on the Morton order, beside
- * the iterations), "diffuse_cap" (diagnostic: records in that kernel's LDS tile, 0 = default 640), "sdf_cull" (pbf_sdf_from_mesh / pbf_set_collider_mesh only: 1 = a wave skips the
+ * the iterations), "diffuse_cap" (diagnostic: records in that kernel's LDS tile, 0 = default 640), "build_wg" / "reader_wg" / "iter_wg" (with
+ * row_major: the workgroup width of the row list build — DEFAULT 64, one wave per workgroup, so that each wave's staging LDS
+ * goes back to the CU when that wave ends —, of the row delta-p reader — DEFAULT 256 —, or of both; 64, 128 or 256, anything
+ * else PBF_ERR_INVALID; the lists are the same at every width, so it may change between any two launches), "sdf_cull" (pbf_sdf_from_mesh / pbf_set_collider_mesh only: 1 = a wave skips the
  * triangles whose bounding sphere is out of its brick's reach; DEFAULT 1, 0 = every pair), "sdf_launch_pairs" (diagnostic, the
  * same calls and pbf_mesh_winding: the cap on lane-triangle pairs per launch of the distance fold and of the winding fold,
  * 0 = the default, 2^33 for the distance; a small cap lets a test reach the split across launches).  Every setting of these

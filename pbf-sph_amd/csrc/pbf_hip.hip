@@ -152,7 +152,7 @@ struct GraphKey {
   uint64_t n;
   uint64_t collider;  // ColliderState::gen: a replay never runs on a lattice (the collider's or the scenery's) that has been
                       // replaced or freed, nor another launch sequence
-  int options[10];
+  int options[12];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
 
@@ -319,6 +319,10 @@ struct pbf_ctx {
                              // (measured at 1 M, round 3: fp32 +3 %, fp64 +2.4 % per step with it)
   int coop = 0;              // option "coop": 0 = one lane per particle (bit-exact), 2 / 4 / 8 = lanes sharing a particle's
                              // list with a wave-shuffle reduction (k_gather_from_lists_coop; rounding-level differences)
+  // options "build_wg" / "reader_wg" ("iter_wg" sets both): the workgroup width of the row build (k_build_rows_op) and of the
+  // plain row reader (k_gather_from_lists<.., false, true>), 64 / 128 / 256; 0 = the default, kIterWgBuild / kIterWgReader.  The
+  // lists are the same at every width, so either may change between any two launches; no derived state depends on them.
+  int buildWg = 0, readerWg = 0;
   bool fusePredict = true;   // option "fuse_predict": pbf_steps runs finalise(t) + predict(t + 1) as one kernel
   bool cellDiffuse = true;   // option "cell_diffuse": one walk per occupied cell instead of one per particle
   // option "overlap_diffuse" (default on): inside pbf_step the colour diffusion — memory-latency bound, 85 % of its wave
@@ -572,6 +576,19 @@ struct StageTimer {
 
 // (at least one workgroup: a slab may own no particle at all, and every kernel bounds-checks its index)
 inline dim3 grid_for(size_t n) { return dim3(unsigned(std::max<size_t>(1, (n + BLOCK - 1) / BLOCK))); }
+// the row iteration kernels at workgroup width wg: BLOCK / wg units per chunk, the grid counts units (iter_unit)
+inline dim3 iter_grid(size_t n, unsigned wg) { return dim3(grid_for(n).x * (unsigned(BLOCK) / wg)); }
+// The default widths (A/B builds override them), measured at 1 M (profiles/wave_workgroups_1m.md).  The build is capped at four
+// waves per SIMD by its staging LDS, which a CU gets back only when a workgroup's last wave ends: one wave per workgroup, every
+// launch of the build 3 to 4.5 us shorter (128: half of that).  The reader is not LDS-capped and measured the same at every width.
+#ifndef PBF_BUILD_WG
+#define PBF_BUILD_WG 64
+#endif
+#ifndef PBF_READER_WG
+#define PBF_READER_WG 256
+#endif
+constexpr int kIterWgBuild = PBF_BUILD_WG, kIterWgReader = PBF_READER_WG;
+inline int iter_wg(int option, int dflt) { return option ? option : dflt; }
 
 #define LAUNCH_CHECK(ctx)                                                  \
   do {                                                                     \
@@ -849,10 +866,18 @@ void launch_from_lists(pbf_ctx *ctx, const StepConsts<N> &c, const typename Op::
                        const uint32_t *table, const RowWalk &rw = {}) {
   const dim3 g = grid_for(ctx->n), b(BLOCK);
   const NbrLists ls = nbr_lists(ctx, false);
-  if (ctx->pipeline > 0)
+  if (ctx->pipeline > 0) {
     hipLaunchKernelGGL((k_gather_from_lists<N, Op, true, ROWS>), g, b, 0, ctx->stream, c, args, key, table, ls, rw);
-  else
-    hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, ROWS>), g, b, 0, ctx->stream, c, args, key, table, ls, rw);
+    return;
+  }
+  if constexpr (ROWS) {  // the plain reader on the row-major copy: at the width option "reader_wg" asks for
+    switch (iter_wg(ctx->readerWg, kIterWgReader)) {
+      case 64: hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, true, 64>), iter_grid(ctx->n, 64), dim3(64), 0, ctx->stream, c, args, key, table, ls, rw); return;
+      case 128: hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, true, 128>), iter_grid(ctx->n, 128), dim3(128), 0, ctx->stream, c, args, key, table, ls, rw); return;
+      default: break;
+    }
+  }
+  hipLaunchKernelGGL((k_gather_from_lists<N, Op, false, ROWS>), g, b, 0, ctx->stream, c, args, key, table, ls, rw);
 }
 
 // the list build on the Morton-sorted arrays with `Ride` riding on it: W pair loads per trip, staging depth LMAX, FW survivors
@@ -1090,8 +1115,14 @@ template <typename N, bool FAST> int lambda_impl(pbf_ctx *ctx, const pbf_params 
   const bool lists = (ctx->gatherKind == 1 || ctx->gatherKind == 3) && ctx->reuseLists && !(ctx->desc.flags & PBF_FLAG_NO_LDS);
   if (lists && ctx->st.rows_usable() && row_mode(ctx) && !fuseDiffuse) {  // the build + lambda on the row-major copy
     typename Op::Args a{ctx->rowPstar[ctx->st.rcur].as<vec4<N>>(), nullptr, ctx->rowType.as<const uint8_t>(), ctx->rowMass.as<const N>()};
-    hipLaunchKernelGGL((k_build_rows_op<N, Op, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, a,
-                       ctx->rowQpos.as<const uint2>(), row_walk<N>(ctx), nbr_lists(ctx, true));
+    const uint2 *qp = ctx->rowQpos.as<const uint2>();
+    const RowWalk rw = row_walk<N>(ctx);
+    const NbrLists ls = nbr_lists(ctx, true);
+    switch (iter_wg(ctx->buildWg, kIterWgBuild)) {  // (option "build_wg": one workgroup per unit of that many lanes)
+      case 64: hipLaunchKernelGGL((k_build_rows_op<N, Op, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW, 64>), iter_grid(ctx->n, 64), dim3(64), 0, ctx->stream, c, a, qp, rw, ls); break;
+      case 128: hipLaunchKernelGGL((k_build_rows_op<N, Op, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW, 128>), iter_grid(ctx->n, 128), dim3(128), 0, ctx->stream, c, a, qp, rw, ls); break;
+      default: hipLaunchKernelGGL((k_build_rows_op<N, Op, PBF_ROWS_W, PBF_ROWS_LMAX, PBF_ROWS_FW>), grid_for(ctx->n), dim3(BLOCK), 0, ctx->stream, c, a, qp, rw, ls); break;
+    }
     LAUNCH_CHECK(ctx);
     ctx->st.lambda_done(lists, /*rows=*/true);
     return PBF_OK;
@@ -1618,6 +1649,11 @@ int pbf_set_option(pbf_ctx *ctx, const char *name, int64_t value) {
     if (value != 0 && value != 2 && value != 4 && value != 8) return fail(ctx, PBF_ERR_INVALID, "coop must be 0, 2, 4 or 8");
     ctx->coop = int(value);
   }
+  else if (n == "iter_wg" || n == "build_wg" || n == "reader_wg") {
+    if (value != 64 && value != 128 && value != 256) return fail(ctx, PBF_ERR_INVALID, n + " must be 64, 128 or 256");
+    if (n != "reader_wg") ctx->buildWg = int(value);
+    if (n != "build_wg") ctx->readerWg = int(value);
+  }
   else if (n == "split_build") ctx->splitBuild = int(value);
   else if (n == "fuse_predict") ctx->fusePredict = value != 0;
   else if (n == "timing_mask") ctx->timingMask = uint32_t(value);
@@ -1693,6 +1729,13 @@ int pbf_create(const pbf_desc *desc, pbf_ctx **out) {
   if (const char *e = std::getenv("PBF_PIPELINE")) ctx->pipeline = std::atoi(e);
   if (const char *e = std::getenv("PBF_ROW_MAJOR")) ctx->rowMajor = std::atoi(e);
   if (const char *e = std::getenv("PBF_GRAPH")) ctx->graphMode = std::atoi(e);
+  auto width_env = [](const char *name, int dflt) {
+    const char *e = std::getenv(name);
+    const int v = e ? std::atoi(e) : 0;
+    return v == 64 || v == 128 || v == 256 ? v : dflt;
+  };
+  ctx->buildWg = width_env("PBF_BUILD_WG", width_env("PBF_ITER_WG", 0));
+  ctx->readerWg = width_env("PBF_READER_WG", width_env("PBF_ITER_WG", 0));
   if (const char *e = std::getenv("PBF_COOP")) {
     const int v = std::atoi(e);
     if (v == 0 || v == 2 || v == 4 || v == 8) ctx->coop = v;
@@ -1939,8 +1982,8 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
   k.collider = ctx->col.gen;
-  const int opt[10] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
-                       int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap)};
+  const int opt[12] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
+                       int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap), ctx->buildWg, ctx->readerWg};
   std::memcpy(k.options, opt, sizeof(opt));
   return k;
 }

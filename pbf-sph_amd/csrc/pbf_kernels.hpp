@@ -152,6 +152,29 @@ __device__ inline uint32_t xcd_chunk() {
   return k * q + min(k, r) + blockIdx.x / NUM_XCD;
 #endif
 }
+// Workgroup -> unit, for the row iteration kernels whose workgroup is narrower than a chunk: a unit is WG lanes of a chunk,
+// BLOCK / WG units make a chunk, and the grid counts units.  The rule is xcd_chunk()'s on units: XCD k works on the k-th
+// contiguous run of the units (a bijection of [0, gridDim) for any grid size), so the units of a chunk and neighbouring chunks
+// stay in one L2.  With one unit per chunk this is xcd_chunk()'s default mapping.
+struct IterUnit {
+  uint32_t chunk, tid;  // the lane's place as the [block][slot][thread] lists address it: particle chunk * BLOCK + tid
+};
+__device__ inline uint32_t xcd_unit() {
+#ifdef PBF_NO_XCD_MAP
+  return blockIdx.x;
+#else
+  const uint32_t g = gridDim.x, k = blockIdx.x % NUM_XCD, q = g / NUM_XCD, r = g % NUM_XCD;
+  return k * q + min(k, r) + blockIdx.x / NUM_XCD;
+#endif
+}
+template <uint32_t WG> __device__ inline IterUnit iter_unit() {
+  static_assert(WG == 64 || WG == 128 || WG == 256, "a unit is one, two or four waves of a 256-lane chunk");
+  static_assert(BLOCK == 256, "the lists' row width");
+  constexpr uint32_t PER_CHUNK = uint32_t(BLOCK) / WG;
+  if constexpr (PER_CHUNK == 1) return IterUnit{xcd_chunk(), threadIdx.x};  // (with the experiments xcd_chunk() carries)
+  const uint32_t u = xcd_unit();
+  return IterUnit{u / PER_CHUNK, (u % PER_CHUNK) * WG + threadIdx.x};
+}
 
 __device__ inline uint32_t wave_incl_scan(uint32_t v, int lane) {
 #pragma unroll
@@ -2142,6 +2165,8 @@ __global__ __launch_bounds__(DIFFUSE_ROW_THREADS) void k_diffuse_rows(StepConsts
           // four records per trip, the next four requested before these are added (reads past the sub-run stay inside the
           // tile's padding and are never added): one LDS latency per row instead of one per trip, no remainder loop
           const uint32_t cnt = e - s;  // (a lane without a sub-run: 0 — its s is meaningless)
+          // (Measured and not kept, profiles/wave_workgroups_1m.md: two buffers swapping roles, two trips per turn — 12 v_mov_b32
+          // per trip become 5 per two, 10 % fewer VALU per wave, and the wave takes as long as before: it waits, it does not issue.)
           if (cnt) {
             vec4<N> cur[4];
 #pragma unroll
@@ -2238,16 +2263,20 @@ template <uint32_t FULL, uint32_t STEP> constexpr uint32_t widest_partial_trip()
 // The list build with an op riding on it, on the row-major copy: lane = row slot.  A (dy, dz) row of three x cells is ONE
 // run [lintab[c - 1], lintab[c + 2]) — walked in pairs (one 16-byte load = two quantised candidates) from a per-lane byte
 // offset that advances by a constant per trip: no run select, no padding slot, one limit compare per slot.
-template <typename N, typename Op, int W, int LMAX = 32, int FW = 4>
-__global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typename Op::Args args, const uint2 *__restrict__ qpos,
-                                                         RowWalk rw, NbrLists lists) {
+// WG: the workgroup's width.  Nothing here crosses a wave (no barrier, staging private per lane), and the staging LDS — what caps
+// the kernel at four waves per SIMD — goes back to the CU only when a workgroup's LAST wave ends: at WG = 64 every wave returns
+// its own 10 KiB the moment it ends.  The workgroup is a unit of its chunk (iter_unit); the lists keep BLOCK as their row width,
+// so lists built at one width are read at any other.
+template <typename N, typename Op, int W, int LMAX = 32, int FW = 4, int WG = BLOCK>
+__global__ __launch_bounds__(WG) void k_build_rows_op(StepConsts<N> c, typename Op::Args args, const uint2 *__restrict__ qpos,
+                                                      RowWalk rw, NbrLists lists) {
   static_assert(4 * W + 2 <= QPOS_PAD, "qpos padding");
   // (a lane stages at most LMAX - 1 + 2 W entries, so a drain trip starts at q <= that count rounded down to FW and reads
   // slots up to q + FW - 1 whether they are taken or not)
   static_assert((LMAX + 2 * W) % FW == 0, "the drain's last trip reads FW slots inside the staging list");
-  __shared__ uint32_t list[(LMAX + 2 * W) * BLOCK];  // per-lane staging: a trip appends up to 2 W past LMAX - 1
-  const uint32_t tid = threadIdx.x;
-  const uint32_t chunk = xcd_chunk();
+  __shared__ uint32_t list[(LMAX + 2 * W) * WG];  // per-lane staging: a trip appends up to 2 W past LMAX - 1
+  const IterUnit unit = iter_unit<uint32_t(WG)>();
+  const uint32_t tid = unit.tid, chunk = unit.chunk;  // (the lane's place in its chunk; threadIdx.x addresses the staging alone)
   const uint32_t i = chunk * BLOCK + tid;
   if (i >= c.n) return;
   Op op;
@@ -2267,9 +2296,10 @@ __global__ __launch_bounds__(BLOCK) void k_build_rows_op(StepConsts<N> c, typena
   // the cursor and "cursor += hit ? SLOT : 0" — a select and a full-rate add, no address arithmetic per candidate.  (The
   // cursor is a 32-bit LDS address kept opaque to the compiler, which otherwise rewrites it as base + offset and adds the
   // base again before every store.)
-  constexpr uint32_t SLOT = BLOCK * 4u;
+  constexpr uint32_t SLOT = uint32_t(WG) * 4u;
+  static_assert(SLOT % 256u == 0u, "a staging slot is whole rows of 64 banks: the lanes' stores stay conflict-free");
   typedef __attribute__((address_space(3))) uint32_t *LdsWord;
-  unsigned char *const lbasePtr = reinterpret_cast<unsigned char *>(list) + tid * 4u;
+  unsigned char *const lbasePtr = reinterpret_cast<unsigned char *>(list) + threadIdx.x * 4u;
   const uint32_t lbase = uint32_t(uintptr_t((__attribute__((address_space(3))) unsigned char *)lbasePtr));
   const uint32_t lfull = lbase + uint32_t(LMAX) * SLOT;  // the cursor of a lane whose LMAX slots are taken
   auto staged = [&](uint32_t byteOff) -> uint32_t & { return *reinterpret_cast<uint32_t *>(lbasePtr + byteOff); };
@@ -2407,14 +2437,17 @@ template <typename N> __device__ inline void pin_registers(SurfSrc<N> &b) {
 // latencies (list entry -> candidate) instead of leaning on the other waves of its SIMD.  Slots past the row (the
 // prefetch runs up to 3 W - 1 ahead) are clamped to the row's last slot and their entries discarded, never used as
 // an address.  Same candidates in the same order: bit-identical to the serial form.
-template <typename N, typename Op, bool PIPELINED = true, bool ROWS = false>
-__global__ __launch_bounds__(BLOCK) void k_gather_from_lists(StepConsts<N> c, typename Op::Args args,
-                                                             const uint32_t *__restrict__ key,
-                                                             const uint32_t *__restrict__ table,
-                                                             NbrLists lists, RowWalk rw = {}) {
-  const uint32_t tid = threadIdx.x;
-  const uint32_t chunk = xcd_chunk();
-  const uint32_t i = chunk * BLOCK + tid;
+// WG (the plain reader on the row-major copy only; the others stay at BLOCK): the workgroup's width, a unit of its chunk like the
+// row build's — a narrower workgroup starts as soon as the registers of ITS waves are free.  (Measured the same at 64, 128 and
+// 256, profiles/wave_workgroups_1m.md: the reader is held at seven waves per SIMD by registers, not by LDS.  Default 256.)
+template <typename N, typename Op, bool PIPELINED = true, bool ROWS = false, int WG = BLOCK>
+__global__ __launch_bounds__(WG) void k_gather_from_lists(StepConsts<N> c, typename Op::Args args,
+                                                          const uint32_t *__restrict__ key,
+                                                          const uint32_t *__restrict__ table,
+                                                          NbrLists lists, RowWalk rw = {}) {
+  static_assert(WG == BLOCK || (!PIPELINED && ROWS), "only the plain reader on the row-major copy runs at other widths");
+  const IterUnit unit = iter_unit<uint32_t(WG)>();
+  const uint32_t i = unit.chunk * BLOCK + unit.tid;
   if (i >= c.n) return;
   Op op;
   if (!op.begin(c, args, i)) return;
