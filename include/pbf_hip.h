@@ -300,8 +300,9 @@ int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);
  * bounds may be infinite); mass <= 0; an inertia <= 0; gain < 0; a damping < 0; a factor other than 0 or 1; centre_min >
  * centre_max; a start pose pbf_set_collider_pose would refuse.
  *
- * Limitations: one body per ctx; no contact of the body with the box or with obstacles beyond the centre bounds; no swept
- * collision (a body that moves further per step than its own thickness can pass through fluid); no restitution; no gyroscopic
+ * Limitations: one body per ctx; no contact of the body with the box or with obstacles beyond the centre bounds (contact
+ * with the scenery: pbf_set_collider_body_contact, below); no swept collision (a body that moves further per step than its
+ * own thickness can pass through fluid); no restitution against the fluid; no gyroscopic
  * term (a spinning asymmetric body does not precess); not in slab mode; whitewater and the observers still do not see the
  * solid. */
 typedef struct pbf_collider_body {
@@ -552,8 +553,8 @@ int pbf_mesh_winding(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf 
  * pbf_scenery_sample is pbf_collider_sample on the scenery's lattice (always the static function): the same arguments,
  * outputs and refusals, PBF_ERR_STATE without scenery.
  *
- * Limitations: the body does not collide with the scenery — only its centre bounds hold it.  There is no friction
- * against the scenery and no reaction on it.  Whitewater's diffuse particles and the observers do not see it.  One
+ * Limitations: the body collides with the scenery only with pbf_set_collider_body_contact (below) on — otherwise only its
+ * centre bounds hold it.  There is no friction of the fluid against the scenery and no reaction on it.  Whitewater's diffuse particles and the observers do not see it.  One
  * collider and one static scenery lattice per ctx: several static solids are composed into the scenery's lattice on the
  * host, by the min of their distances.  Not in slab mode. */
 int pbf_set_scenery(pbf_ctx *ctx, const pbf_collider_sdf *sdf);   /* NULL clears and frees the lattice */
@@ -561,6 +562,98 @@ int pbf_set_scenery_mesh(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_
                          pbf_mesh_sdf_stats *stats /* may be NULL */);
 int pbf_scenery_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const double *points /* 3n, world */,
                        void *phi /* N[n] */, void *moved /* N[3n], solver frame */, uint8_t *hit /* [n] */);
+
+/* Body contact: the rigid body collides with the scenery, on the device (no reference counterpart).  Opt-in: a ctx that
+ * never calls pbf_set_collider_body_contact — a ctx with a body and scenery included — launches exactly what it launched
+ * before and produces the same bytes.
+ *
+ * The body's surface.  The call takes a fixed point set from the collider's lattice, once, at configure time (two kernels
+ * around the library's scan, and one synchronisation to read the count; it is not a step).  One lane per cell (i, j, k) of
+ * the lattice whose three indices are multiples of `stride`; the cell gives a point iff all eight nodes are finite, some
+ * node is < N(level) and some node is >= N(level), and, with b_a = N(origin_a) + (N(i_a) + N(0.5)) * N(spacing), the static
+ * contract above on the collider's lattice with margin := N(level) at b returns inside with len > 0 and p_a = b_a + s * g_a
+ * finite (s = (margin - phi) / len whatever `hit` says, so a centre outside the level is pulled in).  p is the point, in N,
+ * in the body frame.  Points are stored in cell-index order ((i * cells_y + j) * cells_z + k), so one lattice gives one
+ * array on every run.  pbf_collider_body_contact_points returns the count and, where points != NULL, the array.
+ *
+ * The step.  With contact on, stage_body runs `iterations` passes after the body's advance, each two launches with fixed
+ * arguments: one lane per point, then one workgroup.  No read-back, nothing allocated, no atomics: the sums are a fold of a
+ * fixed shape (lanes by an xor butterfly, waves in wave order, partial records 256 at a time in index order), so the same
+ * state gives the same bytes eagerly, through pbf_steps and in a replayed graph.
+ *
+ * The contract (csrc/pbf_body_contact.hpp, plain C++ shared by the kernel and a stand-alone host program).  R and x are the
+ * body record's pose in double; everything is in the order written, not contracted; PBF_FLAG_FAST_MATH does not reach it.
+ * Per point b (N, body frame):
+ *   r_a = (R[a][0] b_0 + R[a][1] b_1) + R[a][2] b_2        w_a = r_a + x_a
+ *   the static contract on the scenery's lattice with margin := N(skin), at (N(w_0), N(w_1), N(w_2))  ->  inside, hit, s, g
+ *   m_a = double(s) * double(g_a)          d = sqrt((m_0 m_0 + m_1 m_1) + m_2 m_2)
+ *   in contact  =  inside && hit && d > 0 && d finite
+ *   sums over the points in contact:  S = sum d,  M_a = sum m_a,  A_a = sum d * r_a,  D = max d,  count
+ * The response, in double.  mass, inertia, F = linear_factor, G = angular_factor and the centre bounds are the body's; e =
+ * restitution, mu = friction, beta = correction; x, v, w the body's centre, velocity and angular velocity:
+ *   passes += 1;  the raw sums S, M, A, D go to the state, impulse = shift = 0
+ *   count == 0: done                                                        (the sums are the zeros)
+ *   ln = sqrt((M_0 M_0 + M_1 M_1) + M_2 M_2)
+ *   S, an M_a, an A_a, D or ln non-finite, or !(ln > 0): rejected += 1, done                  (opposite walls cancel)
+ *   n_a = M_a / ln          r_a = A_a / S          contacts += 1
+ *   cross(p, q) = (p_1 q_2 - p_2 q_1,  p_2 q_0 - p_0 q_2,  p_0 q_1 - p_1 q_0)
+ *   dot(p, q)   = (p_0 q_0 + p_1 q_1) + p_2 q_2
+ *   W(c):  h_b = (R[0][b] c_0 + R[1][b] c_1) + R[2][b] c_2 ;  k_b = h_b / inertia_b
+ *          W_a = ((R[a][0] k_0 + R[a][1] k_1) + R[a][2] k_2) * G_a
+ *   Wn = W(cross(r, n))
+ *   kn = ((F_0 n_0 n_0 + F_1 n_1 n_1) + F_2 n_2 n_2) / mass + dot(n, cross(Wn, r))          (F_a n_a n_a = (F_a * n_a) * n_a)
+ *   u  = v + cross(w, r)          un = dot(u, n)
+ *   un < 0 && kn > 0:  j = -((1 + e) * un) / kn ;  v_a = v_a + ((j * n_a) / mass) * F_a ;  w_a = w_a + j * Wn_a
+ *   else:              j = 0
+ *   mu > 0 && j > 0:   u' = v + cross(w, r) ;  c = dot(u', n) ;  ut_a = u'_a - c * n_a
+ *                      lt = sqrt((ut_0 ut_0 + ut_1 ut_1) + ut_2 ut_2)
+ *                      lt > 0:  t_a = ut_a / lt ;  Wt = W(cross(r, t))
+ *                               kt = ((F_0 t_0 t_0 + F_1 t_1 t_1) + F_2 t_2 t_2) / mass + dot(t, cross(Wt, r))
+ *                               kt > 0:  jt = min(mu * j, lt / kt)
+ *                                        v_a = v_a - ((jt * t_a) / mass) * F_a ;  w_a = w_a - jt * Wt_a
+ *                      (jt = 0 and t = 0 wherever a condition fails)
+ *   impulse_a = j * n_a - jt * t_a
+ *   s = beta * max(D - slop, 0) ;  shift_a = (s * n_a) * F_a ;  x_a = x_a + shift_a
+ *   x_a < centre_min_a or > centre_max_a: x_a = that bound, v_a = 0           (exactly as advance() applies the bounds)
+ *   pose.trans = x (rot and q unchanged); the kernel rewrites N(x) in the pose record the delta-p launches read
+ * The body record's layout and struct pbf_collider_body_state do not change.
+ *
+ * pbf_set_collider_body_contact needs a body that is on and installed scenery (PBF_ERR_STATE otherwise, and in slab mode
+ * as every collider call).  PBF_ERR_INVALID, each with its reason, leaving everything unchanged: a non-finite field; stride
+ * < 1; skin < 0; restitution or correction outside [0, 1]; friction < 0; slop < 0; iterations outside 1..8; a lattice that
+ * yields no point.  Off -> on and on -> off change the launch sequence and drop the captured graphs; so do another level or
+ * stride (another point set) and another number of iterations while on.  Any other change of parameters while on rewrites
+ * the device record by value with a one-lane kernel, like a re-placed body: no synchronisation, no graph dropped; the
+ * counters start again.  NULL turns contact off and frees its buffers; so do pbf_set_collider_body(ctx, NULL),
+ * pbf_set_collider / pbf_set_collider_mesh (clearing included: they turn the body off) and pbf_set_scenery(ctx, NULL) /
+ * a cleared pbf_set_scenery_mesh.  A replaced scenery keeps contact on (the points belong to the body); a re-placed body
+ * keeps it on and zeroes the counters.
+ *
+ * pbf_collider_body_contact_state is an observer between steps like pbf_collider_body_state: it synchronises (a polled
+ * mailbox), is part of no step and changes nothing a step reads.  PBF_ERR_STATE while contact is off.
+ *
+ * Limitations: no contact with the box walls or with obstacle particles (walls are composed into the scenery's lattice);
+ * the position correction translates and never rotates the body; one averaged contact per pass, not a per-point manifold;
+ * no swept contact; one body; not in slab mode; the scenery receives no reaction. */
+typedef struct pbf_body_contact {
+  double level;        /* the body's surface is phi_collider == level (world units, finite) */
+  uint32_t stride;     /* >= 1: only cells whose three indices are multiples of stride give a point */
+  double skin;         /* >= 0: a point is in contact where phi_scenery < skin */
+  double restitution;  /* in [0, 1] */
+  double friction;     /* mu >= 0 */
+  double correction;   /* in [0, 1]: the share of the depth removed per pass */
+  double slop;         /* >= 0: depth left alone */
+  uint32_t iterations; /* 1..8 detect + resolve passes per step */
+} pbf_body_contact;
+int pbf_set_collider_body_contact(pbf_ctx *ctx, const pbf_body_contact *contact);   /* NULL: off */
+int pbf_collider_body_contact_points(pbf_ctx *ctx, uint64_t *n, void *points /* N[3n], body frame; may be NULL */);
+struct pbf_body_contact_state {
+  double depth_sum, push[3], arm[3], depth_max;   /* the raw sums of the LAST pass: S, M, A, D */
+  double impulse[3], shift[3];                    /* what that pass applied */
+  uint64_t points;                                /* points of the body's surface */
+  uint64_t passes, contacts, rejected;            /* passes since configured; of which responded; of which were refused */
+};
+int pbf_collider_body_contact_state(pbf_ctx *ctx, struct pbf_body_contact_state *out);  /* observer; synchronises */
 
 /* ---- particle state (replaces the std::vector<Particle>& in/out argument, src/sph.hpp:124) */
 int pbf_upload(pbf_ctx *ctx, size_t n, const uint64_t *id, const uint8_t *type, const void *mass, const void *pos,

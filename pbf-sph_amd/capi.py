@@ -216,6 +216,25 @@ def collider_body(mass, inertia=(1.0, 1.0, 1.0), rot=np.eye(3), centre=(0.0, 0.0
     return b
 
 
+class BodyContact(C.Structure):
+    """pbf_body_contact (include/pbf_hip.h)"""
+    _fields_ = [("level", C.c_double), ("stride", C.c_uint32), ("skin", C.c_double), ("restitution", C.c_double),
+                ("friction", C.c_double), ("correction", C.c_double), ("slop", C.c_double), ("iterations", C.c_uint32)]
+
+
+class BodyContactState(C.Structure):
+    """struct pbf_body_contact_state (include/pbf_hip.h)"""
+    _fields_ = [("depth_sum", C.c_double), ("push", C.c_double * 3), ("arm", C.c_double * 3), ("depth_max", C.c_double),
+                ("impulse", C.c_double * 3), ("shift", C.c_double * 3), ("points", C.c_uint64), ("passes", C.c_uint64),
+                ("contacts", C.c_uint64), ("rejected", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: np.array(getattr(self, k)) for k in ("push", "arm", "impulse", "shift")}
+        d.update(depth_sum=float(self.depth_sum), depth_max=float(self.depth_max), points=int(self.points), passes=int(self.passes),
+                 contacts=int(self.contacts), rejected=int(self.rejected))
+        return d
+
+
 class ColliderFriction(C.Structure):
     """pbf_collider_friction (include/pbf_hip.h)"""
     _fields_ = [("mu", C.c_double), ("velocity", C.c_double * 3), ("angular_velocity", C.c_double * 3)]
@@ -271,6 +290,9 @@ _SIGS = {
     "pbf_set_collider_body": (C.c_int, [C.c_void_p, C.POINTER(ColliderBody)]),
     "pbf_collider_body_state": (C.c_int, [C.c_void_p, C.POINTER(ColliderBodyState)]),
     "pbf_stage_body": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
+    "pbf_set_collider_body_contact": (C.c_int, [C.c_void_p, C.POINTER(BodyContact)]),
+    "pbf_collider_body_contact_points": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "pbf_collider_body_contact_state": (C.c_int, [C.c_void_p, C.POINTER(BodyContactState)]),
     "pbf_set_collider_friction": (C.c_int, [C.c_void_p, C.POINTER(ColliderFriction)]),
     "pbf_collider_friction_reaction": (C.c_int, [C.c_void_p, C.POINTER(ColliderWrench)]),
     "pbf_mesh_records": (C.c_int, [C.POINTER(Mesh), C.c_int, C.c_void_p, C.POINTER(MeshInfo)]),
@@ -691,6 +713,38 @@ class Solver:
         st = ColliderBodyState()
         self._chk(self.L.pbf_collider_body_state(self.ctx, C.byref(st)), "pbf_collider_body_state")
         return st if raw else st.as_dict()
+
+    def set_collider_body_contact(self, level=0.0, stride=1, skin=0.0, restitution=0.0, friction=0.0, correction=0.8, slop=0.0,
+                                  iterations=1, on=True):
+        """Contact of the body with the scenery (pbf_set_collider_body_contact, include/pbf_hip.h): the body's surface, phi ==
+        level of the collider's lattice sampled every `stride` cells, is tested against the scenery after every advance,
+        `iterations` times per step, and answered with one impulse (restitution, Coulomb friction) and a shift of the centre
+        (`correction` of the depth beyond `slop`) on the device.  Needs a body and scenery.  on=False turns it off.  Calling
+        it again with the same level and stride rewrites the device record without a recapture."""
+        if not on:
+            self._chk(self.L.pbf_set_collider_body_contact(self.ctx, None), "pbf_set_collider_body_contact")
+            return self
+        c = BodyContact(float(level), int(stride), float(skin), float(restitution), float(friction), float(correction), float(slop),
+                        int(iterations))
+        self._chk(self.L.pbf_set_collider_body_contact(self.ctx, C.byref(c)), "pbf_set_collider_body_contact")
+        return self
+
+    def collider_body_contact_state(self, raw=False):
+        """The contact's state between steps (pbf_collider_body_contact_state; it synchronises) -> dict(depth_sum, push (3,),
+        arm (3,), depth_max — the raw sums of the last pass —, impulse, shift — what that pass applied —, points, passes,
+        contacts, rejected); raw: the BodyContactState itself."""
+        st = BodyContactState()
+        self._chk(self.L.pbf_collider_body_contact_state(self.ctx, C.byref(st)), "pbf_collider_body_contact_state")
+        return st if raw else st.as_dict()
+
+    def collider_body_contact_points(self):
+        """The body's surface points (pbf_collider_body_contact_points) -> (n, 3) of the solver's dtype, body frame, in
+        cell-index order"""
+        n = C.c_uint64(0)
+        self._chk(self.L.pbf_collider_body_contact_points(self.ctx, C.byref(n), None), "pbf_collider_body_contact_points")
+        pts = np.empty((int(n.value), 3), self.dtype)
+        self._chk(self.L.pbf_collider_body_contact_points(self.ctx, C.byref(n), _vp(pts)), "pbf_collider_body_contact_points")
+        return pts
 
     def set_collider_friction(self, mu=None, velocity=(0.0, 0.0, 0.0), angular_velocity=(0.0, 0.0, 0.0)):
         """Coulomb friction against the installed collider (pbf_set_collider_friction, include/pbf_hip.h): one pass after every

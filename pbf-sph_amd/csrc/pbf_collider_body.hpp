@@ -44,7 +44,8 @@
 //            one non-finite P or L: no kick, and `rejected` goes up by one
 //
 // Limitations: there is no gyroscopic term (w x I w): a spinning asymmetric body does not precess.  No contact of the body
-// with the box or with obstacles beyond the bounds of its centre, no swept collision, no restitution.
+// with the box or with obstacles beyond the bounds of its centre (contact with the scenery: csrc/pbf_body_contact.hpp), no
+// swept collision, no restitution against the fluid.
 #pragma once
 
 #include <cstddef>

@@ -34,6 +34,8 @@
 #include "pbf_solid_lattice.hpp"
 #include "pbf_collider_pose.hpp"
 #include "pbf_collider_friction.hpp"
+#include "pbf_body_contact.hpp"
+#include "pbf_body_contact_kernels.hpp"
 
 using namespace pbf;
 
@@ -152,6 +154,7 @@ struct GraphKey {
   uint64_t n;
   uint64_t collider;  // ColliderState::gen: a replay never runs on a lattice (the collider's or the scenery's) that has been
                       // replaced or freed, nor another launch sequence
+  uint64_t contact;   // bodycontact::Mode::gen: the body's contact passes, their number and their point buffer
   int options[12];
   bool operator<(const GraphKey &o) const { return std::memcmp(this, &o, sizeof(GraphKey)) < 0; }
 };
@@ -239,6 +242,13 @@ struct pbf_ctx {
   // pbf_set_collider_body: the one colliderbody::Record on the device (parameters and state; allocated by the first call)
   DevBuf bodyRec;
   Mailbox<BodyStateRecord> hostBody;
+  // pbf_set_collider_body_contact (csrc/pbf_body_contact.hpp): on / off, the point count, the passes per step and the
+  // generation, changed through its events only; the configuration as given; the body's surface points in N (body frame), one
+  // partial record per DIAG_TILE points, the one bodycontact::Record on the device, and the observer's pinned mailbox
+  bodycontact::Mode contact;
+  pbf_body_contact contactCfg{};
+  DevBuf contactPoints, contactPartials, contactRec;
+  Mailbox<ContactStateRecord> hostContact;
   // pbf_set_collider_friction: the record {mu, V, W} the pass reads through a pointer, the device's counters, the pass's own
   // partial records (they outlive the step: the observer and the next step's body stage fold them)
   DevBuf frictionRec, frictionCtl, frictionPartials;
@@ -1486,6 +1496,18 @@ template <typename N> int stage_body(pbf_ctx *ctx, const pbf_params *p) {
   else
     hipLaunchKernelGGL((k_body_advance<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, nb, ctx->pushPartials.as<const WrenchPartial>(),
                        double(p->dt), ctx->bodyRec.as<colliderbody::Record>(), ctx->colliderPose.as<ColliderPose<N>>());
+  if (ctx->contact.on) {  // (pbf_set_collider_body_contact: the advanced body against the scenery, `iterations` passes of two launches)
+    const uint32_t np = uint32_t(ctx->contact.points), cnb = (np + DIAG_TILE - 1) / DIAG_TILE;
+    const ColliderSdf<N> scenery = sdf_args<N>(ctx->solid[ColliderState::SCENERY]);  // (its margin is replaced by the record's skin)
+    for (uint32_t it = 0; it < ctx->contact.iterations; ++it) {
+      hipLaunchKernelGGL((k_contact_partial<N>), dim3(cnb), dim3(BLOCK), 0, ctx->stream, scenery, np, ctx->contactPoints.as<const N>(),
+                         ctx->bodyRec.as<const colliderbody::Record>(), ctx->contactRec.as<const bodycontact::Record>(),
+                         ctx->contactPartials.as<ContactPartial>());
+      hipLaunchKernelGGL((k_contact_resolve<N>), dim3(1), dim3(BLOCK), 0, ctx->stream, cnb, ctx->contactPartials.as<const ContactPartial>(),
+                         ctx->bodyRec.as<colliderbody::Record>(), ctx->contactRec.as<bodycontact::Record>(),
+                         ctx->colliderPose.as<ColliderPose<N>>());
+    }
+  }
   LAUNCH_CHECK(ctx);
   return PBF_OK;
 }
@@ -1982,6 +2004,7 @@ GraphKey graph_key(pbf_ctx *ctx, const pbf_params *p, const StepState &before) {
   std::memcpy(k.params + sizeof(v) + 16, st, 16);
   k.n = ctx->n;
   k.collider = ctx->col.gen;
+  k.contact = ctx->contact.gen;
   const int opt[12] = {ctx->gatherKind, ctx->splitBuild, ctx->coop, ctx->pipeline, int(ctx->cellDiffuse), int(ctx->overlapDiffuse),
                        int(ctx->fuseDiffuse), int(ctx->reuseLists), int(ctx->listMax), int(ctx->tileCap), ctx->buildWg, ctx->readerWg};
   std::memcpy(k.options, opt, sizeof(opt));
@@ -2613,6 +2636,16 @@ int collider_drop_graphs(pbf_ctx *ctx) {
   ctx->graphs.clear();
   return PBF_OK;
 }
+// Body contact off (pbf_set_collider_body_contact(NULL), a cleared body, a replaced or cleared collider, a cleared scenery):
+// the step loses its passes, so the captured graphs go (which synchronises), then the buffers are freed.
+int contact_clear(pbf_ctx *ctx) {
+  if (!ctx->contact.cleared()) return PBF_OK;
+  if (int rc = collider_drop_graphs(ctx)) return rc;
+  HIPCHK(ctx, ctx->contactPoints.reset());
+  HIPCHK(ctx, ctx->contactPartials.reset());
+  HIPCHK(ctx, ctx->contactRec.reset());
+  return PBF_OK;
+}
 // The one install path of both solids: `fresh` (the lattice on the device, empty when sdf == NULL clears) becomes the ctx's
 // collider or scenery.  Every install moves the captured steps' key.  A collider and scenery together run
 // DeltaOp<.., COLLIDE_REACT_SCENERY>, which writes the records: the call that completes the pair turns the reaction on if it
@@ -2622,6 +2655,8 @@ int solid_install(pbf_ctx *ctx, ColliderState::Solid which, const pbf_collider_s
   if (ctx->col.install_needs_reaction(which, sdf != nullptr))
     if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;
   if (int rc = collider_drop_graphs(ctx)) return rc;  // (first: they hold the old lattice's address)
+  if (which == ColliderState::COLLIDER || !sdf)  // (the points came from the old collider; without scenery there is nothing to touch)
+    if (int rc = contact_clear(ctx)) return rc;
   ctx->solid[which].put(sdf, fresh);                  // (frees the old lattice)
   if (!(which == ColliderState::SCENERY ? ctx->col.scenery_installed(sdf != nullptr) : ctx->col.installed(sdf != nullptr)))
     return fail(ctx, PBF_ERR_STATE, "a collider beside scenery needs the reaction records");  // (enabled above: not reached)
@@ -2784,6 +2819,61 @@ int collider_sample_impl(pbf_ctx *ctx, const ColliderSdf<N> &sdf, const Collider
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pts is a temporary; the caller reads the answers)
   return PBF_OK;
 }
+// pbf_set_collider_body_contact with a configuration that passed its checks, a body on and scenery installed.  The same level
+// and stride as the points in place: the record alone is rewritten, by value, on the stream.  Otherwise the points are taken
+// from the collider's lattice — count, scan, one read-back of the total, emit — into buffers of their own, and only when
+// everything a step will need exists do they replace the ctx's: a refusal or a failed allocation leaves everything as it was.
+template <typename N> int body_contact_configure(pbf_ctx *ctx, const pbf_body_contact *c) {
+  if (ctx->contact.same_points(c->level, c->stride)) {
+    hipLaunchKernelGGL(k_contact_store, dim3(1), dim3(1), 0, ctx->stream, bodycontact::record_of(*c, ctx->contact.points),
+                       ctx->contactRec.as<bodycontact::Record>());
+    LAUNCH_CHECK(ctx);
+    ctx->contactCfg = *c;
+    return ctx->contact.rewritten(c->iterations) ? collider_drop_graphs(ctx) : PBF_OK;  // (another number of passes: other launches)
+  }
+  const auto &lat = ctx->solid[ColliderState::COLLIDER];
+  ColliderSdf<N> sdf = sdf_args<N>(lat);
+  sdf.margin = N(c->level);
+  ContactCells cells{};
+  cells.stride = c->stride;
+  uint64_t lanes = 1;
+  for (int a = 0; a < 3; ++a) {
+    cells.cells[a] = uint32_t((uint64_t(lat.dims[a]) - 2u) / c->stride + 1u);  // (ceil((dims - 1) / stride), dims >= 2)
+    lanes *= cells.cells[a];
+  }
+  cells.lanes = uint32_t(lanes);  // (< 2^31: at most the node count)
+  const uint32_t len = cells.lanes + 1, snb = (len + SCAN_TILE - 1) / SCAN_TILE;
+  DevBuf counts, offsets, sums, points, partials, rec;
+  HIPCHK(ctx, hipMalloc(&counts.p, (size_t(len) + SCAN_TILE) * 4));
+  HIPCHK(ctx, hipMalloc(&offsets.p, (size_t(len) + SCAN_TILE) * 4));
+  HIPCHK(ctx, hipMalloc(&sums.p, (size_t(snb) + 1) * 4));
+  ctx->allocEpoch++;
+  HIPCHK(ctx, hipMemsetAsync(counts.as<uint32_t>() + cells.lanes, 0, 4, ctx->stream));  // closing sentinel: offsets[lanes] = total
+  hipLaunchKernelGGL((k_contact_count<N>), grid_for(cells.lanes), dim3(BLOCK), 0, ctx->stream, sdf, N(lat.spacing), cells, counts.as<uint32_t>());
+  launch_scans(ctx, scan_job(counts.as<const uint32_t>(), len, sums.as<uint32_t>(), offsets.as<uint32_t>()), 1);
+  LAUNCH_CHECK(ctx);
+  uint32_t total = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&total, offsets.as<uint32_t>() + cells.lanes, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the point buffer is sized from the count
+  if (total == 0) return fail(ctx, PBF_ERR_INVALID, "pbf_set_collider_body_contact: the lattice yields no point (no cell crosses the level)");
+  const uint32_t nb = (total + DIAG_TILE - 1) / DIAG_TILE;
+  HIPCHK(ctx, hipMalloc(&points.p, size_t(total) * 3 * sizeof(N)));
+  points.cap = size_t(total) * 3 * sizeof(N);
+  HIPCHK(ctx, hipMalloc(&partials.p, size_t(nb) * sizeof(ContactPartial)));
+  partials.cap = size_t(nb) * sizeof(ContactPartial);
+  HIPCHK(ctx, hipMalloc(&rec.p, sizeof(bodycontact::Record)));
+  rec.cap = sizeof(bodycontact::Record);
+  HIPCHK(ctx, ctx->hostContact.rec.ensure(1));  // (so that the observer allocates nothing either)
+  hipLaunchKernelGGL((k_contact_emit<N>), grid_for(cells.lanes), dim3(BLOCK), 0, ctx->stream, sdf, N(lat.spacing), cells,
+                     offsets.as<const uint32_t>(), total, points.as<N>());
+  hipLaunchKernelGGL(k_contact_store, dim3(1), dim3(1), 0, ctx->stream, bodycontact::record_of(*c, total), rec.as<bodycontact::Record>());
+  LAUNCH_CHECK(ctx);
+  if (int rc = collider_drop_graphs(ctx)) return rc;  // (synchronises: the scan's scratch is local, and no replay holds the old buffers)
+  ctx->contactPoints = std::move(points), ctx->contactPartials = std::move(partials), ctx->contactRec = std::move(rec);
+  ctx->contactCfg = *c;
+  ctx->contact.configured(total, c->iterations, c->level, c->stride);
+  return PBF_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2852,8 +2942,10 @@ int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body) {
   }
   if (int rc = collider_needed(ctx, "pbf_set_collider_body")) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!body)  // off: the solid stays where it is, as an ordinary pose; the reaction stays on
+  if (!body) {  // off: the solid stays where it is, as an ordinary pose; the reaction stays on (contact goes with the body)
+    if (int rc = contact_clear(ctx)) return rc;
     return ctx->col.body_cleared() ? collider_drop_graphs(ctx) : PBF_OK;
+  }
   if (int rc = pbf_set_collider_reaction(ctx, 1)) return rc;  // (a no-op when it is on already)
   if (int rc = ensure(ctx, ctx->colliderPose, sizeof(ColliderPose<double>))) return rc;
   if (int rc = ensure(ctx, ctx->bodyRec, sizeof(colliderbody::Record))) return rc;
@@ -2869,6 +2961,9 @@ int pbf_set_collider_body(pbf_ctx *ctx, const pbf_collider_body *body) {
   // body as placed here does not receive them)
   if (ctx->col.friction)
     hipLaunchKernelGGL(k_friction_pending_clear, dim3(1), dim3(1), 0, ctx->stream, ctx->frictionCtl.as<colliderfriction::Ctl>());
+  if (ctx->contact.on)  // (a re-placed body keeps its contact and its points; the counters start again)
+    hipLaunchKernelGGL(k_contact_store, dim3(1), dim3(1), 0, ctx->stream, bodycontact::record_of(ctx->contactCfg, ctx->contact.points),
+                       ctx->contactRec.as<bodycontact::Record>());
   LAUNCH_CHECK(ctx);
   return ctx->col.body_set() ? collider_drop_graphs(ctx) : PBF_OK;  // (a re-placed body changes no key and drops no graph)
 }
@@ -2883,6 +2978,48 @@ int pbf_collider_body_state(pbf_ctx *ctx, struct pbf_collider_body_state *out) {
   hipLaunchKernelGGL(k_body_read, dim3(1), dim3(1), 0, ctx->stream, ctx->bodyRec.as<const colliderbody::Record>(), ctx->hostBody.rec.p, seq);
   LAUNCH_CHECK(ctx);
   return receive(ctx, ctx->hostBody, "collider body read-back", *out);
+}
+
+static_assert(sizeof(struct pbf_body_contact_state) == 18 * 8 && offsetof(ContactStateRecord, seq) == sizeof(struct pbf_body_contact_state) &&
+                  sizeof(bodycontact::Record) == (5 + 18) * 8,
+              "the contact record is doubles and 64-bit counters throughout (k_contact_read copies it in 64-bit words)");
+int pbf_set_collider_body_contact(pbf_ctx *ctx, const pbf_body_contact *contact) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (contact) {
+    const char *why = nullptr;
+    if (bodycontact::check(contact, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  }
+  if (int rc = collider_refuse_slab(ctx)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!contact) return contact_clear(ctx);
+  if (!ctx->col.body) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_body_contact: no body set (pbf_set_collider_body)");
+  if (!scenery_on(ctx)) return fail(ctx, PBF_ERR_STATE, "pbf_set_collider_body_contact: no scenery set (pbf_set_scenery)");
+  return ctx->fp64 ? body_contact_configure<double>(ctx, contact) : body_contact_configure<float>(ctx, contact);
+}
+
+int pbf_collider_body_contact_points(pbf_ctx *ctx, uint64_t *n, void *points) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!n) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_body_contact_points: n == NULL");
+  if (!ctx->contact.on) return fail(ctx, PBF_ERR_STATE, "pbf_collider_body_contact_points: contact is off (pbf_set_collider_body_contact)");
+  *n = ctx->contact.points;
+  if (!points) return PBF_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpyAsync(points, ctx->contactPoints.p, size_t(ctx->contact.points) * 3 * (ctx->fp64 ? 8 : 4), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
+}
+
+int pbf_collider_body_contact_state(pbf_ctx *ctx, struct pbf_body_contact_state *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_collider_body_contact_state: out == NULL");
+  if (!ctx->contact.on) return fail(ctx, PBF_ERR_STATE, "pbf_collider_body_contact_state: contact is off (pbf_set_collider_body_contact)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  uint32_t seq;
+  HIPCHK(ctx, ctx->hostContact.arm(seq));
+  hipLaunchKernelGGL(k_contact_read, dim3(1), dim3(1), 0, ctx->stream, ctx->contactRec.as<const bodycontact::Record>(), ctx->hostContact.rec.p, seq);
+  LAUNCH_CHECK(ctx);
+  return receive(ctx, ctx->hostContact, "body contact read-back", *out);
 }
 
 static_assert(sizeof(pbf_collider_friction) == 7 * 8, "the friction record is seven doubles: mu, V, W");

@@ -60,6 +60,10 @@ struct Args {
   bool colliderBody = false;
   double colliderBodyCfg[5] = {0, 0, 0, 0, 0.49};   // mass, the principal moments (0 = a solid ball of the collider's radius), gain
   size_t colliderBodyReport = 0;          // 0 = off
+  // --collider-body-contact[=restitution[,mu[,iterations]]] with --collider-body and --scenery: the body collides with the
+  // scenery (pbf_set_collider_body_contact); the report line then carries contact_points, contact_depth and contacts
+  bool colliderBodyContact = false;
+  double colliderBodyContactCfg[3] = {0, 0, 1};   // restitution, mu, iterations
   // --collider-friction=mu with --resident and --collider: Coulomb friction against the solid (pbf_set_collider_friction; inf =
   // no-slip), relative to --collider-motion's velocities when given; --collider-friction-report[=every] prints the pass's sums
   double colliderFriction = 0;            // 0 = off
@@ -151,6 +155,12 @@ struct Args {
           "                                        about the lattice's axes (default: a solid ball of the sphere's radius);\n"
           "                                        gain 0.49 (default) returns the momentum the fluid was given\n"
           "      --collider-body-report[=every]    One JSON line per `every` frames with the body's state\n"
+          "      --collider-body-contact[=restitution[,mu[,iterations]]]  With --collider-body and --scenery: the body collides\n"
+          "                                        with the scenery — its surface (the collider's zero level, one point per\n"
+          "                                        crossed lattice cell) is tested against the scenery after every advance and\n"
+          "                                        answered with an impulse and a shift of the centre on the device. Defaults:\n"
+          "                                        restitution 0, mu 0, 1 pass per step. The report line gains contact_points,\n"
+          "                                        contact_depth and contacts\n"
           "      --collider-friction=[mu]          With --resident and --collider: Coulomb friction against the solid, one pass\n"
           "                                        after every finalise; mu > 0, inf = no-slip. With --collider-motion the drag is\n"
           "                                        towards the moving solid's contact velocity, with --collider-body the body's\n"
@@ -325,6 +335,17 @@ struct Args {
           if (f.size() != 1) throw std::runtime_error("--collider-friction: expected mu");
           if (!(f[0] > 0)) throw std::runtime_error("--collider-friction: mu must be > 0 (inf = no-slip)");
           colliderFriction = f[0];
+        }
+        else if (a == "--collider-body-contact") colliderBodyContact = true;
+        else if (a.rfind("--collider-body-contact=", 0) == 0) {
+          const auto f = numbers(a.substr(24));
+          if (f.empty() || f.size() > 3) throw std::runtime_error("--collider-body-contact: expected restitution[,mu[,iterations]]");
+          for (double x : f)
+            if (!std::isfinite(x)) throw std::runtime_error("--collider-body-contact: the values must be finite");
+          if (f[0] < 0 || f[0] > 1 || (f.size() >= 2 && f[1] < 0) || (f.size() == 3 && (f[2] < 1 || f[2] > 8 || f[2] != std::floor(f[2]))))
+            throw std::runtime_error("--collider-body-contact: restitution in [0, 1], mu >= 0, iterations 1..8");
+          colliderBodyContact = true;
+          for (size_t k = 0; k < f.size(); ++k) colliderBodyContactCfg[k] = f[k];
         }
         else if (a == "--collider-body-report") colliderBodyReport = 1;
         else if (a.rfind("--collider-body-report=", 0) == 0) {

@@ -154,6 +154,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cout << "--collider-body / --collider-body-report take effect with --resident and --collider: ignored" << std::endl;
   const bool colliderBody = args.colliderBody && collider && args.resident;
   const size_t colliderBodyReport = colliderBody ? args.colliderBodyReport : 0;
+  if (args.colliderBodyContact && !(colliderBody && scenery)) {
+    std::cerr << "--collider-body-contact needs --collider-body and --scenery (with --resident and --collider): the body collides with the scenery"
+              << std::endl;
+    return 1;
+  }
+  const bool colliderBodyContact = args.colliderBodyContact;
   const size_t colliderReaction = collider && args.resident ? args.colliderReaction : 0;
   if ((args.colliderFriction > 0 || args.colliderFrictionReport) && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--collider-friction / --collider-friction-report are single-device features: they cannot be combined with --slabs / --all-devices"
@@ -303,6 +309,15 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     solver.setColliderBody(body);
     std::cout << "Collider body        : mass " << body.mass << ", moments " << body.inertia[0] << " " << body.inertia[1] << " " << body.inertia[2]
               << ", gain " << body.gain << ", centre " << bodyCentre[0] << " " << bodyCentre[1] << " " << bodyCentre[2] << std::endl;
+  }
+  if (colliderBodyContact) {  // the collider's zero level, every crossed cell; four fifths of the depth taken back per pass
+    pbf_body_contact contact{};
+    contact.level = 0, contact.stride = 1, contact.skin = 0, contact.correction = 0.8, contact.slop = 0;
+    contact.restitution = args.colliderBodyContactCfg[0], contact.friction = args.colliderBodyContactCfg[1];
+    contact.iterations = uint32_t(args.colliderBodyContactCfg[2]);
+    solver.setColliderBodyContact(contact);
+    std::cout << "Collider body contact: " << solver.colliderBodyContact().points << " surface points, restitution " << contact.restitution
+              << ", mu " << contact.friction << ", " << contact.iterations << " pass(es) per step" << std::endl;
   }
   if (colliderFriction) {  // (against a solid at rest; --collider-motion rewrites the velocities every frame, a body supplies its own)
     solver.setColliderFriction(args.colliderFriction);
@@ -480,7 +495,12 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     std::cout << "{\"frame\":" << frame << ",\"body\":{\"rot\":" << vecn(st.pose.rot, 9) << ",\"centre\":" << vecn(st.pose.trans, 3)
               << ",\"quat\":" << vecn(st.quat, 4) << ",\"velocity\":" << vecn(st.velocity, 3) << ",\"angular_velocity\":"
               << vecn(st.angular_velocity, 3) << ",\"impulse\":" << vecn(st.impulse, 3) << ",\"angular\":" << vecn(st.angular, 3)
-              << ",\"hits\":" << st.hits << ",\"steps\":" << st.steps << ",\"rejected\":" << st.rejected << "}}" << std::endl;
+              << ",\"hits\":" << st.hits << ",\"steps\":" << st.steps << ",\"rejected\":" << st.rejected;
+    if (colliderBodyContact) {  // (only with --collider-body-contact: without it the line is what it always was)
+      const struct pbf_body_contact_state cs = solver.colliderBodyContact();
+      std::cout << ",\"contact_points\":" << cs.points << ",\"contact_depth\":" << num(cs.depth_max) << ",\"contacts\":" << cs.contacts;
+    }
+    std::cout << "}}" << std::endl;
     diagMillis += duration_millis(hrc::now() - d0).count();
   };
   const bool probing = args.resident && !args.probes.empty();

@@ -563,6 +563,35 @@ public:
     check(pbf_collider_body_state(ctx_, &st), "pbf_collider_body_state");
     return st;
   }
+  // Body contact (pbf_set_collider_body_contact): the body collides with the scenery — its surface, phi == level of the
+  // collider's lattice sampled every `stride` cells, is tested against the scenery after every advance and answered with one
+  // impulse and a shift of the centre on the device, pbf_steps and graph replays included.  Needs a body and scenery.  Calling
+  // it again with the same level and stride rewrites the record without a recapture.  colliderBodyContact() synchronises;
+  // colliderBodyContactPoints() returns the surface points, 3 values of N each, in the body frame.
+  Solver &setColliderBodyContact(const pbf_body_contact &contact) {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_body_contact(ctx_, &contact), "pbf_set_collider_body_contact");
+    return *this;
+  }
+  Solver &clearColliderBodyContact() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    check(pbf_set_collider_body_contact(ctx_, nullptr), "pbf_set_collider_body_contact");
+    return *this;
+  }
+  struct pbf_body_contact_state colliderBodyContact() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    struct pbf_body_contact_state st {};
+    check(pbf_collider_body_contact_state(ctx_, &st), "pbf_collider_body_contact_state");
+    return st;
+  }
+  std::vector<N> colliderBodyContactPoints() {
+    if (multi()) throw std::runtime_error("a collider is a single-device feature");
+    uint64_t n = 0;
+    check(pbf_collider_body_contact_points(ctx_, &n, nullptr), "pbf_collider_body_contact_points");
+    std::vector<N> points(size_t(n) * 3);
+    check(pbf_collider_body_contact_points(ctx_, &n, points.data()), "pbf_collider_body_contact_points");
+    return points;
+  }
   // Collider friction (pbf_set_collider_friction): Coulomb drag against the installed collider, relative to the solid's contact
   // velocity (velocity + angular_velocity x (x - the pose's t); a body's own while a body is on), one pass after every finalise,
   // pbf_steps and graph replays included.  mu = +inf is no-slip.  Calling it again rewrites the record without a recapture.
