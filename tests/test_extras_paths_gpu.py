@@ -32,8 +32,10 @@ PATHS = [dict(gather=0), dict(gather=0, pad_lds=16384), dict(flags="NO_LDS"), di
 ALL = ("vorticity", "xsph", "surface")
 
 
-def params(pkg, name, passes=()):
-    iteration, _, force = ER.SCENES[name]
+def params(pkg, name, passes=(), iteration=None):
+    """iteration: a solver iteration count other than the scene's own"""
+    own, _, force = ER.SCENES[name]
+    iteration = own if iteration is None else iteration
     p = pkg.default_params(iteration, 1000.0)
     for c in range(3):
         p.constant_force[c] = force[c]
@@ -41,15 +43,18 @@ def params(pkg, name, passes=()):
     return p
 
 
-def run(pkg, name, fp64, fast, passes=(), path=None, stop_after_sort=False):
-    """-> the solver after the scene's warm steps (passes off) and ONE step with `passes` on"""
+def run(pkg, name, fp64, fast, passes=(), path=None, stop_after_sort=False, solids=None, iteration=None):
+    """-> the solver after the scene's warm steps (passes off) and ONE step with `passes` on; solids(s, name, fp64), when given,
+    installs what the ctx carries beside the particles, right after the upload; iteration: params()'s"""
     path = dict(path or {})
     flags = (pkg.FLAG_FAST_MATH if fast else 0) | (pkg.FLAG_NO_LDS if path.pop("flags", None) else 0)
     s = pkg.Solver(h=H, fp64=fp64, flags=flags)
     for k, v in path.items():
         s.set_option(k, v)
     s.upload(**scene(name))
-    p0 = params(pkg, name)
+    if solids:
+        solids(s, name, fp64)
+    p0 = params(pkg, name, iteration=iteration)
     warm = ER.SCENES[name][1]
     if warm:
         s.steps(p0, warm)
@@ -57,11 +62,14 @@ def run(pkg, name, fp64, fast, passes=(), path=None, stop_after_sort=False):
         return s.stage("predict", p0).stage("sort", p0)
     if "surface" in passes:
         s.set_surface_tension(ER.GAMMA, ER.BETA)
-    return s.step(params(pkg, name, passes))
+    return s.step(params(pkg, name, passes, iteration))
 
 
-def state_bytes(s, passes):
+def state_bytes(s, passes, more=None):
+    """more(s) -> further named bytes of the ctx (the records of its solids)"""
     out = {k: v.tobytes() for k, v in s.download().items()}
+    if more:
+        out.update(more(s))
     if "vorticity" in passes:
         out["omega"] = s.omega().tobytes()
     if "surface" in passes:
@@ -69,13 +77,14 @@ def state_bytes(s, passes):
     return out
 
 
-def check_against_reference(pkg, name, fp64, fast):
-    """test 1 for one scene and variant -> {record: (worst error / bar, ambiguous share)}"""
+def check_against_reference(pkg, name, fp64, fast, solids=None, also=None, iteration=None):
+    """test 1 for one scene and variant -> {record: (worst error / bar, ambiguous share)}; solids: run()'s; also(on, off, passes),
+    when given, holds whatever else a pass must leave alone; iteration: params()'s"""
     dtype = np.float64 if fp64 else np.float32
-    p = params(pkg, name)
-    off = run(pkg, name, fp64, fast)
+    p = params(pkg, name, iteration=iteration)
+    off = run(pkg, name, fp64, fast, solids=solids, iteration=iteration)
     a = off.download()
-    cut = run(pkg, name, fp64, fast, stop_after_sort=True)
+    cut = run(pkg, name, fp64, fast, stop_after_sort=True, solids=solids, iteration=iteration)
     assert np.array_equal(cut.download()["id"], a["id"])
     cells = key_cells(cut.keys())
     ps = off.pstar()[:, :3].astype(np.float64)
@@ -101,11 +110,13 @@ def check_against_reference(pkg, name, fp64, fast):
         assert not np.asarray(got)[obstacle].any(), (record, "an obstacle's record must be zero")
 
     def twin(passes):
-        on = run(pkg, name, fp64, fast, passes)
+        on = run(pkg, name, fp64, fast, passes, solids=solids, iteration=iteration)
         b = on.download()
         assert np.array_equal(a["id"], b["id"]) and np.array_equal(a["pos"], b["pos"])   # the pass runs after the solve
         assert np.array_equal(on.pstar()[:, :3], off.pstar()[:, :3])
         assert np.array_equal(a["vel"][obstacle], b["vel"][obstacle])                    # bit for bit
+        if also:
+            also(on, off, passes)
         return on, b["vel"].astype(np.float64) - vel
 
     on, dv = twin(("vorticity",))
@@ -124,15 +135,17 @@ def check_against_reference(pkg, name, fp64, fast):
     return seen
 
 
-def check_paths(pkg, name, fp64, fast, paths):
-    """test 3 for one scene and variant: every path's bytes equal the default path's, passes on and off"""
-    want_on, want_off = state_bytes(run(pkg, name, fp64, fast, ALL), ALL), state_bytes(run(pkg, name, fp64, fast), ())
+def check_paths(pkg, name, fp64, fast, paths, solids=None, more=None, iteration=None):
+    """test 3 for one scene and variant: every path's bytes equal the default path's, passes on and off; solids: run()'s,
+    more: state_bytes()'s, iteration: params()'s"""
+    want_on = state_bytes(run(pkg, name, fp64, fast, ALL, solids=solids, iteration=iteration), ALL, more)
+    want_off = state_bytes(run(pkg, name, fp64, fast, solids=solids, iteration=iteration), (), more)
     assert want_on["vel"] != want_off["vel"]
     for path in paths:
-        got_off = state_bytes(run(pkg, name, fp64, fast, (), path), ())
+        got_off = state_bytes(run(pkg, name, fp64, fast, (), path, solids=solids, iteration=iteration), (), more)
         solve = [k for k in want_off if got_off[k] != want_off[k]]
         assert not solve, (path, "the SOLVE differs from the default path's (passes off)", solve)
-        got_on = state_bytes(run(pkg, name, fp64, fast, ALL, path), ALL)
+        got_on = state_bytes(run(pkg, name, fp64, fast, ALL, path, solids=solids, iteration=iteration), ALL, more)
         passes = [k for k in want_on if got_on[k] != want_on[k]]
         assert not passes, (path, "the opt-in PASSES differ from the default path's (the solve does not)", passes)
 
