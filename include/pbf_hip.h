@@ -151,7 +151,8 @@ int pbf_set_surface_tension(pbf_ctx *ctx, double cohesion, double adhesion);
  * gives the same bytes; "coop" 2 / 4 / 8 differs at rounding level as it does without a collider.
  * Limitations: there is no restitution term — finalise derives the velocity from the projected position, as it does for
  * the box — and friction is an opt-in pass of its own (pbf_set_collider_friction below).  Whitewater's diffuse particles
- * and the observers (surface, sampling, diagnostics, anisotropy) do not see the collider.  One collider and one static scenery lattice (pbf_set_scenery below) per ctx.  A
+ * see the collider only with pbf_set_whitewater_solids on (below); the observers (surface, sampling, diagnostics,
+ * anisotropy) do not see it.  One collider and one static scenery lattice (pbf_set_scenery below) per ctx.  A
  * triangle mesh becomes a lattice through pbf_sdf_from_mesh / pbf_set_collider_mesh below.
  *
  * pbf_collider_sample is the window onto that device function, for debugging an uploaded collider: its own synchronising
@@ -209,8 +210,8 @@ int pbf_collider_sample(pbf_ctx *ctx, const pbf_params *params, size_t n, const 
  * Limitations: the wall pushes through positions and is free-slip unless pbf_set_collider_friction (below) is on, which is
  * also the only place the solid's contact velocity enters; there is no restitution, and finalise derives the velocity
  * from the projected position with the reference's damping.  There is no swept collision: a body that moves further per
- * step than its own thickness can pass through fluid.  One collider per ctx; no pose across slabs; whitewater and the
- * observers do not see the collider. */
+ * step than its own thickness can pass through fluid.  One collider per ctx; no pose across slabs; whitewater sees the
+ * posed collider only with pbf_set_whitewater_solids on (below), the observers do not see it. */
 typedef struct pbf_collider_pose {
   double rot[9];     /* row-major R, body -> world */
   double trans[3];   /* t, world */
@@ -303,8 +304,9 @@ int pbf_collider_reaction(pbf_ctx *ctx, pbf_collider_wrench *out);
  * Limitations: one body per ctx; no contact of the body with the box or with obstacles beyond the centre bounds (contact
  * with the scenery: pbf_set_collider_body_contact, below); no swept collision (a body that moves further per step than its
  * own thickness can pass through fluid); no restitution against the fluid; no gyroscopic
- * term (a spinning asymmetric body does not precess); not in slab mode; whitewater and the observers still do not see the
- * solid. */
+ * term (a spinning asymmetric body does not precess); not in slab mode; whitewater sees the body only with
+ * pbf_set_whitewater_solids on (below; diffuse particles are massless and exert nothing on it), the observers still do not
+ * see the solid. */
 typedef struct pbf_collider_body {
   double mass, inertia[3];                 /* principal moments about the centre of mass, along the lattice's axes */
   double gain;                             /* 0.49: the momentum finalise gave the fluid; 1: the position-based estimate */
@@ -554,7 +556,8 @@ int pbf_mesh_winding(pbf_ctx *ctx, const pbf_mesh *mesh, const pbf_collider_sdf 
  * outputs and refusals, PBF_ERR_STATE without scenery.
  *
  * Limitations: the body collides with the scenery only with pbf_set_collider_body_contact (below) on — otherwise only its
- * centre bounds hold it.  There is no friction of the fluid against the scenery and no reaction on it.  Whitewater's diffuse particles and the observers do not see it.  One
+ * centre bounds hold it.  There is no friction of the fluid against the scenery and no reaction on it.  Whitewater's diffuse particles see it only with
+ * pbf_set_whitewater_solids on (below); the observers do not see it.  One
  * collider and one static scenery lattice per ctx: several static solids are composed into the scenery's lattice on the
  * host, by the min of their distances.  Not in slab mode. */
 int pbf_set_scenery(pbf_ctx *ctx, const pbf_collider_sdf *sdf);   /* NULL clears and frees the lattice */
@@ -939,6 +942,71 @@ int pbf_whitewater_step(pbf_ctx *ctx, const pbf_params *params, pbf_whitewater_s
 size_t pbf_whitewater_count(const pbf_ctx *ctx);
 /* pos / vel = 3 values of N per diffuse particle, life = 1; any pointer may be NULL */
 int pbf_whitewater_download(pbf_ctx *ctx, void *pos, void *vel, void *life, uint8_t *kind, uint64_t *parent_id);
+
+/* ---- whitewater against the solids: diffuse particles collide with the collider and the scenery (opt-in) -------------
+ * A ctx that never calls pbf_set_whitewater_solids runs pbf_whitewater_step launch for launch and byte for byte as without
+ * this block.  With the setting on, every diffuse particle is projected out of the collider and then out of the scenery
+ * after its advection, its velocity gets a contact response, and no particle is left inside a solid at the end of the call.
+ * The setting is a wish: it needs no installed lattice and outlives pbf_set_collider, pbf_set_scenery, their _mesh forms,
+ * clearing, poses, bodies and friction.  Each pbf_whitewater_step collides with whichever of the two lattices is installed
+ * when it runs; with neither installed the pass is not launched.  The setting touches no collider mode and drops no captured
+ * graph (the whitewater step is never captured), and a fluid step never notices it.
+ *
+ * The contract (csrc/pbf_whitewater_solids.hpp restates it).  Everything is in N, in the order written, not contracted;
+ * PBF_FLAG_FAST_MATH does not reach it; sqrt and divide are IEEE.  Per diffuse particle after step 1 (advect) above: x its
+ * world position (clamped to the box), v its velocity in the solver frame, its alive flag, and nF exactly as the advection
+ * forms it (weight == 0 ? 0 : count[0]).  A particle that is dead on entry is skipped: nothing of it is moved or counted.
+ * e = N(restitution), f = N(friction).
+ *
+ *   q_a = x_a / scale
+ *   collider installed:  (q1, hit1) = what pbf_collider_sample computes for this q: the posed contract through the pose record
+ *                        when one is set, else the static contract;      else q1 = q, hit1 = false
+ *   scenery installed:   (q2, hit2) = the static contract on q1 with the scenery's lattice;    else q2 = q1, hit2 = false
+ *   x'_a = (hit1 || hit2) ? min(maxB_a, max(minB_a, q2_a * scale)) : x_a                       (bits kept without a hit)
+ *
+ *   response(d, vb) for a solid that moved the point by d (solver frame) and has the velocity vb there:
+ *     len = sqrt((d_x d_x + d_y d_y) + d_z d_z)      act = hit && len > 0        n_a = d_a / len
+ *     u_a = v_a - vb_a      un = (u_x n_x + u_y n_y) + u_z n_z      ut_a = u_a - un * n_a
+ *     v_a <- (act && un < 0) ? (vb_a + (1 - f) * ut_a) - (e * un) * n_a : v_a                  (bits kept otherwise)
+ *   collider first:  d = q1 - q;   r_a = q1_a * scale - t_a;   c_x = W_y r_z - W_z r_y  (y, z cyclic; each product rounded,
+ *                    one subtraction, as the friction contract forms it);   vb_a = (V_a + c_a) / scale
+ *                    V, W = N(velocity), N(angular_velocity) of the body's state as the kernel finds it while a body is on;
+ *                    else the friction record's while friction is on;  else vb = 0.
+ *                    t = the pose record's trans as the kernel finds it (no pose ever set: 0)
+ *   then scenery:    d = q2 - q1;  vb = 0, on the velocity the collider's response left
+ *   alive <- alive && !(absorb && nF == 0 && (hit1 || hit2))
+ *
+ * Life, kind and parent are untouched.  Obstacle particles play no part.  Outside a lattice nothing is loaded, NaN included.
+ * The box wins over both solids and the scenery over the collider, as in delta-p.  A receding particle (un >= 0) keeps its
+ * velocity, so spray a moving collider has just pushed is not slowed; a push the box undoes entirely (len == 0) still
+ * counts as a hit.  A child that step 4 (emit) places is projected by the same two position contracts before the call
+ * returns: its velocity and life are kept, it never dies at birth, and it counts in born_inside when either lattice hit.
+ * pbf_whitewater_stats.died includes the absorbed particles; alive + died keeps its meaning.  The call still makes exactly
+ * one read-back.  The same resident state, solids, configuration, pool and frame give the same bytes under every setting of
+ * pbf_set_option.
+ *
+ * pbf_set_whitewater_solids(ctx, NULL) turns the setting off.  PBF_ERR_INVALID, the ctx unchanged: restitution or friction
+ * outside [0, 1] or NaN, reserved != 0.  pbf_whitewater_solids_stats (an observer, synchronises): the counts of the last
+ * whitewater step — hit_collider / hit_scenery: particles alive on entry with hit1 / hit2 — and `step`, the whitewater steps
+ * run since the setting was turned on; PBF_ERR_STATE while the setting is off or no whitewater step has run since it was
+ * turned on, PBF_ERR_INVALID for out == NULL.
+ *
+ * Limitations: the observers (pbf_sample_*, the surface, the diagnostics, anisotropy) still do not see the solids; whitewater
+ * is still not available in slab mode; no swept collision (spray that crosses a solid thinner than its own step in one step
+ * passes through); the potentials ignore the solids (trapped air against a wall and obstacle particles stay as they are);
+ * diffuse particles are massless, so they exert no force or friction on a body. */
+typedef struct pbf_whitewater_solids {
+  double restitution;   /* e in [0, 1] */
+  double friction;      /* f in [0, 1]: the share of the tangential relative velocity a hit removes */
+  uint32_t absorb;      /* != 0: a diffuse particle with nF == 0 that hits a solid dies (what the box walls already do) */
+  uint32_t reserved;    /* 0 */
+} pbf_whitewater_solids;
+/* (the struct shares its name with the call that fills it, so it has no typedef: write `struct pbf_whitewater_solids_stats`) */
+struct pbf_whitewater_solids_stats {
+  uint64_t hit_collider, hit_scenery, absorbed, born_inside, step;
+};
+int pbf_set_whitewater_solids(pbf_ctx *ctx, const pbf_whitewater_solids *cfg);               /* NULL: off */
+int pbf_whitewater_solids_stats(pbf_ctx *ctx, struct pbf_whitewater_solids_stats *out);      /* observer, synchronises */
 
 /* ---- per-particle anisotropy after Yu & Turk 2013 on the resident state (no reference counterpart) --------------------
  * Yu & Turk, "Reconstructing surfaces of particle-based fluids using anisotropic kernels" (ACM TOG 32(1)): for each particle

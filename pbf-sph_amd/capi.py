@@ -142,6 +142,17 @@ class WhitewaterStats(C.Structure):
                 ("kind", C.c_uint64 * 3)]
 
 
+class WhitewaterSolids(C.Structure):
+    """pbf_whitewater_solids (include/pbf_hip.h): two doubles and two 32-bit words, 24 bytes"""
+    _fields_ = [("restitution", C.c_double), ("friction", C.c_double), ("absorb", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class WhitewaterSolidsStats(C.Structure):
+    """pbf_whitewater_solids_stats (include/pbf_hip.h): 5 eight-byte words"""
+    _fields_ = [("hit_collider", C.c_uint64), ("hit_scenery", C.c_uint64), ("absorbed", C.c_uint64),
+                ("born_inside", C.c_uint64), ("step", C.c_uint64)]
+
+
 class Anisotropy(C.Structure):
     """pbf_anisotropy (include/pbf_hip.h)"""
     _fields_ = [("smoothing", C.c_double), ("k_r", C.c_double), ("k_s", C.c_double), ("k_n", C.c_double),
@@ -338,6 +349,8 @@ _SIGS = {
     "pbf_whitewater_step": (C.c_int, [C.c_void_p, C.POINTER(Params), C.POINTER(WhitewaterStats)]),
     "pbf_whitewater_count": (C.c_size_t, [C.c_void_p]),
     "pbf_whitewater_download": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
+    "pbf_set_whitewater_solids": (C.c_int, [C.c_void_p, C.POINTER(WhitewaterSolids)]),
+    "pbf_whitewater_solids_stats": (C.c_int, [C.c_void_p, C.POINTER(WhitewaterSolidsStats)]),
     "pbf_read_buffer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "pbf_table_size": (C.c_size_t, [C.c_void_p]),
     "pbf_selftest_math": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -977,6 +990,22 @@ class Solver:
         self._chk(self.L.pbf_whitewater_download(self.ctx, _vp(o["pos"]), _vp(o["vel"]), _vp(o["life"]), _vp(o["kind"]),
                                                  _vp(o["parent_id"])), "pbf_whitewater_download")
         return o
+
+    def set_whitewater_solids(self, restitution=0.0, friction=0.0, absorb=False, off=False, reserved=0):
+        """Diffuse particles collide with the collider and the scenery from the next whitewater step on
+        (pbf_set_whitewater_solids, include/pbf_hip.h).  restitution=None or off=True turns the setting off."""
+        if off or restitution is None:
+            self._chk(self.L.pbf_set_whitewater_solids(self.ctx, None), "pbf_set_whitewater_solids")
+            return self
+        cfg = WhitewaterSolids(float(restitution), float(friction), 1 if absorb else 0, int(reserved))
+        self._chk(self.L.pbf_set_whitewater_solids(self.ctx, C.byref(cfg)), "pbf_set_whitewater_solids")
+        return self
+
+    def whitewater_solids_stats(self):
+        """The counts of the last whitewater step -> dict(hit_collider, hit_scenery, absorbed, born_inside, step)"""
+        st = WhitewaterSolidsStats()
+        self._chk(self.L.pbf_whitewater_solids_stats(self.ctx, C.byref(st)), "pbf_whitewater_solids_stats")
+        return {k: int(getattr(st, k)) for k, _ in WhitewaterSolidsStats._fields_}
 
     def whitewater_potentials(self):
         """(n,4): {I_ta, I_wc, E_k, n_d} of the last whitewater step, device order (zero for obstacles)"""

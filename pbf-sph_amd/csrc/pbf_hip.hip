@@ -24,6 +24,7 @@
 #include "pbf_tiles.hpp"
 #include "pbf_mc.hpp"
 #include "pbf_whitewater.hpp"
+#include "pbf_whitewater_solids.hpp"
 #include "pbf_anisotropy.hpp"
 #include "pbf_aniso_field.hpp"
 #include "pbf_mesh_sdf.hpp"
@@ -295,6 +296,14 @@ struct pbf_ctx {
   DevBuf wwSample, wwAlive, wwAliveOff, wwSums, wwFieldA, wwFieldB, wwPot, wwEmit, wwOffset, wwChildKind;
   Mailbox<WwRecord> hostWw;
   uint64_t wwPotAt = 0;
+  // pbf_set_whitewater_solids (csrc/pbf_whitewater_solids.hpp): a wish that outlives every solid — the setting as given, the
+  // whitewater steps run since it was turned on, the per-workgroup partial counts of its two kernels (sized to the pool's
+  // capacity: ww_solids_buffers) and the device's WwSolidsRecord.  No ColliderState mode, no graph key: the step never reads it.
+  bool wwSolidsOn = false;
+  pbf_whitewater_solids wwSolids{};
+  uint64_t wwSolidsSteps = 0;
+  bool wwSolidsFolded = false;  // the last whitewater step ran the kernels and wrote wwSolidsRec (else its counts are zero)
+  DevBuf wwSolidsPartials, wwSolidsRec;
   // pbf_anisotropy_compute (csrc/pbf_anisotropy.hpp): AnisotropyOp's outputs in one allocation sized to the capacity —
   // {centre 3, G 6, axes 9, radii 3} values of N and one uint32 per particle — made by the first call.  Scratch of an
   // observer: no step reads or writes it.
@@ -2466,6 +2475,73 @@ int ww_resize_pool(pbf_ctx *ctx, size_t cap) {
   return ensure(ctx, ctx->wwAliveOff, (cap + SCAN_TILE) * 4);
 }
 
+// pbf_set_whitewater_solids: the buffers its kernels write, allocated where the setting or the pool's capacity changes and
+// never inside a step.  Partials: 3 words per workgroup of k_ww_solids, then one per workgroup of k_ww_solids_children.
+size_t ww_solids_pool_blocks(const pbf_ctx *ctx) { return grid_for(size_t(ctx->ww.capacity)).x; }
+int ww_solids_buffers(pbf_ctx *ctx) {
+  if (!ctx->wwSolidsOn || !ctx->wwOn) return PBF_OK;
+  if (int rc = ensure(ctx, ctx->wwSolidsPartials, (3 * ww_solids_pool_blocks(ctx) + wwsolids::CHILD_BLOCKS) * 4)) return rc;
+  return ensure(ctx, ctx->wwSolidsRec, sizeof(WwSolidsRecord));
+}
+static_assert(sizeof(pbf_whitewater_solids) == 24 && sizeof(struct pbf_whitewater_solids_stats) == 5 * 8 &&
+                  sizeof(WwSolidsRecord) == sizeof(struct pbf_whitewater_solids_stats),
+              "WwSolidsRecord (pbf_whitewater_solids.hpp) is pbf_whitewater_solids_stats");
+// the solids as the whitewater kernels take them, and which instantiation reads them: bit 0 a collider, 1 its pose record,
+// 2 a solid velocity (a body, else friction), 3 the scenery.  0: neither lattice is installed, nothing is launched.
+template <typename N> int ww_solids_args(pbf_ctx *ctx, const StepConsts<N> &c, WwSolidsArgs<N> &a) {
+  const bool col = collider_on(ctx), scn = scenery_on(ctx);
+  const bool posed = col && ctx->col.posed, vel = col && (ctx->col.body || ctx->col.friction);
+  a = WwSolidsArgs<N>{};
+  if (col) a.collider = sdf_args<N>(ctx->solid[ColliderState::COLLIDER]);
+  if (scn) a.scenery = sdf_args<N>(ctx->solid[ColliderState::SCENERY]);
+  if (posed || vel) a.pose = ctx->colliderPose.as<const ColliderPose<N>>();
+  if (vel)  // (addresses only, as stage_friction forms them)
+    a.vw = ctx->col.body ? ctx->bodyRec.as<const colliderbody::Record>()->st.velocity
+                         : ctx->frictionRec.as<const pbf_collider_friction>()->velocity;
+  a.frame.scale = c.scale;
+  for (int k = 0; k < 3; ++k) a.frame.minB[k] = c.minB[k], a.frame.maxB[k] = c.maxB[k];
+  a.e = N(ctx->wwSolids.restitution), a.f = N(ctx->wwSolids.friction), a.absorb = ctx->wwSolids.absorb;
+  return int(col) | int(posed) << 1 | int(vel) << 2 | int(scn) << 3;
+}
+template <typename N>
+void ww_solids_pool(pbf_ctx *ctx, int mode, const WwSolidsArgs<N> &a, uint32_t m, const WwPool<N> &pool, const N *weight,
+                    const uint32_t *count, uint32_t *alive, uint32_t *partials) {
+#define WW_SOLIDS_CASE(COL, POSED, VEL, SCN)                                                                                  \
+  case (COL | POSED << 1 | VEL << 2 | SCN << 3):                                                                              \
+    hipLaunchKernelGGL((k_ww_solids<N, COL != 0, POSED != 0, VEL != 0, SCN != 0>), grid_for(m), dim3(BLOCK), 0, ctx->stream, \
+                       a, m, pool, weight, count, alive, partials);                                                           \
+    break;
+  switch (mode) {
+    WW_SOLIDS_CASE(0, 0, 0, 1)
+    WW_SOLIDS_CASE(1, 0, 0, 0)
+    WW_SOLIDS_CASE(1, 1, 0, 0)
+    WW_SOLIDS_CASE(1, 0, 1, 0)
+    WW_SOLIDS_CASE(1, 1, 1, 0)
+    WW_SOLIDS_CASE(1, 0, 0, 1)
+    WW_SOLIDS_CASE(1, 1, 0, 1)
+    WW_SOLIDS_CASE(1, 0, 1, 1)
+    WW_SOLIDS_CASE(1, 1, 1, 1)
+  }
+#undef WW_SOLIDS_CASE
+}
+template <typename N>
+void ww_solids_children(pbf_ctx *ctx, int mode, const WwSolidsArgs<N> &a, uint32_t n, const uint32_t *emit, const uint32_t *offset,
+                        uint32_t m, const uint32_t *alive, const uint32_t *aliveOff, uint32_t cap, vec4<N> *pos4, uint32_t *partials) {
+#define WW_SOLIDS_CASE(COL, POSED, SCN)                                                                                    \
+  case (COL | POSED << 1 | SCN << 3):                                                                                      \
+    hipLaunchKernelGGL((k_ww_solids_children<N, COL != 0, POSED != 0, SCN != 0>), dim3(wwsolids::CHILD_BLOCKS), dim3(BLOCK), \
+                       0, ctx->stream, a, n, emit, offset, m, alive, aliveOff, cap, pos4, partials);                        \
+    break;
+  switch (mode & ~4) {  // (a child's velocity is kept: no solid velocity is read)
+    WW_SOLIDS_CASE(0, 0, 1)
+    WW_SOLIDS_CASE(1, 0, 0)
+    WW_SOLIDS_CASE(1, 1, 0)
+    WW_SOLIDS_CASE(1, 0, 1)
+    WW_SOLIDS_CASE(1, 1, 1)
+  }
+#undef WW_SOLIDS_CASE
+}
+
 template <typename N, bool FAST> int whitewater_passes(pbf_ctx *ctx, const StepConsts<N> &c, uint32_t seq) {
   const int s = ctx->st.cur, ws = ctx->wwCur, wd = 1 - ws;
   const uint32_t n = uint32_t(ctx->n), m = uint32_t(ctx->wwCount), cap = uint32_t(ctx->ww.capacity);
@@ -2473,12 +2549,18 @@ template <typename N, bool FAST> int whitewater_passes(pbf_ctx *ctx, const StepC
   const WwPool<N> src = ww_pool<N>(ctx, ws), dst = ww_pool<N>(ctx, wd);
   uint32_t *alive = ctx->wwAlive.as<uint32_t>(), *aliveOff = ctx->wwAliveOff.as<uint32_t>();
   uint32_t *emit = ctx->wwEmit.as<uint32_t>(), *offset = ctx->wwOffset.as<uint32_t>();
+  // pbf_set_whitewater_solids: the pool against the lattices installed right now (solidsMode 0: none, nothing more is launched)
+  WwSolidsArgs<N> solids{};
+  const int solidsMode = ctx->wwSolidsOn ? ww_solids_args<N>(ctx, c, solids) : 0;
+  uint32_t *poolPartials = ctx->wwSolidsPartials.as<uint32_t>();
+  uint32_t *childPartials = ctx->wwSolidsOn ? poolPartials + 3 * ww_solids_pool_blocks(ctx) : nullptr;
   if (m) {  // 1: advect what is in the pool on the state the last step left
     const SampleOut<N> out = SamplePlanes(cap, sizeof(N), /*withColour=*/false).in<N>(ctx->wwSample);
     const WwPoolSource<N> from{src.pos4, m};
     if (int rc = launch_sample<N, FAST>(ctx, c, from, m, SAMPLE_VELOCITY, out)) return rc;
     hipLaunchKernelGGL((k_ww_advect<N>), grid_for(m), dim3(BLOCK), 0, ctx->stream, c, w, m, src, out.weight, out.mv, out.count,
                        alive);
+    if (solidsMode) ww_solids_pool<N>(ctx, solidsMode, solids, m, src, out.weight, out.count, alive, poolPartials);
     LAUNCH_CHECK(ctx);
   }
   if (n) {  // 2, 3: normals into the whitewater state's own fields, then the potentials and the child counts
@@ -2512,6 +2594,12 @@ template <typename N, bool FAST> int whitewater_passes(pbf_ctx *ctx, const StepC
     hipLaunchKernelGGL((k_ww_emit<N>), grid_for(n), dim3(BLOCK), 0, ctx->stream, c, w, ctx->pos4[s].as<const vec4<N>>(),
                        ctx->vel4[s].as<const vec4<N>>(), ctx->id[s].as<const uint64_t>(), ctx->wwPot.as<const vec4<N>>(), emit,
                        offset, ctx->wwChildKind.as<const uint8_t>(), m, alive, aliveOff, cap, dst);
+  if (n && solidsMode) ww_solids_children<N>(ctx, solidsMode, solids, n, emit, offset, m, alive, aliveOff, cap, dst.pos4, childPartials);
+  if (solidsMode)
+    hipLaunchKernelGGL(k_ww_solids_fold, dim3(1), dim3(BLOCK), 0, ctx->stream, m ? grid_for(m).x : 0u, poolPartials,
+                       n ? wwsolids::CHILD_BLOCKS : 0u, childPartials, (unsigned long long)(ctx->wwSolidsSteps + 1),
+                       ctx->wwSolidsRec.as<WwSolidsRecord>());
+  ctx->wwSolidsFolded = solidsMode != 0;  // (no lattice: nothing was launched, and the stats are zero on the host's side)
   hipLaunchKernelGGL(k_ww_final, dim3(1), dim3(BLOCK), 0, ctx->stream, n, emit, offset, m, alive, aliveOff, cap, dst.kind,
                      ctx->hostWw.rec.p, seq);
   LAUNCH_CHECK(ctx);
@@ -2531,6 +2619,7 @@ template <typename N> int whitewater_step_impl(pbf_ctx *ctx, const pbf_params *p
   pbf_whitewater_stats st;
   if (int rc = receive(ctx, ctx->hostWw, "whitewater read-back", st)) return rc;
   ctx->wwCount = size_t(st.alive), ctx->wwCur = 1 - ctx->wwCur, ctx->wwFrame++;
+  if (ctx->wwSolidsOn) ctx->wwSolidsSteps++;
   ctx->wwPotAt = ctx->n ? ctx->orderEpoch : 0;
   if (out) *out = st;
   return PBF_OK;
@@ -3283,7 +3372,45 @@ int pbf_whitewater_configure(pbf_ctx *ctx, const pbf_whitewater *config) {
     ctx->wwPotAt = 0;
     return PBF_OK;
   }
+  if (int rc = ww_solids_buffers(ctx)) return rc;  // (pbf_set_whitewater_solids: its partials follow the capacity)
   return ensure_whitewater_fields(ctx);
+}
+
+// pbf_set_whitewater_solids: a wish — no lattice is needed, no ColliderState mode is touched and no captured graph dropped
+int pbf_set_whitewater_solids(pbf_ctx *ctx, const pbf_whitewater_solids *cfg) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!cfg) {
+    ctx->wwSolidsOn = false, ctx->wwSolidsSteps = 0;
+    return PBF_OK;
+  }
+  const char *why = nullptr;
+  if (wwsolids::check(cfg, &why) != PBF_OK) return fail(ctx, PBF_ERR_INVALID, why);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const bool was = ctx->wwSolidsOn;
+  ctx->wwSolidsOn = true;
+  if (int rc = ww_solids_buffers(ctx)) {
+    ctx->wwSolidsOn = was;
+    return rc;
+  }
+  ctx->wwSolids = *cfg;
+  if (!was) ctx->wwSolidsSteps = 0;
+  return PBF_OK;
+}
+
+int pbf_whitewater_solids_stats(pbf_ctx *ctx, struct pbf_whitewater_solids_stats *out) {
+  if (!ctx) return PBF_ERR_INVALID;
+  if (!out) return fail(ctx, PBF_ERR_INVALID, "pbf_whitewater_solids_stats: out == NULL");
+  if (!ctx->wwSolidsOn) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_solids_stats: the setting is off (pbf_set_whitewater_solids)");
+  if (!ctx->wwSolidsSteps) return fail(ctx, PBF_ERR_STATE, "pbf_whitewater_solids_stats: no whitewater step since the setting was turned on");
+  if (!ctx->wwSolidsFolded) {  // the last step found no lattice and launched nothing: there is nothing to copy
+    out->hit_collider = out->hit_scenery = out->absorbed = out->born_inside = 0;
+    out->step = ctx->wwSolidsSteps;
+    return PBF_OK;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->wwSolidsRec.p, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return PBF_OK;
 }
 
 int pbf_whitewater_upload(pbf_ctx *ctx, size_t n, const void *pos, const void *vel, const void *life) {

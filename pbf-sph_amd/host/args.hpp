@@ -70,6 +70,10 @@ struct Args {
   size_t colliderFrictionReport = 0;      // 0 = off
   double wwTa = 0, wwWc = 0;              // --whitewater=k_ta,k_wc[,capacity]: spray / foam / bubbles (Ihmsen 2012) with --resident
   size_t wwCapacity = 0;                  // 0 = off
+  // --whitewater-solids[=restitution[,friction[,absorb]]] with --whitewater: the diffuse particles collide with the collider
+  // and the scenery (pbf_set_whitewater_solids); the whitewater report then carries the four counts of the last step
+  bool wwSolids = false;
+  double wwSolidsCfg[3] = {0, 0, 0};      // restitution, friction, absorb
   bool anisotropy = false;                // --anisotropy[=smoothing,k_r,k_s,k_n,min_neighbours]: ellipsoids.ply (Yu & Turk 2013) with --resident
   double anisoCfg[4] = {0.9, 4.0, 20.0 / 3.0, 0.5};
   unsigned anisoMinNeighbours = 25;
@@ -171,6 +175,10 @@ struct Args {
           "                                        the 10 % / 90 % quantiles of the potentials at the first frame. Pool of\n"
           "                                        `capacity` particles (default 262144); whitewater.ply beside cloud.ply.\n"
           "                                        Single device only\n"
+          "      --whitewater-solids[=e[,f[,absorb]]]  With --whitewater: spray, foam and bubbles collide with --collider and\n"
+          "                                        --scenery: projected out after their advection, restitution e and tangential\n"
+          "                                        loss f in [0, 1] (defaults 0, 0); absorb = 1: spray outside the fluid dies on\n"
+          "                                        a solid. The whitewater report gains the step's four counts\n"
           "      --anisotropy[=s,k_r,k_s,k_n,N]    With --resident: smoothed centres and anisotropy (Yu & Turk 2013) of the final\n"
           "                                        state, computed on the device; ellipsoids.ply beside cloud.ply (centre, three\n"
           "                                        radii, three axes and the neighbour count per fluid particle). Defaults:\n"
@@ -309,6 +317,15 @@ struct Args {
           const auto f = numbers(v);
           if (f.size() != 3) throw std::runtime_error("--probe: expected x,y,z");
           probes.push_back({f[0], f[1], f[2]});
+        }
+        else if (a == "--whitewater-solids") wwSolids = true;
+        else if (a.rfind("--whitewater-solids=", 0) == 0) {
+          const auto f = numbers(a.substr(20));
+          if (f.empty() || f.size() > 3) throw std::runtime_error("--whitewater-solids: expected restitution[,friction[,absorb]]");
+          if (!(f[0] >= 0 && f[0] <= 1) || (f.size() >= 2 && !(f[1] >= 0 && f[1] <= 1)) || (f.size() == 3 && f[2] != 0 && f[2] != 1))
+            throw std::runtime_error("--whitewater-solids: restitution and friction in [0, 1], absorb 0 or 1");
+          wwSolids = true;
+          for (size_t k = 0; k < f.size(); ++k) wwSolidsCfg[k] = f[k];
         }
         else if (value(i, a, "", "--whitewater", v)) {
           const auto f = numbers(v);

@@ -186,6 +186,10 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     return 1;
   }
   if (whitewater && !args.resident) std::cout << "--whitewater takes effect with --resident: ignored" << std::endl;
+  if (args.wwSolids && !whitewater) {
+    std::cerr << "--whitewater-solids needs --whitewater: it is the diffuse particles that collide with the solids" << std::endl;
+    return 1;
+  }
   if (args.anisotropy && (slabbed || args.allDevices || args.slabs > 0)) {
     std::cerr << "--anisotropy is a single-device feature: it cannot be combined with --slabs / --all-devices" << std::endl;
     return 1;
@@ -355,11 +359,17 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
   // quantiles; every frame after its fluid step runs one whitewater step
   pbf_whitewater ww{};
   bool wwConfigured = false;
+  size_t wwSteps = 0;  // whitewater steps run: the solids' counts exist only after one
   if (whitewater && args.resident) {
     ww.capacity = args.wwCapacity, ww.seed = 1;
     ww.tau_ta[1] = ww.tau_wc[1] = ww.tau_k[1] = 1.0;
     ww.lifetime[0] = 2.0, ww.lifetime[1] = 5.0, ww.k_b = 2.0, ww.k_d = 0.8, ww.spray_below = 6, ww.bubble_from = 20;
     solver.whitewater(ww);
+    if (args.wwSolids) {
+      pbf_whitewater_solids ws{};
+      ws.restitution = args.wwSolidsCfg[0], ws.friction = args.wwSolidsCfg[1], ws.absorb = args.wwSolidsCfg[2] != 0 ? 1u : 0u;
+      solver.setWhitewaterSolids(&ws);
+    }
   }
   auto one = [&](size_t frame) {
     if (args.resident) {
@@ -380,6 +390,7 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
       solver.step(frameParam(frame), scene);
       if (whitewater && solver.count()) {
         solver.whitewaterStep(frameParam(frame));
+        ++wwSteps;
         if (!wwConfigured) {
           solver.whitewaterQuantileTaus(ww);
           ww.k_ta = args.wwTa, ww.k_wc = args.wwWc;
@@ -554,6 +565,11 @@ template <typename N> int run(sph::driver::Args args, const std::vector<int> &de
     diffuse = solver.whitewaterParticles();
     std::cout << "Whitewater           : " << w.alive << " alive (" << w.kind[0] << " spray, " << w.kind[1] << " foam, " << w.kind[2]
               << " bubble), last frame: " << w.emitted << " emitted, " << w.dropped << " dropped, " << w.died << " died\n";
+    if (args.wwSolids && wwSteps) {
+      const auto s = solver.whitewaterSolidsStats();
+      std::cout << "Whitewater solids    : last frame: " << s.hit_collider << " hit the collider, " << s.hit_scenery << " hit the scenery, "
+                << s.absorbed << " absorbed, " << s.born_inside << " born inside (" << s.step << " steps)\n";
+    }
   }
   if (args.indexedMesh)
     std::cout << "Indexed mesh         : " << imesh.vs.size() << " vertices, " << imesh.tris.size() / 3 << " triangles\n";

@@ -905,6 +905,19 @@ public:
     return whitewaterStats_;
   }
   const pbf_whitewater_stats &whitewaterStats() const { return whitewaterStats_; }  // the record of the last whitewater step
+  // The diffuse particles collide with the collider and the scenery (pbf_set_whitewater_solids, include/pbf_hip.h): a wish
+  // that needs no installed solid and outlives them all.  NULL turns it off.  whitewaterSolidsStats(): the counts of the last
+  // whitewater step (synchronises).
+  Solver &setWhitewaterSolids(const pbf_whitewater_solids *config) {
+    if (multi()) throw std::runtime_error("whitewater is a single-device feature");
+    check(pbf_set_whitewater_solids(ctx_, config), "pbf_set_whitewater_solids");
+    return *this;
+  }
+  struct pbf_whitewater_solids_stats whitewaterSolidsStats() {
+    struct pbf_whitewater_solids_stats s {};
+    check(pbf_whitewater_solids_stats(ctx_, &s), "pbf_whitewater_solids_stats");
+    return s;
+  }
   WhitewaterParticles<N, V> whitewaterParticles() {
     WhitewaterParticles<N, V> o;
     const size_t n = pbf_whitewater_count(ctx_);
